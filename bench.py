@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BEOM time-step throughput on MI355X (contract: see README / DESIGN.md §6).
 
-  python bench.py --gpus N --steps K --warmup W [--case headline|sill4|beach8|jet]
+  python bench.py --gpus N --steps K --warmup W [--case headline|sill4|beach8|jet] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one model time step (update_h → update_mont_rvor_pvor_dive_kine →
@@ -19,6 +19,12 @@ disagrees with --gpus is an error.  torch.distributed (gloo) carries only the co
 the RCCL unique id, barriers, the max over ranks.
 
 Prints ONE JSON line (rank 0).
+
+A plain run only sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline figure does
+not need: the CPU baseline (cpu_baseline), the check of the state after the timed region and, N > 1, the bitwise check
+of the cut step against the plain exchange.  `--dump-outputs DIR` writes the prognostic fields after the last timed step
+as DIR/<field>.npy (float64, layers x cells [x time levels]; a fixed seeded sample of the cells where the frame holds more
+than DUMP_BYTES).
 """
 from __future__ import annotations
 
@@ -47,6 +53,10 @@ KERNEL_ORDER = ("update_h", "update_mont", "update_viscosity", "update_u", "upda
                 "update_mont+update_viscosity", "update_u+update_v", "(unused)")
 NCLS = len(KERNEL_ORDER)
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: 8.0 TB/s spec (≈6.3 TB/s achievable)
+# --dump-outputs: everything that determines the future of a run (v_cc/v_ll are not kept by the fused sweeps)
+DUMP_FIELDS = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy")
+DUMP_BYTES = 48 << 20         # FP64 values written in all, at most
+DUMP_SEED = 12345             # the cells sampled when a frame holds more than that
 
 CASES = {
     # name: (recipe factory, description) — BASELINE.json configs; sizes overridable with --lm/--mm/--nlay
@@ -71,7 +81,14 @@ def parse():
     ap.add_argument("--lm", type=int, default=0)
     ap.add_argument("--mm", type=int, default=0)
     ap.add_argument("--nlay", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline (unless "
+                         "--no-cpu-baseline), the state after the timed region (finite, checksums) and, N > 1, the cut step "
+                         "against the plain exchange bit for bit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write %s as DIR/<field>.npy (float64, layers x cells [x time levels]; a fixed "
+                         "seeded sample of the cells where all of them would exceed %d MiB)" % ("/".join(DUMP_FIELDS), DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample", default="1024x1024x4")
     ap.add_argument("--prewarm-s", type=float, default=1.0,
                     help="seconds of untimed stepping before the W warm-up steps (clocks settle); the initial state is "
@@ -85,7 +102,10 @@ def parse():
     ap.add_argument("--force-bands", action="store_true",
                     help="rehearsal on one GPU: take the N > 1 path (rows from the recipe, beom_multi_create_local, RCCL) "
                          "with a single band; with --case jet the ring then closes on itself over RCCL")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def cpu_baseline(sample: str):
@@ -158,6 +178,57 @@ def gpu_sensors(pci: str | None) -> dict:
     return out
 
 
+def dump_cells(p, levels: int):
+    """Packed cells (1..ndeg; 0 is the land sentinel) that --dump-outputs writes: all of them where every field fits in
+    DUMP_BYTES (`levels` = FP64 values per cell and layer over DUMP_FIELDS, time levels included), else the same seeded
+    sample in every run, ascending."""
+    import numpy as np
+    n = DUMP_BYTES // (8 * p.nlay * levels)
+    if p.ndeg <= n:
+        return np.arange(1, p.ndeg + 1)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(p.ndeg, n, replace=False)) + 1
+
+
+def dump_outputs(out_dir, eng, p, geom, world, rank, dist):
+    """DUMP_FIELDS at dump_cells() as out_dir/<field>.npy, float64 (nlay, cells[, time levels]).  geom None: the handle
+    holds the whole frame.  Else this rank's band (owned rows; band 0 of a ring also the companion frame's row mm+1) goes
+    to rank 0."""
+    import numpy as np
+    tail = {k: getattr(eng.f, k).shape[2:] for k in DUMP_FIELDS}            # rs_h, dmdx, dmdy keep time levels
+    cells = dump_cells(p, sum(int(np.prod(t)) for t in tail.values()))
+    if geom is None:
+        vals = {k: eng.download((k,))[k][:, cells] for k in DUMP_FIELDS}      # one field at a time: host memory
+    else:
+        L = geom.L
+        band, orphan = eng.download(DUMP_FIELDS, orphan=True)
+        la, _ = geom.local_rows(geom.own0, geom.own1)
+        lo, hi = 1 + (geom.own0 - 1) * L, 1 + geom.own1 * L                  # packed range of the owned rows, whole frame
+        sel = np.nonzero((cells >= lo) & (cells < hi))[0]
+        parts = [(sel, {k: band[k][:, la + cells[sel] - lo] for k in DUMP_FIELDS})]
+        if orphan is not None:
+            lo = 1 + p.mm * L
+            sel = np.nonzero(cells >= lo)[0]
+            parts.append((sel, {k: orphan[k][:, 1 + cells[sel] - lo] for k in DUMP_FIELDS}))
+        del band, orphan
+        if world > 1:
+            gathered = [None] * world if rank == 0 else None
+            dist.gather_object(parts, gathered, dst=0)
+            parts = [x for g in gathered for x in g] if rank == 0 else []
+        if rank != 0:
+            return cells.size
+        vals = {k: np.empty((p.nlay, cells.size) + tail[k]) for k in DUMP_FIELDS}
+        seen = np.zeros(cells.size, dtype=bool)
+        for sel, v in parts:
+            seen[sel] = True
+            for k in DUMP_FIELDS:
+                vals[k][:, sel] = v[k]
+        if not seen.all():
+            raise RuntimeError("bench.py: --dump-outputs: %d sampled cells belong to no band" % int((~seen).sum()))
+    for k in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(vals[k], dtype=np.float64))
+    return cells.size
+
+
 def main():
     a = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -175,8 +246,10 @@ def main():
     # the CPU leg first: no process of this job has touched a GPU yet when the reference binary is started
     # (N > 1: the other ranks wait in the rendezvous meanwhile — before anything is timed)
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.cpu_sample)
+    if rank == 0 and a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
 
     # Libraries underneath (RCCL prints a version banner at communicator creation) write to fd 1: the ONE line this
     # script owes its caller goes to the real stdout, everything else to stderr
@@ -310,22 +383,25 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # N > 1: on THIS machine the overlapped form (split steps around the exchange in flight) must reproduce the
+    # N > 1, --full: on THIS machine the overlapped form (split steps around the exchange in flight) must reproduce the
     # plain form (every step waits for its ghosts) bit for bit on every band
     if banded:
-        names = ("hlay", "u", "v", "h_u", "h_v")
-        eng.set_option("overlap", 0)
-        eng.step(1, 9)
-        plain = eng.download(names)
-        reset()
-        eng.set_option("overlap", 1)
-        eng.step(1, 9)
-        over = eng.download(names)
-        same = all(np.array_equal(plain[k], over[k]) for k in names)
-        halo["overlap_verified_bitwise_vs_plain_exchange"] = all_min(same)
-        halo["band_steps_split_vs_plain"] = eng.stats()
-        del plain, over
-        reset()
+        cut_ok = True
+        halo["overlap_verified_bitwise_vs_plain_exchange"] = None
+        if a.full:
+            names = ("hlay", "u", "v", "h_u", "h_v")
+            eng.set_option("overlap", 0)
+            eng.step(1, 9)
+            plain = eng.download(names)
+            reset()
+            eng.set_option("overlap", 1)
+            eng.step(1, 9)
+            over = eng.download(names)
+            same = all(np.array_equal(plain[k], over[k]) for k in names)
+            cut_ok = halo["overlap_verified_bitwise_vs_plain_exchange"] = all_min(same)
+            halo["band_steps_split_vs_plain"] = eng.stats()
+            del plain, over
+            reset()
         # which form is faster on THIS machine: the step cut boundary first (edge strips, packing and the exchange inside the
         # interior rows of the momentum sweep) or the step in one piece with the exchange behind it?  Over a wire the cut form
         # hides the transfer; over a loop-back (one rank) there is nothing to hide.  20 + 60 steps each, untimed region.
@@ -344,9 +420,9 @@ def main():
                 dtq = float(tt.item())
             form_ms[name] = dtq / 60 * 1e3
             reset()
-        use_cut = halo["overlap_verified_bitwise_vs_plain_exchange"] and form_ms["cut"] <= form_ms["whole"]
+        use_cut = cut_ok and form_ms["cut"] <= form_ms["whole"]
         if os.environ.get("BEOM_BENCH_FORM") in ("cut", "whole"):
-            use_cut = os.environ["BEOM_BENCH_FORM"] == "cut" and halo["overlap_verified_bitwise_vs_plain_exchange"]
+            use_cut = os.environ["BEOM_BENCH_FORM"] == "cut" and cut_ok
         eng.set_option("overlap", 1 if use_cut else 0)
         halo["step_form"] = {"chosen": "cut boundary first (exchange inside the interior rows of the momentum sweep)" if use_cut
                              else "whole step, exchange behind it", "ms_per_step_probe": form_ms}
@@ -440,19 +516,26 @@ def main():
         except Exception:
             pass
 
-    # the state after the timed region: finite, and a checksum of hlay, u, v (sum of |x| per field, over the owned rows of all ranks)
-    after = eng.download(("hlay", "u", "v"))
-    if banded and not a.single_process:
-        la, lb = geom.local_rows(geom.own0, geom.own1)
-        after = {k: v[:, la:lb] for k, v in after.items()}
-    finite = all(bool(np.isfinite(v).all()) for v in after.values())
-    sums = [float(np.abs(after[k]).sum()) for k in ("hlay", "u", "v")]
-    if world > 1:
-        tt = torch.tensor(sums + [1.0 if finite else 0.0], dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.SUM)
-        sums, finite = [float(x) for x in tt[:3]], float(tt[3]) == float(world)
-    state_check = {"finite": finite, "sum_abs": dict(zip(("hlay", "u", "v"), sums)), "after_steps": W + K}
-    del after
+    # --full: the state after the timed region: finite, and a checksum of hlay, u, v (sum of |x| per field, over the owned
+    # rows of all ranks)
+    state_check = None
+    if a.full:
+        after = eng.download(("hlay", "u", "v"))
+        if banded and not a.single_process:
+            la, lb = geom.local_rows(geom.own0, geom.own1)
+            after = {k: v[:, la:lb] for k, v in after.items()}
+        finite = all(bool(np.isfinite(v).all()) for v in after.values())
+        sums = [float(np.abs(after[k]).sum()) for k in ("hlay", "u", "v")]
+        if world > 1:
+            tt = torch.tensor(sums + [1.0 if finite else 0.0], dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.SUM)
+            sums, finite = [float(x) for x in tt[:3]], float(tt[3]) == float(world)
+        state_check = {"finite": finite, "sum_abs": dict(zip(("hlay", "u", "v"), sums)), "after_steps": W + K}
+        del after
+
+    n_dumped = None
+    if a.dump_outputs:
+        n_dumped = dump_outputs(a.dump_outputs, eng, p, geom if banded and not a.single_process else None, world, rank, dist)
 
     out = {
         "metric": "cell-layer updates/s", "value": value, "unit": "cell-layer updates/s",
@@ -465,11 +548,14 @@ def main():
                    "dense_fast_path": bool(dense), "setup_s": round(t_setup, 1),
                    "prewarm": {"seconds": a.prewarm_s, "steps": prewarm_steps,
                                "note": "untimed; the initial state is uploaded again before the W warm-up steps"},
-                   "gpu_at_start": s0, "gpu_at_end": s1, "state_after_timed_region": state_check},
+                   "gpu_at_start": s0, "gpu_at_end": s1, "full": bool(a.full), "state_after_timed_region": state_check},
         "roofline": roof,
     }
     if halo:
         out["config"]["halo"] = halo
+    if a.dump_outputs:
+        out["config"]["dump_outputs"] = {"dir": a.dump_outputs, "fields": list(DUMP_FIELDS), "cells": int(n_dumped),
+                                         "after_steps": W + K}
     out["cpu_baseline"] = cpu
     sys.stdout.flush()
     os.dup2(real_stdout, 1)

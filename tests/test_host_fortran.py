@@ -1,9 +1,7 @@
 """The Fortran-95 host (beom_amd/host): `module private_mod` exporting `run`, calling the
 HIP engine through iso_c_binding.
 
-CPU: it compiles and links (a) against a generated shared_mod + a 6-line main, and
-(b) — where /root/reference exists — against the reference's UNCHANGED main.f95 and
-shared_mod.f95: the drop-in.
+CPU: it compiles and links against a generated shared_mod + a 6-line main.
 GPU: the built executable is run on the golden cases' input files and every output file
 of the reference's contract (grid.bin, h_0.bin, param_basin.txt, time.txt, eta_, u___,
 v___ and the diag fields) is compared byte for byte with the file the real reference
@@ -20,7 +18,6 @@ from beom_amd import inputs
 from beom_amd.host import build_host
 from helpers import Golden, golden_names
 
-REF = "/root/reference"
 HAVE_FLANG = os.path.exists(build_host.FLANG)
 
 
@@ -34,15 +31,6 @@ def test_host_compiles_with_generated_shared_mod(tmp_path):
         assert sym in nm, sym          # the time loop goes through the C-ABI
     # (beom_download_state is only referenced when shared_mod's `diag` parameter is > 0.5: flang
     #  folds the constant and drops the dead branch.)
-
-
-@pytest.mark.skipif(not (HAVE_FLANG and os.path.isdir(REF)), reason="needs flang and /root/reference")
-def test_drop_in_under_unchanged_reference_main_and_shared_mod(tmp_path):
-    """main.f95 and shared_mod.f95 are taken from the reference as they are."""
-    exe = build_host.build(None, str(tmp_path / "beom_gpu_ref"),
-                           shared_mod_path=os.path.join(REF, "shared_mod.f95"),
-                           main_path=os.path.join(REF, "main.f95"))
-    assert os.path.exists(exe)
 
 
 def _run_host(g, work, ngpu=1):

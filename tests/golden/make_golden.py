@@ -78,10 +78,56 @@ def case_island(nlay=3):
     return p, {"h_bo": h_bo, "init": init, "taus": taus, "hdot": hdot, "bodf": bodf, "fcor": fcor}
 
 
-def case_tide():
+def case_island_deep(nlay=10):
+    """Closed island basin with a column of more layers than the fused sweeps take (nlay > 8: per-layer Montgomery and
+    viscosity launches next to the fused u+v sweep); topl spread over the whole column, wind, drag and Leith viscosity."""
+    lm, mm = 14, 11
+    h_bo = np.zeros((lm + 2, mm + 2))
+    h_bo[1:-1, 1:-1] = 500.0
+    x = np.arange(lm + 2)[:, None]; y = np.arange(mm + 2)[None, :]
+    h_bo[1:-1, 1:-1] -= 120.0 * np.exp(-((x - 4.0) ** 2 + (y - 3.0) ** 2) / 12.0)[1:-1, 1:-1]
+    h_bo[6:9, 5:8] = 0.0          # island
+    h_bo[1:4, mm - 2:mm + 1] = 0.0    # land in the NW corner -> bay
+    h_bo[11, 1:5] = 0.0           # peninsula
+    ndeg = I.get_nbr_deg_freedom(h_bo)
+    xc = (x - 0.5 * (lm + 1)) * np.ones((1, mm + 2)); yc = (y - 0.5 * (mm + 1)) * np.ones((lm + 2, 1))
+    mound = 0.8 * np.exp(-(xc ** 2 + yc ** 2) / 10.0)
+    topl = list(np.linspace(0.0, 0.7, nlay))
+    n = np.zeros((lm + 2, mm + 2, nlay)); u = np.zeros_like(n); v = np.zeros_like(n)
+    for k in range(nlay):
+        n[:, :, k] = mound * (1.0 - topl[k]) * (1.0 if k == 0 else -2.0)
+    u[:, :, 0] = 0.05 * np.sin(0.5 * yc)
+    v[:, :, nlay - 1] = -0.03 * np.cos(0.4 * xc)
+    u[:, :, nlay // 2] = 0.02 * np.cos(0.3 * yc)
+    init = np.stack([n, u, v], axis=3)
+    init[h_bo == 0.0] = 0.0
+    taus = np.zeros((lm + 2, mm + 2, 2))
+    taus[:, :, 0] = 0.1 * np.cos(np.pi * yc / mm)
+    taus[:, :, 1] = 0.02 * np.sin(np.pi * xc / lm)
+    fcor = 1.0e-4 + 2.0e-11 * 5.0e3 * yc
+    dl = 5.0e3
+    cext = np.sqrt(9.8 * h_bo.max())
+    dt = 0.5 * dl / cext
+    p = make_params(lm, mm, nlay, ndeg, dl, cext, 1.0e-4, list(np.linspace(1026.0, 1028.0, nlay)), topl,
+                    12 * dt / 86400.0, 4 * dt / 86400.0, 6.4 * dt / 86400.0, 0.0, 5.0, 0.3, 2.5e-3,
+                    1.0, 10.0, 10.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0,
+                    desc="golden: island, %d layers, wind, quadratic drag, Leith" % nlay)
+    return p, {"h_bo": h_bo, "init": init, "taus": taus, "fcor": fcor}
+
+
+def case_sill_deep(nlay=16):
+    """Outcropping sill with nudged northern and southern sponges and a column of 16 layers (BEOM_MAX_LAYERS): the
+    interfaces spread over the upper 60 % of the deepest water column, so the deep ones outcrop on the sill."""
+    from beom_amd.params import format_like_print_params
+    p, f = I.case_sill_exchange3d(lm=5, mm=17, nlay=nlay, dt_s=0.01, npts=3, sill_halfwidth=3.0)
+    topl = format_like_print_params("topl", np.linspace(0.0, 0.6, nlay))[2:-2].split(",")
+    return p.replace(topl=topl), f
+
+
+def case_tide(lm=20, mm=9):
     """Nudged western boundary with a tidal constituent in eta and u (cos path,
     private_mod.f95:1453-1454,1538-1539,1632-1634)."""
-    lm, mm, nlay = 20, 9, 2
+    nlay = 2
     h_bo = np.zeros((lm + 2, mm + 2)); h_bo[1:-1, 1:-1] = 80.0
     ndeg = I.get_nbr_deg_freedom(h_bo)
     nudg = np.zeros((lm + 2, mm + 2, 3))
@@ -99,9 +145,9 @@ def case_tide():
     return p, {"h_bo": h_bo, "nudg": nudg, "tide": tide, "init": init}
 
 
-def case_3d_variant():
+def case_3d_variant(lm=24, mm=11):
     """private_mod3d.f95 epilogue (:1635-1683): 3 layers, eta nudging on both halves."""
-    lm, mm, nlay = 24, 11, 3
+    nlay = 3
     h_bo = np.zeros((lm + 2, mm + 2)); h_bo[1:-1, 1:-1] = 900.0
     ndeg = I.get_nbr_deg_freedom(h_bo)
     nudg = np.zeros((lm + 2, mm + 2, 3))
@@ -110,7 +156,7 @@ def case_3d_variant():
         nudg[lm + 1 - i, :, 0] = 0.04 * (6 - i)
     nudg[0:3, :, 1] = 0.02       # a nudged western segment must exist (:1226-1231)
     init = np.zeros((lm + 2, mm + 2, nlay, 3))
-    x = (np.arange(lm + 2) - 12.0)[:, None] * np.ones((1, mm + 2))
+    x = (np.arange(lm + 2) - lm // 2)[:, None] * np.ones((1, mm + 2))
     init[:, :, 1, 0] = 20.0 * np.tanh(x / 4.0)
     init[:, :, 2, 0] = -150.0 * (x > 3)          # makes hlay(:,3) straddle 20*hsal on the east side
     cext = np.sqrt(9.8 * 900.0); dl = 1.0e3; dt = 0.5 * dl / cext
@@ -296,6 +342,9 @@ CASES = {
     # ocrp = 1, since the operators are set up inside get_equilibrium_thickness_h_0, :505-563; g_fb = 1 is overridden, :1880)
     "rigid_lid_sill_2l": (lambda: (lambda pf: (pf[0].replace(rgld="1."), pf[1]))(
         I.case_sill_exchange3d(lm=24, mm=31, nlay=2, dt_s=0.01, npts=5, sill_halfwidth=6.0)), "private_mod.f95"),
+    # columns of more than 8 layers (up to BEOM_MAX_LAYERS = 16)
+    "island_10l_deep": (case_island_deep, "private_mod.f95"),
+    "sill_16l_ocrp": (case_sill_deep, "private_mod.f95"),
     "rigid_lid_closed_3l_wind": (lambda: (lambda pf: (pf[0].replace(rgld="1.", ocrp="1.", bdrg="2.e-4", tauw=["0.05", "0.02"], g_fb="0."), pf[1]))(
         _short(I.case_conservation(lx=200.0e3, nlay=3, outc=1, xper=0, yper=0))), "private_mod.f95"),
 }

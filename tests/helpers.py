@@ -2,11 +2,11 @@
 reference by tests/golden/make_golden.py) and comparisons."""
 from __future__ import annotations
 
+import contextlib
+import copy
 import glob
 import json
 import os
-
-import copy
 
 import numpy as np
 
@@ -77,3 +77,29 @@ def maxrel(a, b):
     a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
     scale = max(float(np.max(np.abs(b))), 1e-300)
     return float(np.max(np.abs(a - b))) / scale
+
+
+def land_mask(p, ragged):
+    """An island, and with `ragged` a ragged coast in the south-eastern corner (one cell in seven left wet)."""
+    x = np.arange(p.lm + 2)[:, None]; y = np.arange(p.mm + 2)[None, :]
+    land = ((x - 0.3 * p.lm) ** 2 + (y - 0.55 * p.mm) ** 2) < (0.12 * p.lm) ** 2          # an island
+    if ragged:
+        land = land | ((x > 0.8 * p.lm) & (y < 0.3 * p.mm) & ((x + y) % 7 != 0))         # a ragged corner
+    return land
+
+
+@contextlib.contextmanager
+def tile_geometry(rows):
+    """Forces the tile geometry of the tiled sweeps (rows = 4: 64 x 4 tiles, one row per thread; rows = 8: 64 x 8 tiles, two
+    rows per thread) for the handles created inside the block: BEOM_TILE4 is read when a handle is created.  The previous
+    value is restored on exit, after an exception too."""
+    assert rows in (4, 8), rows
+    old = os.environ.get("BEOM_TILE4")
+    os.environ["BEOM_TILE4"] = "1" if rows == 4 else "0"
+    try:
+        yield rows
+    finally:
+        if old is None:
+            os.environ.pop("BEOM_TILE4", None)
+        else:
+            os.environ["BEOM_TILE4"] = old

@@ -8,7 +8,7 @@ import pytest
 
 import oracle_lib
 from beom_amd import capi
-from helpers import GOLDEN_STEPS, SCRATCH, STATE, Golden, golden_names, maxrel, same, same_bits
+from helpers import GOLDEN_STEPS, SCRATCH, STATE, Golden, golden_names, maxrel, same, same_bits, tile_geometry, land_mask
 
 pytestmark = pytest.mark.gpu
 NAMES = golden_names()
@@ -55,6 +55,16 @@ def _engine(f, variant=0, mode="dense_fused", **kw):
     return e
 
 
+# the modes that launch a tiled sweep (k_mont_visc, k_uv_fused): run in both tile geometries (64 x 4 keeps the test ids of
+# the frames' own choice, 64 x 8 adds "-t8"); gather and dense_unfused do not depend on the geometry
+TILED_MODES = ("dense_fused", "dense_fused_keepdiag", "dense_fuse_mv_only", "dense_fuse_uv_only")
+
+
+def _geometries(items):
+    """(item, tile_rows) pairs: every item in the 64 x 4 geometry under its old id, and in the 64 x 8 geometry as "<id>-t8"."""
+    return ([pytest.param(x, 4, id=x) for x in items] + [pytest.param(x, 8, id=x + "-t8") for x in items])
+
+
 def _fuses(p):
     """Montgomery(+Leith) runs as the fused sweep for this configuration (beom_engine.hip can_fuse): the
     viscosity is refreshed every step, or never after step 3."""
@@ -67,14 +77,21 @@ def _fusion_active(g, e):
     return e.is_dense and _fuses(g.p)
 
 
-@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("mode,tile_rows", [pytest.param(m, None, id=m) for m in MODES if m not in TILED_MODES]
+                         + _geometries(TILED_MODES))
 @pytest.mark.parametrize("name", NAMES)
-def test_step_matches_reference_golden(name, mode):
+def test_step_matches_reference_golden(name, mode, tile_rows):
     """beom_step over steps 1..10 == FP64 module state of the reference run.  In the default
     fused mode v_cc, v_ll, rvor, dive are not kept (only their products are formed), so the
-    check covers everything that determines the future: prognostic fields and histories."""
+    check covers everything that determines the future: prognostic fields and histories.
+    The modes with tiled sweeps run in both tile geometries (the fixtures' frames only reach edge tiles of 64 x 8)."""
     g = Golden(name)
-    e = _engine(_fields(g), variant=g.variant, mode=mode)
+    if tile_rows is None:
+        e = _engine(_fields(g), variant=g.variant, mode=mode)
+    else:
+        with tile_geometry(tile_rows):
+            e = _engine(_fields(g), variant=g.variant, mode=mode)
+        assert e.info("tile_rows") == (tile_rows if e.is_dense else 0)
     exact = not g.uses_cos()
     lossy = mode in ("dense_fused", "dense_fuse_mv_only") and _fusion_active(g, e)
     t = 0
@@ -168,8 +185,8 @@ def test_long_run_matches_oracle():
     e.close()
 
 
-@pytest.mark.parametrize("case", ["island_leith", "island_wind_drag", "bay_ocrp_nudged", "sponge_obc_island"])
-def test_land_frames_on_the_rectangle_match_oracle_and_table_path(case):
+@pytest.mark.parametrize("case,tile_rows", _geometries(["island_leith", "island_wind_drag", "bay_ocrp_nudged", "sponge_obc_island"]))
+def test_land_frames_on_the_rectangle_match_oracle_and_table_path(case, tile_rows):
     """Frames WITH land wide enough to have regular tiles away from the coast: the embedded form (packed cells in the
     slots of their (i, j), land slots holding the sentinel's values, masks from the caller's arrays in the tiles that
     touch land, the fused mask-free paths elsewhere) against the oracle and against the table path, bit for bit."""
@@ -189,16 +206,16 @@ def test_land_frames_on_the_rectangle_match_oracle_and_table_path(case):
         p, files = I.case_sill_exchange3d(lm=400, mm=130, nlay=3, dt_s=0.01, npts=5, sill_halfwidth=20.0)
     files = {k: np.array(v, dtype=np.float64) for k, v in files.items()}
     h = files["h_bo"]
-    x = np.arange(p.lm + 2)[:, None]; y = np.arange(p.mm + 2)[None, :]
-    land = ((x - 0.3 * p.lm) ** 2 + (y - 0.55 * p.mm) ** 2) < (0.12 * p.lm) ** 2          # an island
-    land |= (x > 0.8 * p.lm) & (y < 0.3 * p.mm) & ((x + y) % 7 != 0) if case == "bay_ocrp_nudged" else False   # a ragged corner
+    land = land_mask(p, case == "bay_ocrp_nudged")
     h[land] = 0.0
     if "init" in files:
         files["init"][land] = 0.0
     p = p.replace(ndeg=I.get_nbr_deg_freedom(h))
     f = read_input_data(p, files=files)
-    emb, tab, o = capi.Engine(f), capi.Engine(f, dense_hint=0), oracle_lib.Oracle(f)
+    with tile_geometry(tile_rows):
+        emb, tab, o = capi.Engine(f), capi.Engine(f, dense_hint=0), oracle_lib.Oracle(f)
     assert emb.is_embedded and not tab.is_dense
+    assert emb.info("tile_rows") == tile_rows
     for x_ in (emb, tab, o):
         x_.step(1, 13)
     a, b = emb.download(), tab.download()
@@ -299,8 +316,8 @@ def test_restart_split_equals_single_run():
         x.close()
 
 
-@pytest.mark.parametrize("case", ["closed", "sill_ocrp", "beach_zero_visc", "soliton_zero_visc"])
-def test_lean_thickness_curvature_matches_oracle(case):
+@pytest.mark.parametrize("case,tile_rows", _geometries(["closed", "sill_ocrp", "beach_zero_visc", "soliton_zero_visc"]))
+def test_lean_thickness_curvature_matches_oracle(case, tile_rows):
     """Production pair of fused sweeps on a frame with DEEP tiles (>= 3 tiles away from every
     edge): k_mont_visc stores d2hx/d2hy only around non-interior tiles, k_uv_fused re-derives
     them from the staged hlay.  Prognostic state must equal the oracle and the run with
@@ -316,10 +333,12 @@ def test_lean_thickness_curvature_matches_oracle(case):
     else:
         p, files = I.case_sill_exchange3d(lm=330, mm=75, nlay=3, dt_s=0.01, npts=5, sill_halfwidth=20.0)
     f = read_input_data(p, files=files)
-    lean, full = capi.Engine(f), capi.Engine(f)
+    with tile_geometry(tile_rows):
+        lean, full = capi.Engine(f), capi.Engine(f)
     full.set_option("lean_d2h", 0)
     full.set_option("lean_visc", 0)
     assert lean.is_dense
+    assert lean.info("tile_rows") == tile_rows and full.info("tile_rows") == tile_rows
     o = oracle_lib.Oracle(f)
     n = 14
     for x in (lean, full, o):
@@ -332,7 +351,7 @@ def test_lean_thickness_curvature_matches_oracle(case):
         assert same_bits(sl[k], o.state()[k]), (case, k, "sign of zero")
     cl, cf = lean.download_scratch(), full.download_scratch()
     L = p.lm + 1
-    ip = 200 + (40 - 1) * L                      # cell (200, 40): tile x0 = 193, y0 = 33 is deep
+    ip = 200 + (40 - 1) * L                      # cell (200, 40): tile x0 = 193, y0 = 33 is deep in both geometries
     if case == "closed":                         # (the sill frame is flat there: both are zero)
         assert not np.array_equal(cl["d2hx"][:, ip - 3:ip + 3], cf["d2hx"][:, ip - 3:ip + 3])
     assert same(cl["mont"], cf["mont"]) and same(cl["pvor"], cf["pvor"])
@@ -393,16 +412,19 @@ def _big_cases():
     }
 
 
-@pytest.mark.parametrize("case", ["closed_3l", "closed_3l_biharm", "soliton_xper", "jet_xyper_2l",
-                                  "sill_ocrp_nudg_4l", "stommel_wind_drag", "beach_ocrp_8l", "closed_8l"])
-def test_dense_interior_waves_match_oracle_and_gather(case):
+@pytest.mark.parametrize("case,tile_rows", _geometries(["closed_3l", "closed_3l_biharm", "soliton_xper", "jet_xyper_2l",
+                                                        "sill_ocrp_nudg_4l", "stommel_wind_drag", "beach_ocrp_8l", "closed_8l"]))
+def test_dense_interior_waves_match_oracle_and_gather(case, tile_rows):
     """Grids wide enough (L >= 130) that most waves take the INTERIOR specialisation of
     CellDenseT; the dense path, the gather path and the oracle must agree bitwise."""
     from beom_amd.grid import read_input_data
     p, files = _big_cases()[case]()
     f = read_input_data(p, files=files)
-    engines = {m: _engine(f, mode=m) for m in MODES}
+    with tile_geometry(tile_rows):
+        engines = {m: _engine(f, mode=m) for m in MODES}
     assert engines["dense_fused"].is_dense and not engines["gather"].is_dense
+    for e in engines.values():
+        assert e.info("tile_rows") == (tile_rows if e.is_dense else 0)
     o = oracle_lib.Oracle(f)
     for x in list(engines.values()) + [o]:
         x.step(1, 12)
@@ -454,20 +476,16 @@ def test_stress_folded_into_momentum_sweep(case, tile_rows):
     """distribute_stress (private_mod.f95:1921-2149) formed inside the fused u+v sweep (k_uv_fused_sf, both tile geometries):
     against the oracle, against the same engine with the fold off (its own launch + the three arrays) and on three bands, bit
     for bit with the sign of zero."""
-    import os
     from beom_amd.grid import read_input_data
     p, files = _forced_cases()[case]()
     f = read_input_data(p, files=files)
     obc = bool(f.flag_nudging) and float(p.mcbc) < 0.5
-    old = os.environ.get("BEOM_TILE4")
-    os.environ["BEOM_TILE4"] = "1" if tile_rows == 4 else "0"          # (read when a handle is created)
-    try:
+    with tile_geometry(tile_rows):
         fold, plain, o = capi.Engine(f), capi.Engine(f), oracle_lib.Oracle(f)
         bands = None if obc else capi.MultiEngine(f, devices=[0, 0, 0])
-    finally:
-        if old is None: os.environ.pop("BEOM_TILE4")
-        else: os.environ["BEOM_TILE4"] = old
-    assert fold.info("tile_rows") == tile_rows
+    assert fold.info("tile_rows") == tile_rows and plain.info("tile_rows") == tile_rows
+    if bands:
+        assert bands.info("tile_rows") == tile_rows
     plain.set_option("fold_stress", 0)
     n = 15
     for x in [fold, plain, o] + ([bands] if bands else []):
@@ -593,10 +611,7 @@ def test_cut_step_matches_single_domain(case, world, tile_rows):
     else:
         p, files = I.case_sill_exchange3d(lm=133, mm=141, nlay=2, dt_s=0.01, npts=5, sill_halfwidth=6.0)
     f = read_input_data(p, files=files)
-    import os
-    old = os.environ.get("BEOM_TILE4")
-    os.environ["BEOM_TILE4"] = "1" if tile_rows == 4 else "0"          # (read when a handle is created; bands of the headline
-    try:                                                               #  frame cut 2 or 4 ways run the 64 x 8 geometry)
+    with tile_geometry(tile_rows):                                     # (bands of the headline frame cut 2 or 4 ways run 64 x 8)
         whole = capi.Engine(f)
         runs = []
         for g in slab.decompose(p.mm, p.lm, world):
@@ -604,9 +619,7 @@ def test_cut_step_matches_single_domain(case, world, tile_rows):
             assert e.info("tile_rows") == tile_rows
             runs.append(slab.SlabRunner(e, g, p.nlay, dist=None))
             e.set_stream(torch.cuda.current_stream().cuda_stream)     # one stream: ordering by program order
-    finally:
-        if old is None: os.environ.pop("BEOM_TILE4")
-        else: os.environ["BEOM_TILE4"] = old
+    assert whole.info("tile_rows") == tile_rows
 
     def move():
         for k in range(world - 1):

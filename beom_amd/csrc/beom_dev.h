@@ -261,11 +261,8 @@ struct CellGather {
 // INTERIOR = true is the specialisation for waves whose 64 cells all have
 // 2 <= i <= L-2 and 2 <= j <= M-2: every neighbour is a plain offset and every mask is 1
 // (x*1.0 folds exactly), chosen per wave by a scalar test in the kernels.
-#ifndef BEOM_TILE_X
 #define BEOM_TILE_X 64
-#endif
 #define BEOM_TILE_Y (BEOM_BLOCK / BEOM_TILE_X)
-#define BEOM_TILE_WX (BEOM_TILE_X / 64)
 
 template <bool INTERIOR>
 struct CellDenseT {
@@ -285,8 +282,8 @@ struct CellDenseT {
         int ty, ch;
         if (!tm.locate(blockIdx.x, ty, ch)) return false;
         const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-        j = ty * BEOM_TILE_Y + wave / BEOM_TILE_WX + 1;
-        i = ch * BEOM_TILE_X + (wave % BEOM_TILE_WX) * 64 + ((int)threadIdx.x & 63) + 1;
+        j = ty * BEOM_TILE_Y + wave + 1;
+        i = ch * BEOM_TILE_X + ((int)threadIdx.x & 63) + 1;
         ipnt = i + (j - 1) * P;
         jg = j + d.joff; Mg = d.Mg; ywrap = d.yper && !d.slab;
         dv = &d;

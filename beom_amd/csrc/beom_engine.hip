@@ -14,18 +14,7 @@
 #include <vector>
 
 #include "beom_dev.h"
-// the kernels, once per tile geometry (beom_launch_tiled.h): t8 also serves every kernel that is not tiled
-namespace t8 {
 #include "beom_kernels.h"
-}
-#undef MV_Q
-#undef UV_Q
-#define MV_Q 1
-#define UV_Q 1
-namespace t4 {
-#include "beom_kernels.h"
-}
-using namespace t8;
 #include "beom_dense_host.h"
 
 namespace {
@@ -836,16 +825,32 @@ static void launch_uv(beom_engine *E, int ilay, double gene, double ramp, double
     else LAUNCH_CTX((k_update_uv<CellGather, XDIR>), (k_update_uv<CellDense, XDIR>), nz, E->d, ilay, gene, ramp, ctim, copy_hist);
     if (!copy_hist) { if (XDIR) rot3(E->d.dmx); else rot3(E->d.dmy); }
 }
-#define TNS t8
-#define TSUF t8
-#include "beom_launch_tiled.h"
-#undef TNS
-#undef TSUF
-#define TNS t4
-#define TSUF t4
-#include "beom_launch_tiled.h"
-#undef TNS
-#undef TSUF
+// the tiled sweeps in the tile geometry Q (beom_kernels.h: TileGeom)
+template <int Q>
+static bool raw_mont_visc(beom_engine *E, bool leith) {
+    const dim3 g = mont_visc_grid<Q>(E->d), b(BEOM_BLOCK);
+    switch (E->d.nlay) {
+#define CASE_NL(n) case n: if (leith) hipLaunchKernelGGL((k_mont_visc<Q, n, true>), g, b, 0, E->stream, E->d); \
+                           else hipLaunchKernelGGL((k_mont_visc<Q, n, false>), g, b, 0, E->stream, E->d); return true;
+        CASE_NL(1) CASE_NL(2) CASE_NL(3) CASE_NL(4) CASE_NL(5) CASE_NL(6) CASE_NL(7) CASE_NL(8)
+#undef CASE_NL
+        default: return false;
+    }
+}
+template <int Q>
+static void raw_uv_fused(beom_engine *E, bool first_x, bool prod, bool zv, double gene, double ramp, double ctim) {
+    const dim3 g = uv_fused_grid<Q>(E->d), b(TileGeom<Q>::BLOCK);
+    DevView &d = E->d;
+#define UV_GO(kern, fx, pr, z) hipLaunchKernelGGL((kern<Q, fx, pr, z>), g, b, 0, E->stream, d, gene, ramp, ctim)
+#define UV_PICK(fx) do { \
+        if (d.stress_fold) { if (zv) UV_GO(k_uv_fused_sf, fx, true, true); else if (prod) UV_GO(k_uv_fused_sf, fx, true, false); else UV_GO(k_uv_fused_sf, fx, false, false); } \
+        else { if (zv) UV_GO(k_uv_fused, fx, true, true); else if (prod) UV_GO(k_uv_fused, fx, true, false); else UV_GO(k_uv_fused, fx, false, false); } \
+    } while (0)
+    // (stress_fold: distribute_stress formed inside the sweep — its own instantiations, so that the unforced ones stay lean)
+    if (first_x) UV_PICK(true); else UV_PICK(false);
+#undef UV_PICK
+#undef UV_GO
+}
 // fused Montgomery + Leith sweep (dense frames); false if no instantiation for this nlay
 // leith: this step refreshes the Leith viscosity (:2188, :2268); else the sweep forms the products of the
 // standing v_cc, v_ll.  keep_visc: a refreshed viscosity has to stand for later steps (n_3d > 1).
@@ -854,7 +859,7 @@ static bool launch_mont_visc(beom_engine *E, bool uv_fused_follows, bool leith, 
     E->d.keep_visc = keep_visc;
     E->d.zero_visc = !leith && uv_fused_follows && E->lean_visc && E->visc_all_zero && E->P.dvis == 0.0 && E->P.bvis == 0.0 &&
                      !E->d.keep_diag;
-    return E->tile4 ? raw_mont_visc_t4(E, leith) : raw_mont_visc_t8(E, leith);
+    return E->tile4 ? raw_mont_visc<1>(E, leith) : raw_mont_visc<2>(E, leith);
 }
 // fused U+V sweep (dense frames): first_x = update_u first (even tstp)
 static void uv_fused_swap(beom_engine *E, bool first_x) {
@@ -866,8 +871,8 @@ static void uv_fused_swap(beom_engine *E, bool first_x) {
 static void launch_uv_fused(beom_engine *E, bool first_x, bool prod, double gene, double ramp, double ctim,
                             bool swap = true) {
     const bool zv = prod && E->d.zero_visc;       // set by launch_mont_visc of this step
-    if (E->tile4) raw_uv_fused_t4(E, first_x, prod, zv, gene, ramp, ctim);
-    else raw_uv_fused_t8(E, first_x, prod, zv, gene, ramp, ctim);
+    if (E->tile4) raw_uv_fused<1>(E, first_x, prod, zv, gene, ramp, ctim);
+    else raw_uv_fused<2>(E, first_x, prod, zv, gene, ramp, ctim);
     if (swap) uv_fused_swap(E, first_x);
 }
 static bool can_fuse(const beom_engine *E, int n_3d, bool first3) {

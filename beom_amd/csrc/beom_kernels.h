@@ -7,8 +7,9 @@
 // Arithmetic follows the reference statement by statement and in its operation order
 // (compiled with -ffp-contract=off) so results are bit-identical to the Fortran.
 // HBM-bound FP64 stencils: no MFMA (nothing here is a contraction).
-// (no include guard: beom_engine.hip includes this file once per tile geometry, each time inside a namespace,
-//  after beom_dev.h; MV_Q and UV_WAVES select the geometry)
+// The tiled sweeps (k_mont_visc, k_uv_fused, k_uv_fused_sf) take their tile geometry as the template parameter Q,
+// the rows (cells) per thread (TileGeom); beom_engine.hip picks Q per frame.  Include after beom_dev.h.
+#pragma once
 
 #define LL(a, ip, il) (a)[(long long)(ip) + d.n1 * (long long)((il) - 1)]
 #define FNUD_(ip, il, iv) d.fnud[(long long)(ip) + d.n1 * ((long long)((il) - 1) + (long long)d.nlay * ((iv) - 1))]
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(BEOM_BLOCK) void k_update_mont_all(DevView d) {
 }
 
 // ---- fused sweep: update_mont_rvor_pvor_dive_kine (:2318-2439) + update_viscosity
-//      (:2441-2502) for dense frames.  rvor and dive of a 64 x MV_TY tile plus a one-cell ring
+//      (:2441-2502) for dense frames.  rvor and dive of a 64 x TY tile plus a one-cell ring
 //      are staged in LDS (double-buffered over layers, one barrier per layer); the Leith
 //      stencil reads them from LDS, and the sweep hands update_u/update_v the products
 //          pcd = v_cc*dive   and   qlr = v_ll*rvor
@@ -268,27 +269,22 @@ __global__ __launch_bounds__(BEOM_BLOCK) void k_update_mont_all(DevView d) {
 //      Leith launch, its 4 words, and 2 words in each momentum sweep.  With keep_diag the
 //      four arrays are stored as well (parity tests; needed when viscosity is not refreshed
 //      every step — then the unfused path runs instead).
-#define MV_TX 64
-#ifndef MV_Q
-#define MV_Q 2                         // rows (cells) per thread
-#endif
-#define MV_TY (4 * MV_Q)
-#ifndef MV_UNROLL
-#define MV_UNROLL 4                    // measured: not unrolling the layer loop is 20 % slower
-#endif
-// tile of the fused u+v sweep (k_uv_fused, further down): k_mont_visc needs its geometry for lean_d2h
-#define UV_TX 64
-#ifndef UV_Q
-#define UV_Q 2                         // rows (cells) per thread
-#endif
-#ifndef UV_WAVES
-#define UV_WAVES 4                     // waves (rows of 64 cells) per workgroup
-#endif
-#define UV_BLOCK (64 * UV_WAVES)
-#define UV_TY (UV_WAVES * UV_Q)
-static constexpr int kUvBlock = UV_BLOCK;      // (for the launch code: the macros hold the LAST geometry included)
-#define MV_LDX (MV_TX + 2 + 1)          // +1 pad column
-#define MV_LDY (MV_TY + 2)
+// Tile geometry of k_mont_visc and of the fused u+v sweep (k_uv_fused, further down), which share one tiling (lean_d2h):
+// Q rows (cells) per thread.  Q = 2: 64 x 8 tiles (frames of many rounds of workgroups); Q = 1: 64 x 4 tiles (frames of
+// one or two rounds, where a workgroup's lifetime is the step time).
+template <int Q>
+struct TileGeom {
+    static constexpr int TX = 64;
+    static constexpr int WAVES = 4;                  // waves (rows of 64 cells) per workgroup
+    static constexpr int BLOCK = 64 * WAVES;
+    static constexpr int TY = WAVES * Q;
+    static constexpr int MV_LDX = TX + 2 + 1;        // k_mont_visc stage: tile + ring, +1 pad column
+    static constexpr int MV_LDY = TY + 2;
+    static constexpr int LDX = TX + 1 + 1;           // k_uv_fused: new transport of the first update
+    static constexpr int SROWS = TY + 2, SLDX = TX + 2;      // UVstage
+    static constexpr int HROWS = TY + 4, HLDX = TX + 4;      // UVhstage
+    static_assert(BLOCK == BEOM_BLOCK, "lean_d2h: k_mont_visc (BEOM_BLOCK threads, Q rows each) runs the tiles of k_uv_fused");
+};
 
 // u, v around a cell: loads and arithmetic kept apart so that a thread can issue the loads of all
 // its cells (and of its ring cell) before the first use — one memory round trip per layer
@@ -320,25 +316,27 @@ __device__ __forceinline__ bool halo_target(const DevView &d, int &a, int &b) {
 // LEITH = false: configurations whose viscosity is never refreshed after the first three steps
 // (dvis <= 1e-3, svis = 0): v_cc, v_ll keep whatever update_viscosity left there (:2188) and only
 // the products with this step's dive, rvor are formed — no ring of rvor/dive is needed.
-template <int NL, bool INT, bool LEITH>
+template <int Q, int NL, bool INT, bool LEITH>
 __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0, bool wr_d2h, bool wr_prod,
-                                               double (*s_rv)[MV_LDY][MV_LDX], double (*s_dv)[MV_LDY][MV_LDX],
-                                               double (*s_hh)[MV_LDY][MV_LDX]) {
+                                               double (*s_rv)[TileGeom<Q>::MV_LDY][TileGeom<Q>::MV_LDX],
+                                               double (*s_dv)[TileGeom<Q>::MV_LDY][TileGeom<Q>::MV_LDX],
+                                               double (*s_hh)[TileGeom<Q>::MV_LDY][TileGeom<Q>::MV_LDX]) {
+    using G = TileGeom<Q>;
     const int tid = threadIdx.x;
     const int lx = tid & 63, wy = tid >> 6;              // column in tile, wave = row pair
     const int i = x0 + lx;
     const double i_gr = d.i_gr, i_ns = d.i_ns, hs_8 = d.hsal;
     // own cells: rows y0+wy (+4 per extra cell)
-    CellDenseT<INT> c[MV_Q];
-    bool ok[MV_Q], wr[MV_Q];
-    double hcol[MV_Q], fcor[MV_Q], h_th[MV_Q], h_to[MV_Q], hown[NL][MV_Q];
-    int n1[MV_Q], n3[MV_Q], n5[MV_Q], n6[MV_Q], n7[MV_Q];
+    CellDenseT<INT> c[Q];
+    bool ok[Q], wr[Q];
+    double hcol[Q], fcor[Q], h_th[Q], h_to[Q], hown[NL][Q];
+    int n1[Q], n3[Q], n5[Q], n6[Q], n7[Q];
     // The staged entry at a geometric position is what a NEIGHBOUR lookup of that target returns.
     // Under periodic wraps the orphan column i = L / row j = M are wrap targets
     // (private_mod.f95:619-620,647-648): they must hold the wrapped cell's values (widx).
-    int widx[MV_Q];                                      // -1: the cell's own values are staged
+    int widx[Q];                                      // -1: the cell's own values are staged
 #pragma unroll
-    for (int q = 0; q < MV_Q; ++q) {
+    for (int q = 0; q < Q; ++q) {
         const int j = y0 + wy + 4 * q;
         ok[q] = (i <= d.L) && (j <= d.M);
         if (!INT && ok[q] && !slot_is_cell(d, i + (j - 1) * d.P)) ok[q] = false;     // embedded: a land slot is the sentinel
@@ -360,12 +358,12 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
             }
         }
     }
-    // halo cell of this thread: ring of the (MV_TX+2) x (MV_TY+2) region
+    // halo cell of this thread: ring of the (TX+2) x (TY+2) region
     int hr = -1, hc = -1;
-    if (tid < MV_TX + 2) { hr = 0; hc = tid; }
-    else if (tid < 2 * (MV_TX + 2)) { hr = MV_TY + 1; hc = tid - (MV_TX + 2); }
-    else if (tid < 2 * (MV_TX + 2) + MV_TY) { hr = 1 + tid - 2 * (MV_TX + 2); hc = 0; }
-    else if (tid < 2 * (MV_TX + 2) + 2 * MV_TY) { hr = 1 + tid - 2 * (MV_TX + 2) - MV_TY; hc = MV_TX + 1; }
+    if (tid < G::TX + 2) { hr = 0; hc = tid; }
+    else if (tid < 2 * (G::TX + 2)) { hr = G::TY + 1; hc = tid - (G::TX + 2); }
+    else if (tid < 2 * (G::TX + 2) + G::TY) { hr = 1 + tid - 2 * (G::TX + 2); hc = 0; }
+    else if (tid < 2 * (G::TX + 2) + 2 * G::TY) { hr = 1 + tid - 2 * (G::TX + 2) - G::TY; hc = G::TX + 1; }
     CellDenseT<INT> hcell;
     int hidx = 0;                                        // packed index of the ring target, 0 = sentinel
     hcell.set_cell(d, 1, 1);
@@ -375,12 +373,12 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
     }
 
 #pragma unroll
-    for (int l = 0; l < NL; ++l) {      // must stay unrolled: d.rhon[l] may not become a dynamic index
+    for (int l = 0; l < NL; ++l) {      // must stay unrolled: d.rhon[l] may not become a dynamic index (measured: not unrolling is 20 % slower)
         const int ilay = l + 1, buf = l & 1;
         // every load of this layer first ...
-        double w[MV_Q][6], wh[6], hring = 0.0, vcc0[MV_Q], vll0[MV_Q];
+        double w[Q][6], wh[6], hring = 0.0, vcc0[Q], vll0[Q];
 #pragma unroll
-        for (int q = 0; q < MV_Q; ++q) {
+        for (int q = 0; q < Q; ++q) {
             if (INT || ok[q]) uv6_load<INT>(d, c[q], ilay, w[q]);
             else { w[q][0] = w[q][1] = w[q][2] = w[q][3] = w[q][4] = w[q][5] = 0.0; }
             if (!LEITH) {     // zero_visc: v_cc = v_ll = +0 everywhere (dvis = bvis = 0), verified by the engine
@@ -393,9 +391,9 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
             if (LEITH && hidx != 0) uv6_load<INT>(d, hcell, ilay, wh);
         }
         // ... then the arithmetic and the stage
-        double rv[MV_Q], dv[MV_Q];
+        double rv[Q], dv[Q];
 #pragma unroll
-        for (int q = 0; q < MV_Q; ++q) {
+        for (int q = 0; q < Q; ++q) {
             rv[q] = 0.0; dv[q] = 0.0;
             if (INT || ok[q]) rv_dv_calc<INT>(d, c[q], w[q], rv[q], dv[q]);
             double srv = rv[q], sdv = dv[q], shh = hown[l][q];
@@ -428,7 +426,7 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
         }
         __syncthreads();
 #pragma unroll
-        for (int q = 0; q < MV_Q; ++q) {
+        for (int q = 0; q < Q; ++q) {
             if (!wr[q]) continue;
             const CellDenseT<INT> &cc = c[q];
             const int ipnt = cc.ipnt;
@@ -505,40 +503,34 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
 // would take 172 and run two).  Measured on one box, alternating builds (tools/ab_variants.sh): mont+visc 1000 -> 905 us at
 // 4096^2 x 4, 180 -> 157 us on the sill frame (Leith + outcropping), 822 -> 706 us at 8192 x 1024 x 8 despite 84-328 B of
 // scratch per lane there; a cap for four waves (128 VGPRs) spills more than it hides.
-#ifndef MV_WAVES_PER_EU
-#define MV_WAVES_PER_EU 3
-#endif
-#if MV_WAVES_PER_EU > 0
-#define MV_OCC_ATTR __attribute__((amdgpu_waves_per_eu(MV_WAVES_PER_EU)))
-#else
-#define MV_OCC_ATTR
-#endif
-template <int NL, bool LEITH = true>
-__global__ __launch_bounds__(BEOM_BLOCK) MV_OCC_ATTR void k_mont_visc(DevView d) {
-    __shared__ double s_rv[LEITH ? 2 : 1][LEITH ? MV_LDY : 1][LEITH ? MV_LDX : 1];
-    __shared__ double s_dv[LEITH ? 2 : 1][LEITH ? MV_LDY : 1][LEITH ? MV_LDX : 1];
-    __shared__ double s_hh[2][MV_LDY][MV_LDX];               // hlay of tile + ring
-    const TileMap tm(d, MV_TX, MV_TY);
+template <int Q, int NL, bool LEITH = true>
+__global__ __launch_bounds__(BEOM_BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void k_mont_visc(DevView d) {
+    using G = TileGeom<Q>;
+    __shared__ double s_rv[LEITH ? 2 : 1][LEITH ? G::MV_LDY : 1][LEITH ? G::MV_LDX : 1];
+    __shared__ double s_dv[LEITH ? 2 : 1][LEITH ? G::MV_LDY : 1][LEITH ? G::MV_LDX : 1];
+    __shared__ double s_hh[2][G::MV_LDY][G::MV_LDX];               // hlay of tile + ring
+    const TileMap tm(d, G::TX, G::TY);
     int ty, ch;
     if (!tm.locate(blockIdx.x, ty, ch)) return;               // whole block: no barrier is skipped by part of it
-    const int x0 = ch * MV_TX + 1, y0 = ty * MV_TY + 1;
+    const int x0 = ch * G::TX + 1, y0 = ty * G::TY + 1;
     // block-uniform: tile and its ring lie in 2..L-2 x 2..M-2 (global rows too) -> no wraps, masks = 1
-    const bool interior = x0 - 1 >= 2 && x0 + MV_TX <= d.L - 2 && y0 - 1 >= 2 && y0 + MV_TY <= d.M - 2
-                          && y0 - 1 + d.joff >= 2 && y0 + MV_TY + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, MV_TY);
+    const bool interior = x0 - 1 >= 2 && x0 + G::TX <= d.L - 2 && y0 - 1 >= 2 && y0 + G::TY <= d.M - 2
+                          && y0 - 1 + d.joff >= 2 && y0 + G::TY + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, G::TY);
     // d.lean_d2h (the fused u+v sweep follows): its interior workgroups re-derive d2hx, d2hy from
     // hlay; only tiles that touch a non-interior tile of that sweep (same tiling) still store them
-    const int uy0 = ((y0 - 1) / UV_TY) * UV_TY + 1;          // first row of the k_uv_fused tile this tile lies in
-    bool deep = x0 - 1 - UV_TX >= 2 && x0 + 2 * UV_TX <= d.L - 2 && uy0 - 1 - UV_TY >= 2 && uy0 + 2 * UV_TY <= d.M - 2
-                && uy0 - 1 - UV_TY + d.joff >= 2 && uy0 + 2 * UV_TY + d.joff <= d.Mg - 2;
+    const int uy0 = ((y0 - 1) / G::TY) * G::TY + 1;          // first row of the k_uv_fused tile this tile lies in
+    bool deep = x0 - 1 - G::TX >= 2 && x0 + 2 * G::TX <= d.L - 2 && uy0 - 1 - G::TY >= 2 && uy0 + 2 * G::TY <= d.M - 2
+                && uy0 - 1 - G::TY + d.joff >= 2 && uy0 + 2 * G::TY + d.joff <= d.Mg - 2;
     if (deep && d.embedded)           // all nine k_uv_fused tiles around this one take the staged interior path
         for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) deep = deep && tile_regular(d, x0 + dx * UV_TX, uy0 + dy * UV_TY, UV_TY);
+            for (int dx = -1; dx <= 1; ++dx) deep = deep && tile_regular(d, x0 + dx * G::TX, uy0 + dy * G::TY, G::TY);
     const bool wr_d2h = !(d.lean_d2h && deep);
     const bool wr_prod = !(d.zero_visc && deep);   // zero viscosity: interior workgroups of k_uv_fused skip the term
-    if (interior) body_mont_visc<NL, true, LEITH>(d, x0, y0, wr_d2h, wr_prod, (double (*)[MV_LDY][MV_LDX])s_rv, (double (*)[MV_LDY][MV_LDX])s_dv, s_hh);
-    else body_mont_visc<NL, false, LEITH>(d, x0, y0, wr_d2h, wr_prod, (double (*)[MV_LDY][MV_LDX])s_rv, (double (*)[MV_LDY][MV_LDX])s_dv, s_hh);
+    if (interior) body_mont_visc<Q, NL, true, LEITH>(d, x0, y0, wr_d2h, wr_prod, (double (*)[G::MV_LDY][G::MV_LDX])s_rv, (double (*)[G::MV_LDY][G::MV_LDX])s_dv, s_hh);
+    else body_mont_visc<Q, NL, false, LEITH>(d, x0, y0, wr_d2h, wr_prod, (double (*)[G::MV_LDY][G::MV_LDX])s_rv, (double (*)[G::MV_LDY][G::MV_LDX])s_dv, s_hh);
 }
-static inline dim3 mont_visc_grid(const DevView &d) { return dim3(TileMap(d, MV_TX, MV_TY).blocks(), 1, 1); }
+template <int Q>
+static inline dim3 mont_visc_grid(const DevView &d) { return dim3(TileMap(d, TileGeom<Q>::TX, TileGeom<Q>::TY).blocks(), 1, 1); }
 
 // ---- update_viscosity (Leith part), private_mod.f95:2441-2502 -----------------------
 template <class C>
@@ -589,16 +581,13 @@ struct UVio {
 // Where a momentum update finds the five fields BOTH updates read (hlay, mont, pvor and the
 // viscous products pcd, qlr) at the cell, at its "b" neighbour (u: W, v: S) and at its "a"
 // neighbour (u: N, v: E): global memory, or the LDS image staged by the fused u+v sweep.
-#define UV_LDX (UV_TX + 1 + 1)
-#define UV_SROWS (UV_TY + 2)
-#define UV_SLDX (UV_TX + 2)
-typedef double UVstage[UV_SROWS][UV_SLDX];           // rows y0-1 .. y0+TY, cols x0-1 .. x0+TX
+template <int Q>
+using UVstage = double[TileGeom<Q>::SROWS][TileGeom<Q>::SLDX];    // rows y0-1 .. y0+TY, cols x0-1 .. x0+TX
 // hlay is staged one cell wider: the thickness curvatures d2hx, d2hy (:2393-2404) at a cell and
 // at its W / S neighbour are re-evaluated from it, so interior workgroups never read (and the
 // Montgomery sweep never writes) those two arrays
-#define UV_HROWS (UV_TY + 4)
-#define UV_HLDX (UV_TX + 4)
-typedef double UVhstage[UV_HROWS][UV_HLDX];          // rows y0-2 .. y0+TY+1, cols x0-2 .. x0+TX+1
+template <int Q>
+using UVhstage = double[TileGeom<Q>::HROWS][TileGeom<Q>::HLDX];   // rows y0-2 .. y0+TY+1, cols x0-2 .. x0+TX+1
 
 struct ShGlobal {
     const DevView &d; int ipnt, cb, ca, ilay;
@@ -615,9 +604,9 @@ struct ShGlobal {
     template <bool XDIR> __device__ __forceinline__ double d2h_s() const { return LL(XDIR ? d.d2hx : d.d2hy, ipnt, ilay); }
     template <bool XDIR> __device__ __forceinline__ double d2h_b() const { return LL(XDIR ? d.d2hx : d.d2hy, cb, ilay); }
 };
-template <bool XDIR>
+template <int Q, bool XDIR>
 struct ShLds {                                       // field order in the stage: 0 mont 1 pvor 2 pcd 3 qlr
-    const UVstage *s; const double (*h)[UV_HLDX];    // h = the wider hlay stage
+    const UVstage<Q> *s; const double (*h)[TileGeom<Q>::HLDX];    // h = the wider hlay stage
     int r, c;                                        // staged position of the cell (UVstage coordinates)
     double ocrp, hs2;                                // d.ocrp, 2*hsal (outcropping guard of d2h)
     static constexpr int RB = XDIR ? 0 : -1, CB = XDIR ? -1 : 0;   // b neighbour: W | S
@@ -870,7 +859,6 @@ __device__ __forceinline__ double uv_first_halo(const DevView &d, int a, int b, 
     return uv_first_eval<FIRST_X, PROD, false, false, SF>(d, h, ilay, gene, ramp, ctim, sh);
 }
 
-static_assert(MV_TX == UV_TX && UV_TY % MV_TY == 0, "lean_d2h: every tile of k_mont_visc lies inside one tile of k_uv_fused");
 // Interior workgroups of the production pair (PROD, tile and ring strictly inside the wet interior):
 // the five shared fields of tile + ring are staged in LDS once and both updates, ring cells
 // included, read them there.  All loads of a phase are issued before the first use — the
@@ -892,15 +880,16 @@ __device__ __forceinline__ void uv_pre_load(const DevView &d, const CellDenseT<t
     if (gene != 0.0) { pre[5] = LL(dm[0], ipnt, ilay); pre[6] = LL(dm[1], ipnt, ilay); pre[7] = LL(dm[2], ipnt, ilay); }
 }
 
-template <bool FIRST_X, bool ZV, bool SF>
+template <int Q, bool FIRST_X, bool ZV, bool SF>
 __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, int y0, int ilay, double gene,
-                                                     double ramp, double ctim, double (*s_h)[UV_LDX], UVstage *s_f,
-                                                     double (*s_hl)[UV_HLDX]) {
+                                                     double ramp, double ctim, double (*s_h)[TileGeom<Q>::LDX], UVstage<Q> *s_f,
+                                                     double (*s_hl)[TileGeom<Q>::HLDX]) {
+    using G = TileGeom<Q>;
     const int tid = threadIdx.x;
     const int lx = tid & 63, wy = tid >> 6;
     const int i = x0 + lx;
     constexpr int ROFF = FIRST_X ? 1 : 0, COFF = FIRST_X ? 0 : 1;      // s_h coordinates as in body_uv_fused
-    constexpr int NST = UV_SROWS * (UV_TX + 2), NIT = (NST + UV_BLOCK - 1) / UV_BLOCK;
+    constexpr int NST = G::SROWS * (G::TX + 2), NIT = (NST + G::BLOCK - 1) / G::BLOCK;
     const long long lay = d.n1 * (long long)(ilay - 1);
     // ---- phase A loads: stage elements, outer hlay ring, first update of own cells and of the ring cell
     // ZV (zero viscosity): pcd, qlr are neither staged nor read
@@ -910,9 +899,9 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
     int frr[NIT], fcc[NIT];
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
-        const int idx = tid + k * UV_BLOCK;
+        const int idx = tid + k * G::BLOCK;
         const int idc = idx < NST ? idx : tid;           // clamped: the load is harmless, the store is skipped
-        frr[k] = idc / (UV_TX + 2); fcc[k] = idc - frr[k] * (UV_TX + 2);
+        frr[k] = idc / (G::TX + 2); fcc[k] = idc - frr[k] * (G::TX + 2);
         const long long ip = (long long)(x0 - 1 + fcc[k]) + (long long)(y0 - 2 + frr[k]) * d.P + lay;
 #pragma unroll
         for (int f = 0; f < 5; ++f) if (f >= NF && f < 4) fv[k][f] = 0.0; else fv[k][f] = src[f][ip];
@@ -920,25 +909,25 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
     // outer ring of the hlay stage without its corners: d2hy needs the rows y0-2 and y0+TY+1,
     // d2hx the columns x0-2 and x0+TX+1
     int hrr = -1, hcc = -1;
-    if (tid < UV_TX + 2) { hrr = 0; hcc = 1 + tid; }
-    else if (tid < 2 * (UV_TX + 2)) { hrr = UV_HROWS - 1; hcc = 1 + tid - (UV_TX + 2); }
-    else if (tid < 2 * (UV_TX + 2) + UV_SROWS) { hrr = 1 + tid - 2 * (UV_TX + 2); hcc = 0; }
-    else if (tid < 2 * (UV_TX + 2) + 2 * UV_SROWS) { hrr = 1 + tid - 2 * (UV_TX + 2) - UV_SROWS; hcc = UV_HLDX - 1; }
+    if (tid < G::TX + 2) { hrr = 0; hcc = 1 + tid; }
+    else if (tid < 2 * (G::TX + 2)) { hrr = G::HROWS - 1; hcc = 1 + tid - (G::TX + 2); }
+    else if (tid < 2 * (G::TX + 2) + G::SROWS) { hrr = 1 + tid - 2 * (G::TX + 2); hcc = 0; }
+    else if (tid < 2 * (G::TX + 2) + 2 * G::SROWS) { hrr = 1 + tid - 2 * (G::TX + 2) - G::SROWS; hcc = G::HLDX - 1; }
     const double hring = d.hlay[(long long)(x0 - 2 + (hrr >= 0 ? hcc : 2)) + (long long)(y0 - 3 + (hrr >= 0 ? hrr : 2)) * d.P + lay];
-    CellDenseT<true> c[UV_Q];
-    bool wr[UV_Q];
-    double pre[UV_Q][8];
+    CellDenseT<true> c[Q];
+    bool wr[Q];
+    double pre[Q][8];
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
-        const int j = y0 + wy + UV_WAVES * q;
+    for (int q = 0; q < Q; ++q) {
+        const int j = y0 + wy + G::WAVES * q;
         wr[q] = row_selected(d, j);                  // cells outside the strips are evaluated, not stored
         c[q].set_cell(d, i, j);
         uv_pre_load<FIRST_X>(d, c[q], ilay, gene, true, pre[q]);
     }
-    // ring cells of the first update: one row (65) + one column (UV_TY); other threads load their own cell again
+    // ring cells of the first update: one row (65) + one column (TY); other threads load their own cell again
     int rr1 = -1, cc1 = -1;
-    if (tid <= UV_TX) { rr1 = FIRST_X ? 0 : UV_TY; cc1 = tid; }
-    else if (tid <= UV_TX + UV_TY) { rr1 = (tid - UV_TX - 1) + ROFF; cc1 = FIRST_X ? UV_TX : 0; }
+    if (tid <= G::TX) { rr1 = FIRST_X ? 0 : G::TY; cc1 = tid; }
+    else if (tid <= G::TX + G::TY) { rr1 = (tid - G::TX - 1) + ROFF; cc1 = FIRST_X ? G::TX : 0; }
     const int ra = rr1 >= 0 ? (FIRST_X ? x0 : x0 - 1) + cc1 : i;
     const int rb = rr1 >= 0 ? (FIRST_X ? y0 - 1 : y0) + rr1 : y0 + wy;
     CellDenseT<true> hc;
@@ -948,7 +937,7 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
     // ---- stage
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
-        if (tid + k * UV_BLOCK < NST) {
+        if (tid + k * G::BLOCK < NST) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) s_f[f][frr[k]][fcc[k]] = fv[k][f];
             s_hl[frr[k] + 1][fcc[k] + 1] = fv[k][4];
@@ -957,19 +946,19 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
     if (hrr >= 0) s_hl[hrr][hcc] = hring;
     __syncthreads();
     // ---- phase B loads (second update): in flight while the first update is evaluated
-    double pre2[UV_Q][8];
+    double pre2[Q][8];
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) uv_pre_load<!FIRST_X>(d, c[q], ilay, gene, false, pre2[q]);
+    for (int q = 0; q < Q; ++q) uv_pre_load<!FIRST_X>(d, c[q], ilay, gene, false, pre2[q]);
     // ---- first update: own cells, then the ring cell
     const double hs2 = 2.0 * d.hsal;
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
-        const int r = wy + UV_WAVES * q;
-        const ShLds<FIRST_X> sh{s_f, s_hl, r + 1, lx + 1, d.ocrp, hs2};
+    for (int q = 0; q < Q; ++q) {
+        const int r = wy + G::WAVES * q;
+        const ShLds<Q, FIRST_X> sh{s_f, s_hl, r + 1, lx + 1, d.ocrp, hs2};
         s_h[r + ROFF][lx + COFF] = uv_first_eval<FIRST_X, true, true, true, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q], pre[q], ZV);
     }
     if (rr1 >= 0) {
-        const ShLds<FIRST_X> sh{s_f, s_hl, rb - (y0 - 1), ra - (x0 - 1), d.ocrp, hs2};
+        const ShLds<Q, FIRST_X> sh{s_f, s_hl, rb - (y0 - 1), ra - (x0 - 1), d.ocrp, hs2};
         s_h[rr1][cc1] = uv_first_eval<FIRST_X, true, false, true, SF>(d, hc, ilay, gene, ramp, ctim, sh, true, preR, ZV);
     }
     __syncthreads();
@@ -978,36 +967,37 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
     const UVio io{FIRST_X ? d.v : d.u, FIRST_X ? d.v_alt : d.u_alt, FIRST_X ? d.hv_alt : d.hu_alt,
                   dm[0], dm[1], dm[2], dm[0]};
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
+    for (int q = 0; q < Q; ++q) {
         if (!wr[q]) continue;
-        const int r = wy + UV_WAVES * q;
+        const int r = wy + G::WAVES * q;
         double q0, qb, qa, qd;
         if (FIRST_X) {   // v: self, S, E, SE of h_u
             q0 = s_h[r + 1][lx]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r][lx + 1];
         } else {         // u: self, W, N, NW of h_v
             q0 = s_h[r][lx + 1]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r + 1][lx];
         }
-        const ShLds<!FIRST_X> sh{s_f, s_hl, r + 1, lx + 1, d.ocrp, hs2};
+        const ShLds<Q, !FIRST_X> sh{s_f, s_hl, r + 1, lx + 1, d.ocrp, hs2};
         uv_core<!FIRST_X, true, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh, true, pre2[q], ZV);
     }
 }
 
 // Every other workgroup — boundary tiles (wraps, sentinel, masks), and all tiles of the v_cc/v_ll
 // form (PROD = false) — reads global memory as the unfused sweeps do.
-template <bool FIRST_X, bool PROD, bool INT, bool SF>
+template <int Q, bool FIRST_X, bool PROD, bool INT, bool SF>
 __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, int ilay, double gene,
-                                              double ramp, double ctim, double (*s_h)[UV_LDX]) {
+                                              double ramp, double ctim, double (*s_h)[TileGeom<Q>::LDX]) {
+    using G = TileGeom<Q>;
     const int tid = threadIdx.x;
     const int lx = tid & 63, wy = tid >> 6;
     const int i = x0 + lx;
     // s_h coordinates: FIRST_X  -> rows y0-1 .. y0+TY-1, cols x0 .. x0+TX   (own cell at [r+1][lx])
     //                  !FIRST_X -> rows y0 .. y0+TY,     cols x0-1 .. x0+TX-1 (own cell at [r][lx+1])
     constexpr int ROFF = FIRST_X ? 1 : 0, COFF = FIRST_X ? 0 : 1;
-    CellDenseT<INT> c[UV_Q];
-    bool ok[UV_Q], wr[UV_Q];
+    CellDenseT<INT> c[Q];
+    bool ok[Q], wr[Q];
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
-        const int r = wy + UV_WAVES * q, j = y0 + r;
+    for (int q = 0; q < Q; ++q) {
+        const int r = wy + G::WAVES * q, j = y0 + r;
         ok[q] = (i <= d.L) && (j <= d.M);
         if (!INT && ok[q] && !slot_is_cell(d, i + (j - 1) * d.P)) ok[q] = false;     // embedded: land slots are never evaluated
         wr[q] = ok[q] && row_selected(d, j);       // cells outside the strips are evaluated, not stored
@@ -1025,13 +1015,13 @@ __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, 
         }
         s_h[r + ROFF][lx + COFF] = hnew;
     }
-    // ring cells: one row (65) + one column (UV_TY)
+    // ring cells: one row (65) + one column (TY)
     {
         int rr = -1, cc = -1;
-        if (tid <= UV_TX) {                       // the extra row
-            rr = FIRST_X ? 0 : UV_TY; cc = tid;
-        } else if (tid <= UV_TX + UV_TY) {        // the extra column
-            rr = (tid - UV_TX - 1) + ROFF; cc = FIRST_X ? UV_TX : 0;
+        if (tid <= G::TX) {                       // the extra row
+            rr = FIRST_X ? 0 : G::TY; cc = tid;
+        } else if (tid <= G::TX + G::TY) {        // the extra column
+            rr = (tid - G::TX - 1) + ROFF; cc = FIRST_X ? G::TX : 0;
         }
         if (rr >= 0) {
             const int a = (FIRST_X ? x0 : x0 - 1) + cc;
@@ -1047,9 +1037,9 @@ __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, 
     const UVio io{FIRST_X ? d.v : d.u, FIRST_X ? d.v_alt : d.u_alt, FIRST_X ? d.hv_alt : d.hu_alt,
                   dm[0], dm[1], dm[2], dm[0]};
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
+    for (int q = 0; q < Q; ++q) {
         if (!wr[q]) continue;
-        const int r = wy + UV_WAVES * q;
+        const int r = wy + G::WAVES * q;
         double q0, qb, qa, qd;
         if (FIRST_X) {   // v: self, S, E, SE of h_u
             q0 = s_h[r + 1][lx]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r][lx + 1];
@@ -1069,9 +1059,9 @@ __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, 
 // them there like the interior workgroups do; masks stay the predicates of CellDenseT<false>, and the thickness
 // curvatures come from the arrays k_mont_visc stores for these tiles (they carry the coast masks, :2393-2404).
 // (Frames a few tiles tall or wide — the soliton channel, a band of a multi-GPU run — are mostly edge tiles.)
-template <bool XDIR>
+template <int Q, bool XDIR>
 struct ShLdsEdge {                                   // field order in the stage: 0 mont 1 pvor 2 pcd 3 qlr
-    const UVstage *s; const double (*h)[UV_SLDX];    // h = the hlay image
+    const UVstage<Q> *s; const double (*h)[TileGeom<Q>::SLDX];    // h = the hlay image
     int r, c;                                        // staged position of the cell (UVstage coordinates)
     const DevView &d; int ipnt, cb, ilay;            // for the curvature arrays
     static constexpr int RB = XDIR ? 0 : -1, CB = XDIR ? -1 : 0;   // b neighbour: W | S
@@ -1090,16 +1080,18 @@ struct ShLdsEdge {                                   // field order in the stage
     template <bool X> __device__ __forceinline__ double d2h_b() const { return LL(X ? d.d2hx : d.d2hy, cb, ilay); }
 };
 
-template <bool FIRST_X, bool SF>
+template <int Q, bool FIRST_X, bool SF>
 __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int y0, int ilay, double gene, double ramp,
-                                                   double ctim, double (*s_h)[UV_LDX], UVstage *s_f, double (*s_hl)[UV_HLDX]) {
-    static_assert(sizeof(double) * UV_HROWS * UV_HLDX >= sizeof(UVstage), "the hlay image fits the widened hlay stage");
-    double (*s_hs)[UV_SLDX] = (double (*)[UV_SLDX])s_hl;
+                                                   double ctim, double (*s_h)[TileGeom<Q>::LDX], UVstage<Q> *s_f,
+                                                   double (*s_hl)[TileGeom<Q>::HLDX]) {
+    using G = TileGeom<Q>;
+    static_assert(sizeof(UVhstage<Q>) >= sizeof(UVstage<Q>), "the hlay image fits the widened hlay stage");
+    double (*s_hs)[G::SLDX] = (double (*)[G::SLDX])s_hl;
     const int tid = threadIdx.x;
     const int lx = tid & 63, wy = tid >> 6;
     const int i = x0 + lx;
     constexpr int ROFF = FIRST_X ? 1 : 0, COFF = FIRST_X ? 0 : 1;      // s_h coordinates as in body_uv_fused
-    constexpr int NST = UV_SROWS * UV_SLDX, NIT = (NST + UV_BLOCK - 1) / UV_BLOCK;
+    constexpr int NST = G::SROWS * G::SLDX, NIT = (NST + G::BLOCK - 1) / G::BLOCK;
     // ---- stage by lookup
     {
         const double *src[5] = {d.mont, d.pvor, d.pcd, d.qlr, d.hlay};
@@ -1107,9 +1099,9 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
         int frr[NIT], fcc[NIT];
 #pragma unroll
         for (int k = 0; k < NIT; ++k) {
-            const int idx = tid + k * UV_BLOCK;
+            const int idx = tid + k * G::BLOCK;
             const int idc = idx < NST ? idx : tid;
-            frr[k] = idc / UV_SLDX; fcc[k] = idc - frr[k] * UV_SLDX;
+            frr[k] = idc / G::SLDX; fcc[k] = idc - frr[k] * G::SLDX;
             int a = x0 - 1 + fcc[k], b = y0 - 1 + frr[k];
             const int t = halo_target<false>(d, a, b) ? a + (b - 1) * d.P : 0;     // 0: the sentinel (zero in every one of these arrays)
 #pragma unroll
@@ -1117,18 +1109,18 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
         }
 #pragma unroll
         for (int k = 0; k < NIT; ++k) {
-            if (tid + k * UV_BLOCK < NST) {
+            if (tid + k * G::BLOCK < NST) {
 #pragma unroll
                 for (int f = 0; f < 4; ++f) s_f[f][frr[k]][fcc[k]] = fv[k][f];
                 s_hs[frr[k]][fcc[k]] = fv[k][4];
             }
         }
     }
-    CellDenseT<false> c[UV_Q];
-    bool ok[UV_Q], wr[UV_Q];
+    CellDenseT<false> c[Q];
+    bool ok[Q], wr[Q];
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
-        const int j = y0 + wy + UV_WAVES * q;
+    for (int q = 0; q < Q; ++q) {
+        const int j = y0 + wy + G::WAVES * q;
         ok[q] = (i <= d.L) && (j <= d.M);
         if (ok[q] && !slot_is_cell(d, i + (j - 1) * d.P)) ok[q] = false;     // embedded: land slots are never evaluated
         wr[q] = ok[q] && row_selected(d, j);       // cells outside the strips are evaluated, not stored
@@ -1137,8 +1129,8 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
     __syncthreads();
     // ---- first update: own cells, then the ring cell
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
-        const int r = wy + UV_WAVES * q, j = y0 + r;
+    for (int q = 0; q < Q; ++q) {
+        const int r = wy + G::WAVES * q, j = y0 + r;
         double hnew = 0.0;
         if (ok[q]) {
             const int cb = FIRST_X ? c[q].template nb<5>() : c[q].template nb<7>();
@@ -1150,7 +1142,7 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
                 (void)uv_first_eval<FIRST_X, true, true, false, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
                 hnew = uv_first_halo<FIRST_X, true, SF>(d, i, j, ilay, gene, ramp, ctim);
             } else {
-                const ShLdsEdge<FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
+                const ShLdsEdge<Q, FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
                 hnew = uv_first_eval<FIRST_X, true, true, false, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
             }
         }
@@ -1158,8 +1150,8 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
     }
     {
         int rr = -1, cc = -1;
-        if (tid <= UV_TX) { rr = FIRST_X ? 0 : UV_TY; cc = tid; }                              // the extra row
-        else if (tid <= UV_TX + UV_TY) { rr = (tid - UV_TX - 1) + ROFF; cc = FIRST_X ? UV_TX : 0; }   // the extra column
+        if (tid <= G::TX) { rr = FIRST_X ? 0 : G::TY; cc = tid; }                              // the extra row
+        else if (tid <= G::TX + G::TY) { rr = (tid - G::TX - 1) + ROFF; cc = FIRST_X ? G::TX : 0; }   // the extra column
         if (rr >= 0) {
             const int ga = (FIRST_X ? x0 : x0 - 1) + cc, gb = (FIRST_X ? y0 - 1 : y0) + rr;    // geometric position
             int a = ga, b = gb;
@@ -1173,7 +1165,7 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
                     CellDenseT<false> h;
                     h.set_cell(d, a, b);
                     const int cb = FIRST_X ? h.template nb<5>() : h.template nb<7>();
-                    const ShLdsEdge<FIRST_X> sh{s_f, s_hs, gb - (y0 - 1), ga - (x0 - 1), d, h.ipnt, cb, ilay};
+                    const ShLdsEdge<Q, FIRST_X> sh{s_f, s_hs, gb - (y0 - 1), ga - (x0 - 1), d, h.ipnt, cb, ilay};
                     val = uv_first_eval<FIRST_X, true, false, false, SF>(d, h, ilay, gene, ramp, ctim, sh);
                 }
             }
@@ -1186,9 +1178,9 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
     const UVio io{FIRST_X ? d.v : d.u, FIRST_X ? d.v_alt : d.u_alt, FIRST_X ? d.hv_alt : d.hu_alt,
                   dm[0], dm[1], dm[2], dm[0]};
 #pragma unroll
-    for (int q = 0; q < UV_Q; ++q) {
+    for (int q = 0; q < Q; ++q) {
         if (!wr[q]) continue;
-        const int r = wy + UV_WAVES * q;
+        const int r = wy + G::WAVES * q;
         double q0, qb, qa, qd;
         if (FIRST_X) { q0 = s_h[r + 1][lx]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r][lx + 1]; }
         else         { q0 = s_h[r][lx + 1]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r + 1][lx]; }
@@ -1198,51 +1190,45 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
             const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
             uv_core<!FIRST_X, true, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
         } else {
-            const ShLdsEdge<!FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
+            const ShLdsEdge<Q, !FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
             uv_core<!FIRST_X, true, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
         }
     }
 }
 
 // ZV (with PROD): v_cc = v_ll = +0 everywhere — interior workgroups drop the viscous products
-#if defined(UV_WAVES_PER_EU) && UV_WAVES_PER_EU > 0
-#define UV_OCC_ATTR __attribute__((amdgpu_waves_per_eu(UV_WAVES_PER_EU)))
-#else
-#define UV_OCC_ATTR
-#endif
-template <bool FIRST_X, bool PROD, bool ZV, bool SF>
+template <int Q, bool FIRST_X, bool PROD, bool ZV, bool SF>
 __device__ __forceinline__ void uv_fused_workgroup(const DevView &d, double gene, double ramp, double ctim) {
-    __shared__ double s_h[UV_TY + 1][UV_LDX];
-    __shared__ UVstage s_f[PROD ? 4 : 1];                    // (ZV: the interior workgroups use two of them, the edge ones all four)
-    __shared__ double s_hl[PROD ? UV_HROWS : 1][UV_HLDX];
-    const TileMap tm(d, UV_TX, UV_TY);
+    using G = TileGeom<Q>;
+    __shared__ double s_h[G::TY + 1][G::LDX];
+    __shared__ UVstage<Q> s_f[PROD ? 4 : 1];                    // (ZV: the interior workgroups use two of them, the edge ones all four)
+    __shared__ double s_hl[PROD ? G::HROWS : 1][G::HLDX];
+    const TileMap tm(d, G::TX, G::TY);
     int ty, ch;
     if (!tm.locate(blockIdx.x, ty, ch)) return;
-    const int x0 = ch * UV_TX + 1, y0 = ty * UV_TY + 1;
+    const int x0 = ch * G::TX + 1, y0 = ty * G::TY + 1;
     const int ilay = blockIdx.y + 1;
-    const bool interior = x0 - 1 >= 2 && x0 + UV_TX <= d.L - 2 && y0 - 1 >= 2 && y0 + UV_TY <= d.M - 2
-                          && y0 - 1 + d.joff >= 2 && y0 + UV_TY + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, UV_TY);
-    if (interior && PROD) body_uv_fused_staged<FIRST_X, ZV, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
-    else if (interior) body_uv_fused<FIRST_X, PROD, true, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
-    else if (PROD && !d.edge_global) body_uv_fused_edge<FIRST_X, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
-    else body_uv_fused<FIRST_X, PROD, false, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
+    const bool interior = x0 - 1 >= 2 && x0 + G::TX <= d.L - 2 && y0 - 1 >= 2 && y0 + G::TY <= d.M - 2
+                          && y0 - 1 + d.joff >= 2 && y0 + G::TY + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, G::TY);
+    if (interior && PROD) body_uv_fused_staged<Q, FIRST_X, ZV, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
+    else if (interior) body_uv_fused<Q, FIRST_X, PROD, true, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
+    else if (PROD && !d.edge_global) body_uv_fused_edge<Q, FIRST_X, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
+    else body_uv_fused<Q, FIRST_X, PROD, false, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
 }
-template <bool FIRST_X, bool PROD, bool ZV = false>
-__global__ __launch_bounds__(UV_BLOCK) UV_OCC_ATTR void k_uv_fused(DevView d, double gene, double ramp, double ctim) {
-    uv_fused_workgroup<FIRST_X, PROD, ZV, false>(d, gene, ramp, ctim);
+template <int Q, bool FIRST_X, bool PROD, bool ZV = false>
+__global__ __launch_bounds__(TileGeom<Q>::BLOCK) void k_uv_fused(DevView d, double gene, double ramp, double ctim) {
+    uv_fused_workgroup<Q, FIRST_X, PROD, ZV, false>(d, gene, ramp, ctim);
 }
 // ... with distribute_stress formed inside (SF): its own kernels, so that the unforced ones do not carry its registers.  Their
 // zero-viscosity form takes 129 VGPRs; capped for four waves per SIMD it is slower than left at three (wind-driven
 // 4096x2048x2, same box: u+v 730 vs 714 us)
-template <bool FIRST_X, bool PROD, bool ZV = false>
-#ifndef UV_SF_WAVES_PER_EU
-#define UV_SF_WAVES_PER_EU 3
-#endif
-__global__ __launch_bounds__(UV_BLOCK) __attribute__((amdgpu_waves_per_eu(UV_SF_WAVES_PER_EU))) void k_uv_fused_sf(DevView d, double gene, double ramp, double ctim) {
-    uv_fused_workgroup<FIRST_X, PROD, ZV, true>(d, gene, ramp, ctim);
+template <int Q, bool FIRST_X, bool PROD, bool ZV = false>
+__global__ __launch_bounds__(TileGeom<Q>::BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void k_uv_fused_sf(DevView d, double gene, double ramp, double ctim) {
+    uv_fused_workgroup<Q, FIRST_X, PROD, ZV, true>(d, gene, ramp, ctim);
 }
+template <int Q>
 static inline dim3 uv_fused_grid(const DevView &d) {
-    return dim3(TileMap(d, UV_TX, UV_TY).blocks(), (unsigned)d.nlay, 1);
+    return dim3(TileMap(d, TileGeom<Q>::TX, TileGeom<Q>::TY).blocks(), (unsigned)d.nlay, 1);
 }
 
 // ---- distribute_stress, private_mod.f95:1921-2149, as ONE launch --------------------------------------------------

@@ -1,10 +1,10 @@
-"""The two tile geometries of the tiled sweeps (k_mont_visc, k_uv_fused, k_uv_fused_sf; beom_launch_tiled.h) against the
-oracle, and columns of more than 8 layers.
+"""The two tile geometries of the tiled sweeps (k_mont_visc, k_uv_fused, k_uv_fused_sf) against the oracle, and columns of
+more than 8 layers.
 
-beom_engine.hip builds both sweeps for 64 x 8 tiles (two rows per thread, MV_Q = UV_Q = 2) and for 64 x 4 tiles (one row
-per thread) and picks 64 x 4 for every frame of at most 5000 tiles of 64 x 8, so that small frames would otherwise only ever
-meet one of them.  Here BEOM_TILE4 (read when a handle is created) forces each geometry in turn on frames around the tile
-thresholds of both, with every boundary configuration, with every layer count of the fused Montgomery sweep, in every
+beom_engine.hip instantiates both sweeps for 64 x 8 tiles (two rows per thread, Q = 2) and for 64 x 4 tiles (one row per
+thread, Q = 1) and picks 64 x 4 for every frame of at most 5000 tiles of 64 x 8, so that small frames would otherwise only
+ever meet one of them.  Here BEOM_TILE4 (read when a handle is created) forces each geometry in turn on frames around the
+tile thresholds of both, with every boundary configuration, with every layer count of the fused Montgomery sweep, in every
 scheduling regime of TileMap (beom_dev.h), and at the README's land figure, where the engine picks 64 x 8 on its own.
 Above 8 layers the engine runs per-layer Montgomery and viscosity launches next to the fused u+v sweep.
 
@@ -157,7 +157,7 @@ def test_frames_at_the_tile_thresholds(config, frame):
 @pytest.mark.parametrize("leith", [True, False], ids=["leith", "standing_visc"])
 @pytest.mark.parametrize("nlay", range(1, 9))
 def test_every_mont_visc_instantiation(nlay, leith):
-    """k_mont_visc<NL, LEITH> for NL = 1..8 in both geometries on a frame with deep tiles and a ragged M in both (M = 41:
+    """k_mont_visc<Q, NL, LEITH> for NL = 1..8 in both geometries on a frame with deep tiles and a ragged M in both (M = 41:
     M % 8 == 1, M % 4 == 1).  Without Leith (dvis = 0) v_cc, v_ll stand at bvis after step 3."""
     p, files = I.case_headline(258, 40, nlay, dvis=0.2 if leith else 0.0)
     if not leith:

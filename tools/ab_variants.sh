@@ -1,6 +1,6 @@
 #!/bin/bash
-# Several engine builds (ab/<name>.so, e.g. other tile geometries: -DUV_WAVES=8, -DMV_Q=1) against the in-tree library on
-# tools/bench_case.py cases, same box, alternating.  VARIANTS="base w8 q1" CASES="soliton jet" tools/ab_variants.sh
+# Several engine builds (ab/<name>.so from edited copies of beom_amd/csrc, e.g. another TileGeom or waves-per-EU cap) against
+# the in-tree library on tools/bench_case.py cases, same box, alternating.  VARIANTS="base w8 cap4" CASES="soliton jet" tools/ab_variants.sh
 R=${GRAFT_REPO_ROOT:-$PWD}
 for rep in 1 2; do
   for c in ${CASES:-soliton jet stommel}; do

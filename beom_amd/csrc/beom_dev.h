@@ -64,7 +64,6 @@ struct DevView {
     int keep_visc;                // fused sweep (Leith) also stores v_cc, v_ll: they stand for n_3d - 1 more steps
     int zero_visc;                // v_cc = v_ll = +0 everywhere and never refreshed: the viscous products are +-0
     int lean_d2h;                 // fused sweep stores d2hx, d2hy only where the fused u+v sweep reads them
-    int edge_global;              // k_uv_fused: edge workgroups read global memory throughout (A/B switch; default: staged by lookup)
     // biharmonic viscosity (svis > 0, :2508-2599): Laplacians and thickness-weighted fluxes
     double *delu, *delv, *uu4, *vv4; double svis;
     // packed layout: per run of 64 cells (dN, dS) if the run is a uniform wet interior, else (0, 0); may be null

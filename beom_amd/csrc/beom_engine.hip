@@ -11,6 +11,7 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "beom_dev.h"
@@ -69,7 +70,7 @@ struct beom_engine {
     DevView d{};
     bool dense = false;
     std::vector<void *> allocs;
-    int32_t *slot_of_dev = nullptr;    // embedded frames: packed index -> slot (device copy; null otherwise)
+    const int32_t *slot_of_dev = nullptr;   // embedded frames: packed index -> slot (device copy; null otherwise)
     bool embedded = false;
     void *stage = nullptr;             // device image of ONE caller-layout slice [0:ndeg] (<= 32 B per cell) for uploads / downloads
     size_t stage_bytes = 0;
@@ -138,7 +139,7 @@ int slice_to_device(beom_engine *E, T *dev, const T *host, int inner, int K, int
                            dev, (const T *)E->stage, d.ncell + 1, inner, K, m);
     }
     hipLaunchKernelGGL((k_repack<T, true, REMAP>), dim3((unsigned)((work + BEOM_BLOCK - 1) / BEOM_BLOCK)), dim3(BEOM_BLOCK), 0, E->stream,
-                       dev, (T *)E->stage, (long long)d.ndeg, d.L, d.P ? d.P : d.L, inner, K, m, (const int32_t *)E->slot_of_dev);
+                       dev, (T *)E->stage, (long long)d.ndeg, d.L, d.P ? d.P : d.L, inner, K, m, E->slot_of_dev);
     return 0;
 }
 template <class T>
@@ -155,8 +156,7 @@ void slice_gather(beom_engine *E, const T *dev, int inner, int K, int m) {      
     const DevView &d = E->d;
     const long long work = ((long long)d.ndeg + 1) * inner;
     hipLaunchKernelGGL((k_repack<T, false, false>), dim3((unsigned)((work + BEOM_BLOCK - 1) / BEOM_BLOCK)), dim3(BEOM_BLOCK), 0, E->stream,
-                       const_cast<T *>(dev), (T *)E->stage, (long long)d.ndeg, d.L, d.P ? d.P : d.L, inner, K, m,
-                       (const int32_t *)E->slot_of_dev);
+                       const_cast<T *>(dev), (T *)E->stage, (long long)d.ndeg, d.L, d.P ? d.P : d.L, inner, K, m, E->slot_of_dev);
 }
 
 // a static array [outer][0:ndeg][inner] of the caller -> a new device array; src == nullptr: zeros
@@ -181,6 +181,198 @@ bool any_nonzero(const double *a, size_t n) {
     return false;
 }
 
+// ---- beom_create in steps: each returns 0 or an error code with its message in errm ---------------------------------
+int check_create_args(const beom_params *prm, const beom_handle *out, int device, const beom_dense::Grid &g,
+                      const beom_statics &st, char *errm, int errm_len) {
+    if (!prm || !out) { set_err(errm, errm_len, "beom_create: null argument"); return -1; }
+    if (prm->abi_version != BEOM_ABI_VERSION) { set_err(errm, errm_len, "beom_create: ABI version mismatch (%d vs %d)", prm->abi_version, BEOM_ABI_VERSION); return -2; }
+    if (prm->nlay < 1 || prm->nlay > BEOM_MAX_LAYERS || prm->ndeg < 1 || prm->lm < 1 || prm->mm < 1) { set_err(errm, errm_len, "beom_create: bad sizes"); return -3; }
+    if (prm->rgld > 0.5 && (prm->variant == 1 || prm->slab_mm > 0 || prm->ocrp < 0.5)) {
+        // (private_mod3d.f95 has no lid; the Poisson operators are only initialised with ocrp = 1, :505-563; the pressure sweep
+        // couples the whole frame, so no bands)
+        set_err(errm, errm_len, "beom_create: rgld = 1 (rigid lid, private_mod.f95:1705-1838) needs variant 0, ocrp = 1 and a whole frame (no bands)");
+        return -5;
+    }
+    if (prm->variant == 1 && prm->nlay < 3) { set_err(errm, errm_len, "beom_create: variant 1 (private_mod3d.f95) needs nlay >= 3"); return -7; }
+    if (!g.neig || !g.subc || !g.mk_u || !g.mk_v || !g.mk_n || !g.mkpe || !g.mkpi || !st.fcor || !st.h_th || !st.nudg || !st.fnud) { set_err(errm, errm_len, "beom_create: null static array"); return -1; }
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (ndev <= 0 || device < 0 || device >= ndev) { set_err(errm, errm_len, "beom_create: no usable HIP device (%d visible, asked for %d); there is no CPU fallback", ndev, device); return -8; }
+    HIP_TRY(hipSetDevice(device));
+    if (prm->slab_mm > 0 && (prm->slab_row0 < 0 || prm->slab_row0 + prm->mm + 1 > prm->slab_mm + 1)) { set_err(errm, errm_len, "beom_create: slab rows outside the global frame"); return -3; }
+    return 0;
+}
+
+// the constants of the view (everything but the layout and the device arrays), and which optional terms are live
+void fill_view(DevView &d, const beom_params &prm, const beom_statics &st) {
+    const size_t n1h = (size_t)prm.ndeg + 1, nl = (size_t)prm.nlay;      // n1h: cells per layer in the caller's arrays
+    d.ndeg = prm.ndeg; d.nlay = prm.nlay; d.lm = prm.lm; d.mm = prm.mm; d.nsal = prm.nsal;
+    d.variant = prm.variant; d.n1 = (long long)n1h; d.ncell = prm.ndeg;
+    d.L = prm.lm + 1; d.M = prm.mm + 1;
+    d.dl = prm.dl; d.dt = prm.dt; d.grav = prm.grav; d.rho0 = prm.rho0; d.beta = prm.beta;
+    d.epsi = prm.epsi; d.gamm = prm.gamm; d.del1 = prm.del1; d.del2 = prm.del2; d.hmin = prm.hmin;
+    d.hsal = prm.hsal; d.bvis = prm.bvis; d.dvis = prm.dvis; d.bdrg = prm.bdrg; d.tdrg = prm.tdrg;
+    d.qdrg = prm.qdrg; d.hsbl = prm.hsbl; d.hbbl = prm.hbbl; d.uadv = prm.uadv; d.ocrp = prm.ocrp;
+    d.rgld = prm.rgld; d.invf = prm.invf; d.w_ti = prm.w_ti; d.svis = prm.svis;
+    d.mm_glob = prm.slab_mm > 0 ? prm.slab_mm : prm.mm;
+    for (int i = 0; i < BEOM_MAX_LAYERS; ++i) d.rhon[i] = prm.rhon[i];
+    d.i_dl = 1.0 / prm.dl;                      // private_mod.f95:1428,1511,1599,2321
+    d.i_gr = 1.0 / prm.grav;                    // :2322
+    d.i_ns = 1.0 / (double)(prm.nsal - 1);      // :2328
+    d.i_r0 = 1.0 / prm.rho0;                    // :1429
+    d.i_r1 = 1.0 / prm.rhon[0];                 // :1430
+    for (int i = 0; i < prm.nlay; ++i) d.i_rn[i] = 1.0 / prm.rhon[i];   // :2329
+    d.nstrip = 1; d.jlo0 = 1; d.jhi0 = d.M; d.jlo1 = 1; d.jhi1 = 0;
+    d.slab = prm.slab_mm > 0 ? 1 : 0;
+    d.joff = d.slab ? prm.slab_row0 : 0;
+    d.Mg = d.slab ? prm.slab_mm + 1 : d.M;
+    d.has_hdot = any_nonzero(st.hdot, nl * n1h);
+    d.has_tide = any_nonzero(st.tide, 6 * n1h);
+    d.has_bodf = any_nonzero(st.bodf, 2 * nl);
+    d.has_nudg = any_nonzero(st.nudg, 3 * n1h);
+    d.has_hto = any_nonzero(st.h_to, n1h);
+    d.rho_top = prm.rhon[0]; d.rho_bot = prm.rhon[nl - 1];
+}
+
+// which paths the steps take: fused sweeps, tile geometry, stress terms, stress folded into the momentum sweep
+void choose_paths(beom_engine *E, const beom_dense::Grid &g, const beom_statics &st) {
+    const beom_params &prm = E->P;
+    DevView &d = E->d;
+    const size_t n1h = (size_t)prm.ndeg + 1, nl = (size_t)prm.nlay;
+    for (size_t i = 0; i < n1h; ++i) { if (g.mk_u[i] > 0.5) E->any_u = 1; if (g.mk_v[i] > 0.5) E->any_v = 1; }
+    // frames of few rounds of workgroups: the 64 x 4 tile geometry, one row per thread (a workgroup's lifetime is what the
+    // step time is made of there).  Same box, us per step, 64 x 8 -> 64 x 4: stommel 128^2 31.2 -> 24.0, soliton 2048x256
+    // 53.5 -> 43.6, 1024x128x4 74.8 -> 56.3, sill 4096x512x4 614 -> 596; jet 2048^2 x 2 535 -> 557, 4096^2 x 4 and larger: slower
+    E->tile4 = E->dense && (long long)((d.L + 63) / 64) * ((d.M + 7) / 8) <= 5000;
+    if (getenv("BEOM_TILE4")) E->tile4 = E->dense && atoi(getenv("BEOM_TILE4")) != 0;      // (A/B switch)
+    if (E->lid) E->fuse = E->fuse_uv = false;      // the lid's flux rebuild reads the stored d2hx, d2hy of the last layer
+    if (st.taus) for (size_t i = 0; i < 2 * n1h; ++i) if (std::fabs(st.taus[i]) > 1.e-7) { E->wind = true; break; }   // :1945
+    E->bot = prm.bdrg > 1.e-7;                                                                                        // :1969
+    E->top = prm.tdrg > 1.e-7;                                                                                        // :1991
+    d.has_wind = E->wind; d.has_bot = E->bot; d.has_top = E->top;
+    d.has_stress = E->wind || E->bot || E->top;
+    bool neg0 = false;                         // a body force of exactly -0 would make the sign of a skipped +-0 visible
+    if (st.bodf) for (size_t i = 0; i < 2 * nl; ++i) if (st.bodf[i] == 0.0 && std::signbit(st.bodf[i])) neg0 = true;
+    E->fold_static_ok = E->dense && prm.ocrp < 0.5 && !E->lid && d.has_stress && !neg0;
+}
+
+// a host table -> a new device array of n >= v.size() elements (the rest zeroed if zero)
+template <class T>
+int upload_table(beom_engine *E, const T **dst, const std::vector<T> &v, size_t n, bool zero, char *errm, int errm_len) {
+    T *q = nullptr;
+    const int rc = dev_alloc(E, &q, n, errm, errm_len, zero);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));      // (v is the caller's temporary)
+    *dst = q;
+    return 0;
+}
+
+// the staging buffer, the layout's tables, the caller's static arrays, the wave table, the nudging tiles (in this order)
+int upload_statics(beom_engine *E, const beom_dense::Layout &lay, const beom_dense::WaveTable &wt,
+                   const std::vector<unsigned char> &ngt, const beom_dense::Grid &g, const beom_statics &st,
+                   char *errm, int errm_len) {
+    DevView &d = E->d;
+    const size_t n1h = (size_t)d.ndeg + 1, nl = (size_t)d.nlay;
+    E->stage_bytes = n1h * 32;                        // the widest slice: neig (8 x int32), a history (3 doubles)
+    HIP_TRY(hipMalloc(&E->stage, E->stage_bytes));
+    int rc;
+    if (E->embedded) {
+        if ((rc = upload_table(E, &E->slot_of_dev, lay.slot_of, lay.slot_of.size(), false, errm, errm_len))) return rc;
+        if ((rc = upload_table(E, &d.pk_of, lay.pk_of, (size_t)d.n1, true, errm, errm_len))) return rc;
+        if ((rc = upload_table(E, &d.reg4, lay.reg4, lay.reg4.size(), false, errm, errm_len))) return rc;
+    }
+    if ((rc = dev_upload<int32_t, true>(E, &d.neig, g.neig, 1, 8, errm, errm_len))) return rc;
+    if ((rc = dev_upload(E, &d.subc, g.subc, 2, 1, errm, errm_len))) return rc;
+    auto up = [&](const double **dst, const double *src, size_t outer, int inner = 1) {
+        if (!rc) rc = dev_upload(E, dst, src, outer, inner, errm, errm_len);
+    };
+    up(&d.mk_u, g.mk_u, 1); up(&d.mk_v, g.mk_v, 1); up(&d.mk_n, g.mk_n, 1); up(&d.mkpe, g.mkpe, 1); up(&d.mkpi, g.mkpi, 1);
+    up(&d.fcor, st.fcor, 1); up(&d.h_th, st.h_th, 1); up(&d.h_to, st.h_to, 1);
+    up(&d.nudg, st.nudg, 3); up(&d.fnud, st.fnud, 3 * nl); up(&d.hdot, st.hdot, nl);
+    up(&d.tide, st.tide, 3, 2); up(&d.taus, st.taus, 2);
+    // the wind stress as tt3d holds it: at real cells only (distribute_stress writes cells 1..ndeg, :1945-1966; index 0 and
+    // every device slot that is no cell stay +0)
+    std::vector<double> tc(2 * n1h, 0.0);
+    if (st.taus) { std::memcpy(tc.data(), st.taus, 2 * n1h * sizeof(double)); tc[0] = 0.0; tc[n1h] = 0.0; }
+    up(&d.taus_cells, tc.data(), 2);
+    if (rc) return rc;
+    double *q = nullptr;                              // bodf(nlay, 2): no cell dimension
+    if ((rc = dev_alloc(E, &q, 2 * nl, errm, errm_len, true))) return rc;
+    if (st.bodf) HIP_TRY(hipMemcpyAsync(q, st.bodf, 2 * nl * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    d.bodf = q;
+    if (wt.uniform > 0 && (rc = upload_table(E, &d.woff, wt.woff, wt.woff.size(), false, errm, errm_len))) return rc;
+    if (!ngt.empty()) {
+        if ((rc = upload_table(E, &d.ngt, ngt, ngt.size(), false, errm, errm_len))) return rc;
+        d.ngt_nx = (d.L + 63) / 64;
+    }
+    return 0;
+}
+
+// the state, the scratch of the sweeps, and v_cc = v_ll = bvis everywhere, sentinel included (initialize_variables, :276-277)
+int alloc_state(beom_engine *E, char *errm, int errm_len) {
+    DevView &d = E->d;
+    const size_t n = (size_t)d.nlay * (size_t)d.n1;
+    int rc = 0;
+    auto al = [&](std::initializer_list<double **> arrays, size_t len) {
+        for (double **a : arrays) if (!rc) rc = dev_alloc(E, a, len, errm, errm_len);
+    };
+    al({&d.hlay, &d.u, &d.v, &d.h_u, &d.h_v, &d.rs[0], &d.rs[1], &d.dmx[0], &d.dmx[1], &d.dmx[2], &d.dmy[0], &d.dmy[1], &d.dmy[2]}, n);
+    if (E->dense) al({&d.dmx[3], &d.dmy[3], &d.u_alt, &d.v_alt, &d.hu_alt, &d.hv_alt}, n);      // partners for the fused U+V sweep
+    al({&d.v_cc, &d.v_ll}, n);
+    al({&d.tt3d, &d.tb3d, &d.tu3d}, 2 * n);
+    al({&d.pcd, &d.qlr, &d.mont, &d.rvor, &d.pvor, &d.dive, &d.d2hx, &d.d2hy}, n);
+    if (E->P.svis > 0.0) al({&d.delu, &d.delv, &d.uu4, &d.vv4}, n);
+    if (E->lid) al({&d.pi_s, &d.pi_rhs, &d.pi_prev}, (size_t)d.n1);
+    if (rc) return rc;
+    if (E->P.bvis != 0.0) {
+        std::vector<double> b(n, E->P.bvis);      // (padding slots too: never read)
+        HIP_TRY(hipMemcpyAsync(d.v_cc, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, E->stream));
+        HIP_TRY(hipMemcpyAsync(d.v_ll, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, E->stream));
+        HIP_TRY(hipStreamSynchronize(E->stream));
+    }
+    return 0;
+}
+
+// everything of beom_create after the argument checks, for a handle with P and device set
+int setup(beom_engine *E, const beom_dense::Grid &g, const beom_statics &st, char *errm, int errm_len) {
+    const beom_params &prm = E->P;
+    DevView &d = E->d;
+    HIP_TRY(hipStreamCreateWithFlags(&E->own_stream, hipStreamNonBlocking));
+    E->stream = E->own_stream;
+    fill_view(d, prm, st);
+    beom_dense::Layout lay = beom_dense::plan_layout(prm, d.L, d.M, d.joff, d.Mg, d.slab, g);
+    E->dense = lay.dense; E->embedded = lay.embedded;
+    d.xper = lay.xper; d.yper = lay.yper; d.embedded = lay.embedded ? 1 : 0; d.reg_nx = lay.reg_nx;
+    E->dev_index = std::move(lay.dev_index);
+    E->lid = prm.rgld > 0.5;
+    if (E->lid) {
+        const size_t n1h = (size_t)prm.ndeg + 1;
+        E->subc_host.assign(g.subc, g.subc + 2 * n1h);
+        E->neig_host.assign(g.neig, g.neig + 8 * n1h);
+    }
+    if (E->dense) {            // padded row pitch (DevView::P)
+        d.P = lay.P;
+        d.ncell = (long long)d.P * d.M;
+        d.n1 = (d.ncell + 1 + 15) / 16 * 16;
+    }
+    beom_dense::WaveTable wt;
+    if (!E->dense) wt = beom_dense::plan_wave_table(prm.ndeg, g);
+    E->uniform_waves = wt.uniform; E->total_waves = wt.total;
+    const std::vector<unsigned char> ngt = E->dense && d.has_nudg ? beom_dense::plan_nudging_tiles(lay, d.L, d.M, prm.ndeg, st.nudg)
+                                                                  : std::vector<unsigned char>();
+    int rc;
+    if ((rc = upload_statics(E, lay, wt, ngt, g, st, errm, errm_len))) return rc;
+    choose_paths(E, g, st);
+    if ((rc = alloc_state(E, errm, errm_len))) return rc;
+    const unsigned gx = (unsigned)((d.ncell + BEOM_BLOCK - 1) / BEOM_BLOCK);          // launches over all cell slots
+    const unsigned gx0 = (unsigned)((d.ncell + 1 + BEOM_BLOCK - 1) / BEOM_BLOCK);
+    E->grid_cells_layers_flat = dim3(gx, (unsigned)prm.nlay, 1);
+    E->grid_cells0 = dim3(gx0, 1, 1);
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -203,304 +395,17 @@ int beom_create(const beom_params *prm, int device, const int32_t *neig, const i
                 const double *mkpi, const double *fcor, const double *h_th, const double *h_to,
                 const double *nudg, const double *fnud, const double *hdot, const double *tide,
                 const double *bodf, const double *taus, beom_handle *out, char *errm, int errm_len) {
-    if (!prm || !out) { set_err(errm, errm_len, "beom_create: null argument"); return -1; }
-    if (prm->abi_version != BEOM_ABI_VERSION) { set_err(errm, errm_len, "beom_create: ABI version mismatch (%d vs %d)", prm->abi_version, BEOM_ABI_VERSION); return -2; }
-    if (prm->nlay < 1 || prm->nlay > BEOM_MAX_LAYERS || prm->ndeg < 1 || prm->lm < 1 || prm->mm < 1) { set_err(errm, errm_len, "beom_create: bad sizes"); return -3; }
-    if (prm->rgld > 0.5 && (prm->variant == 1 || prm->slab_mm > 0 || prm->ocrp < 0.5)) {
-        // (private_mod3d.f95 has no lid; the Poisson operators are only initialised with ocrp = 1, :505-563; the pressure sweep
-        // couples the whole frame, so no bands)
-        set_err(errm, errm_len, "beom_create: rgld = 1 (rigid lid, private_mod.f95:1705-1838) needs variant 0, ocrp = 1 and a whole frame (no bands)");
-        return -5;
-    }
-    if (prm->variant == 1 && prm->nlay < 3) { set_err(errm, errm_len, "beom_create: variant 1 (private_mod3d.f95) needs nlay >= 3"); return -7; }
-    if (!neig || !subc || !mk_u || !mk_v || !mk_n || !mkpe || !mkpi || !fcor || !h_th || !nudg || !fnud) { set_err(errm, errm_len, "beom_create: null static array"); return -1; }
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0 || device < 0 || device >= ndev) { set_err(errm, errm_len, "beom_create: no usable HIP device (%d visible, asked for %d); there is no CPU fallback", ndev, device); return -8; }
-    HIP_TRY(hipSetDevice(device));
+    const beom_dense::Grid g{neig, subc, mk_u, mk_v, mk_n, mkpe, mkpi};
+    const beom_statics st{fcor, h_th, h_to, nudg, fnud, hdot, tide, bodf, taus};
+    int rc = check_create_args(prm, out, device, g, st, errm, errm_len);
+    if (rc) return rc;
     beom_engine *E = new beom_engine();
     E->P = *prm;
     E->device = device;
-    // from here on every failure releases the handle (its stream and device arrays) on the way out
-#define HIP_TRY_E(expr)                                                                     \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            set_err(errm, errm_len, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                    __FILE__, __LINE__);                                                    \
-            beom_destroy(E);                                                                \
-            return -100 - (int)e_;                                                          \
-        }                                                                                   \
-    } while (0)
-    HIP_TRY_E(hipStreamCreateWithFlags(&E->own_stream, hipStreamNonBlocking));
-    E->stream = E->own_stream;
-    DevView &d = E->d;
-    const size_t n1h = (size_t)prm->ndeg + 1, nl = (size_t)prm->nlay;      // n1h: cells per layer in the caller's arrays
-    d.ndeg = prm->ndeg; d.nlay = prm->nlay; d.lm = prm->lm; d.mm = prm->mm; d.nsal = prm->nsal;
-    d.variant = prm->variant; d.n1 = (long long)n1h;
-    d.L = prm->lm + 1; d.M = prm->mm + 1;
-    d.dl = prm->dl; d.dt = prm->dt; d.grav = prm->grav; d.rho0 = prm->rho0; d.beta = prm->beta;
-    d.epsi = prm->epsi; d.gamm = prm->gamm; d.del1 = prm->del1; d.del2 = prm->del2; d.hmin = prm->hmin;
-    d.hsal = prm->hsal; d.bvis = prm->bvis; d.dvis = prm->dvis; d.bdrg = prm->bdrg; d.tdrg = prm->tdrg;
-    d.qdrg = prm->qdrg; d.hsbl = prm->hsbl; d.hbbl = prm->hbbl; d.uadv = prm->uadv; d.ocrp = prm->ocrp;
-    d.rgld = prm->rgld; d.invf = prm->invf; d.w_ti = prm->w_ti; d.svis = prm->svis;
-    d.mm_glob = prm->slab_mm > 0 ? prm->slab_mm : prm->mm;
-    for (int i = 0; i < BEOM_MAX_LAYERS; ++i) d.rhon[i] = prm->rhon[i];
-    d.i_dl = 1.0 / prm->dl;                      // private_mod.f95:1428,1511,1599,2321
-    d.i_gr = 1.0 / prm->grav;                    // :2322
-    d.i_ns = 1.0 / (double)(prm->nsal - 1);      // :2328
-    d.i_r0 = 1.0 / prm->rho0;                    // :1429
-    d.i_r1 = 1.0 / prm->rhon[0];                 // :1430
-    for (int i = 0; i < prm->nlay; ++i) d.i_rn[i] = 1.0 / prm->rhon[i];   // :2329
-    // periodicity is encoded only in neig (private_mod.f95:614-685); recover it for the dense form
-    d.xper = 0; d.yper = 0;
-    d.nstrip = 1; d.jlo0 = 1; d.jhi0 = d.M; d.jlo1 = 1; d.jhi1 = 0;
-    d.slab = prm->slab_mm > 0 ? 1 : 0;
-    d.joff = d.slab ? prm->slab_row0 : 0;
-    d.Mg = d.slab ? prm->slab_mm + 1 : d.M;
-    if (d.slab && (d.joff < 0 || d.joff + d.M > d.Mg)) { set_err(errm, errm_len, "beom_create: slab rows outside the global frame"); beom_destroy(E); return -3; }
-    E->dense = false;
-    if (prm->dense_hint && (long long)prm->ndeg == (long long)d.L * d.M) {
-        for (int xp = 0; xp < 2 && !E->dense; ++xp)
-            for (int yp = 0; yp < 2 && !E->dense; ++yp) {
-                if (d.slab && yp) continue;      // a slab of a y-periodic frame gets its wrap from the exchange, not from neig
-                if (beom_dense::verify(d.L, d.M, d.joff, d.Mg, d.slab, xp, yp, prm->ndeg, neig, subc, mk_u, mk_v, mk_n, mkpe, mkpi)) {
-                    E->dense = true; d.xper = xp; d.yper = yp;
-                }
-            }
+    if ((rc = setup(E, g, st, errm, errm_len))) {      // every failure releases the handle (its stream and device arrays)
+        beom_destroy(E);
+        return rc;
     }
-    // Frames with land: the same rectangle, every packed cell in the slot of its (i, j) (subc), if the
-    // caller's connectivity is what offsets on the rectangle give — wraps as for a dense frame, and wherever the table says
-    // 0 the offset lands outside the rectangle or on a slot that is no packed cell (it then holds the sentinel's values).
-    std::vector<int32_t> slot_of, pk_of;
-    std::vector<unsigned char> reg4;
-    if (!E->dense && prm->dense_hint && prm->svis == 0.0 && getenv("BEOM_NO_EMBED") == nullptr &&      // (a band of a frame with land too: d.slab)
-        (long long)d.L * d.M < 2000000000ll && (long long)prm->ndeg * 10 >= (long long)d.L * d.M * 3) {     // (at least 30 % of the rectangle in use)
-        const int L = d.L, M = d.M, P = (L + 15) / 16 * 16;
-        slot_of.assign(n1h, 0); pk_of.assign((size_t)P * M + 1, 0);
-        bool ok = true;
-        for (size_t p = 1; p < n1h && ok; ++p) {
-            const int i = subc[p], j = subc[p + n1h];
-            if (i < 1 || i > L || j < 1 || j > M) { ok = false; break; }
-            const int32_t sl = (int32_t)(i + (long long)(j - 1) * P);
-            if (pk_of[sl]) ok = false;
-            slot_of[p] = sl; pk_of[sl] = (int32_t)p;
-        }
-        for (int xp = 0; xp < 2 && ok && !E->embedded; ++xp)
-            for (int yp = 0; yp < 2 && !E->embedded; ++yp) {
-                if (d.slab && yp) continue;
-                const beom_dense::HostNb nb{L, M, xp, yp};
-                bool match = true;
-                for (size_t p = 1; p < n1h && match; ++p) {
-                    const int i = subc[p], j = subc[p + n1h];
-                    for (int k = 0; k < 8 && match; ++k) {
-                        const int q = nb.at(i + beom_dense::kDi[k], j + beom_dense::kDj[k]);      // packed-pitch index on the L x M rectangle, or 0
-                        const int32_t want = neig[k + 8 * p];
-                        const int32_t got = q ? pk_of[(size_t)((q - 1) % L + 1) + (size_t)((q - 1) / L) * P] : 0;
-                        match = want == got;
-                    }
-                }
-                if (match) { E->embedded = true; d.xper = xp; d.yper = yp; }
-            }
-        if (E->embedded) {
-            // 64 x 4 tiles whose every cell, and every cell within 3 of it, is wet interior with unit masks
-            const int ntx = (L + 63) / 64, nty = (M + 3) / 4;
-            std::vector<unsigned char> good((size_t)(L + 2) * (M + 2), 0);       // (i, j) in 0..L+1 x 0..M+1
-            for (size_t p = 1; p < n1h; ++p)
-                if (mk_n[p] == 1.0 && mk_u[p] == 1.0 && mk_v[p] == 1.0 && mkpe[p] == 1.0 && mkpi[p] == 1.0)
-                    good[(size_t)subc[p] + (size_t)subc[p + n1h] * (L + 2)] = 1;
-            // 2-D prefix sums of "not good" -> any bad cell in a window
-            std::vector<int32_t> bad((size_t)(L + 3) * (M + 3), 0);
-            for (int j = 0; j <= M + 1; ++j)
-                for (int i = 0; i <= L + 1; ++i)
-                    bad[(size_t)(i + 1) + (size_t)(j + 1) * (L + 3)] = (good[(size_t)i + (size_t)j * (L + 2)] ? 0 : 1)
-                        + bad[(size_t)i + (size_t)(j + 1) * (L + 3)] + bad[(size_t)(i + 1) + (size_t)j * (L + 3)] - bad[(size_t)i + (size_t)j * (L + 3)];
-            auto any_bad = [&](int i0, int i1, int j0, int j1) {          // inclusive window, clipped to 0..L+1 x 0..M+1 (the margin is bad)
-                if (i0 < 0 || j0 < 0 || i1 > L + 1 || j1 > M + 1) return true;
-                return bad[(size_t)(i1 + 1) + (size_t)(j1 + 1) * (L + 3)] - bad[(size_t)i0 + (size_t)(j1 + 1) * (L + 3)]
-                       - bad[(size_t)(i1 + 1) + (size_t)j0 * (L + 3)] + bad[(size_t)i0 + (size_t)j0 * (L + 3)] != 0;
-            };
-            reg4.assign((size_t)ntx * nty, 0);
-            for (int ty = 0; ty < nty; ++ty)
-                for (int tx = 0; tx < ntx; ++tx) {
-                    const int x0 = tx * 64 + 1, y0 = ty * 4 + 1;
-                    reg4[(size_t)ty * ntx + tx] = any_bad(x0 - 3, x0 + 63 + 3, y0 - 3, y0 + 3 + 3) ? 0 : 1;
-                }
-            d.reg_nx = ntx;
-            E->dense = true;              // the dense kernels, with masks from arrays where a tile is not regular
-        }
-    }
-    d.embedded = E->embedded ? 1 : 0;
-    E->lid = prm->rgld > 0.5;
-    if (E->lid) {
-        E->subc_host.assign(subc, subc + 2 * n1h);
-        E->neig_host.assign(neig, neig + 8 * n1h);
-    }
-    if (E->lid || (E->embedded && prm->flag_nudging && prm->mcbc < 0.5)) {      // packed index -> device index, for tables uploaded later
-        E->dev_index.assign(n1h, 0);
-        const int P = (d.L + 15) / 16 * 16;
-        for (size_t p = 1; p < n1h; ++p)
-            E->dev_index[p] = E->embedded ? slot_of[p] : E->dense ? (int32_t)((p - 1) % d.L + 1 + ((p - 1) / d.L) * (size_t)P) : (int32_t)p;
-    }
-    // device layout: padded row pitch for dense frames (DevView::P), the caller's packed layout otherwise
-    d.P = 0; d.ncell = prm->ndeg;
-    if (E->dense) {
-        d.P = (getenv("BEOM_NO_PITCH") && !E->embedded) ? d.L : (d.L + 15) / 16 * 16;      // (BEOM_NO_PITCH: the packed pitch, for A/B measurements)
-        d.ncell = (long long)d.P * d.M;
-        d.n1 = (d.ncell + 1 + 15) / 16 * 16;
-    }
-    const size_t n1 = (size_t)d.n1;                   // cells per layer on the device
-    int rc = 0;
-    E->stage_bytes = n1h * 32;                        // the widest slice: neig (8 x int32), a history (3 doubles)
-    HIP_TRY_E(hipMalloc(&E->stage, E->stage_bytes));
-    if (E->embedded) {
-        int32_t *q = nullptr;
-        if ((rc = dev_alloc(E, &q, slot_of.size(), errm, errm_len, false))) { beom_destroy(E); return rc; }
-        HIP_TRY_E(hipMemcpyAsync(q, slot_of.data(), slot_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
-        E->slot_of_dev = q;
-        if ((rc = dev_alloc(E, &q, (size_t)d.n1, errm, errm_len, true))) { beom_destroy(E); return rc; }
-        HIP_TRY_E(hipMemcpyAsync(q, pk_of.data(), pk_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
-        d.pk_of = q;
-        unsigned char *r = nullptr;
-        if ((rc = dev_alloc(E, &r, reg4.size(), errm, errm_len, false))) { beom_destroy(E); return rc; }
-        HIP_TRY_E(hipMemcpyAsync(r, reg4.data(), reg4.size(), hipMemcpyHostToDevice, E->stream));
-        d.reg4 = r;
-        HIP_TRY_E(hipStreamSynchronize(E->stream));
-    }
-#define UP(name, src, outer, inner) if ((rc = dev_upload(E, &d.name, src, (size_t)(outer), (inner), errm, errm_len))) { beom_destroy(E); return rc; }
-    if ((rc = dev_upload<int32_t, true>(E, &d.neig, neig, 1, 8, errm, errm_len))) { beom_destroy(E); return rc; }
-    UP(subc, subc, 2, 1)
-    UP(mk_u, mk_u, 1, 1) UP(mk_v, mk_v, 1, 1) UP(mk_n, mk_n, 1, 1) UP(mkpe, mkpe, 1, 1) UP(mkpi, mkpi, 1, 1)
-    UP(fcor, fcor, 1, 1) UP(h_th, h_th, 1, 1) UP(h_to, h_to, 1, 1)
-    UP(nudg, nudg, 3, 1) UP(fnud, fnud, 3 * nl, 1) UP(hdot, hdot, nl, 1)
-    UP(tide, tide, 3, 2) UP(taus, taus, 2, 1)
-    {   // the wind stress as tt3d holds it: at real cells only (distribute_stress writes cells 1..ndeg, :1945-1966; index 0 and
-        // every device slot that is no cell stay +0)
-        std::vector<double> tc(2 * n1h, 0.0);
-        if (taus) { std::memcpy(tc.data(), taus, 2 * n1h * sizeof(double)); tc[0] = 0.0; tc[n1h] = 0.0; }
-        UP(taus_cells, tc.data(), 2, 1)
-    }
-#undef UP
-    {   // bodf(nlay, 2): no cell dimension
-        double *q = nullptr;
-        if ((rc = dev_alloc(E, &q, 2 * nl, errm, errm_len, true))) { beom_destroy(E); return rc; }
-        if (bodf) HIP_TRY_E(hipMemcpyAsync(q, bodf, 2 * nl * sizeof(double), hipMemcpyHostToDevice, E->stream));
-        d.bodf = q;
-    }
-    for (size_t i = 0; i < n1h; ++i) { if (mk_u[i] > 0.5) E->any_u = 1; if (mk_v[i] > 0.5) E->any_v = 1; }
-    d.woff = nullptr;
-    if (!E->dense && getenv("BEOM_NO_WAVE_TABLE") == nullptr) {      // table path: which runs of 64 cells are uniform interior?
-        const long long nw = ((long long)prm->ndeg + 63) / 64;
-        std::vector<int32_t> woff((size_t)(2 * nw), 0);
-        long long nuni = 0;
-        for (long long w = 0; w < nw; ++w) {
-            const long long p0 = 64 * w + 1;
-            if (p0 + 63 > prm->ndeg) break;
-            const int32_t *r0 = neig + 8 * p0;
-            const int dN = r0[2] - (int)p0, dS = (int)p0 - r0[6];
-            bool ok = dN > 0 && dS > 0 && r0[2] != 0 && r0[6] != 0;
-            for (long long p = p0; ok && p < p0 + 64; ++p) {
-                const int32_t *r = neig + 8 * p;
-                ok = r[0] == p + 1 && r[4] == p - 1 && r[2] == p + dN && r[6] == p - dS &&
-                     r[1] == p + dN + 1 && r[3] == p + dN - 1 && r[5] == p - dS - 1 && r[7] == p - dS + 1 &&
-                     r[3] >= 1 && r[5] >= 1 && r[1] <= prm->ndeg &&
-                     mk_u[p] == 1.0 && mk_v[p] == 1.0 && mk_n[p] == 1.0 && mkpe[p] == 1.0 && mkpi[p] == 1.0;
-                for (int q = 0; ok && q < 8; ++q) ok = mk_n[r[q]] == 1.0;
-            }
-            if (ok) { woff[2 * w] = dN; woff[2 * w + 1] = dS; ++nuni; }
-        }
-        E->uniform_waves = nuni; E->total_waves = nw;
-        if (nuni > 0) {      // (table path: packed layout, no repacking)
-            int32_t *q = nullptr;
-            if ((rc = dev_alloc(E, &q, (size_t)(2 * nw), errm, errm_len, false))) { beom_destroy(E); return rc; }
-            HIP_TRY_E(hipMemcpyAsync(q, woff.data(), (size_t)(2 * nw) * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
-            HIP_TRY_E(hipStreamSynchronize(E->stream));
-            d.woff = q;
-        }
-    }
-    d.has_hdot = any_nonzero(hdot, nl * n1h);
-    d.has_tide = any_nonzero(tide, 6 * n1h);
-    d.has_bodf = any_nonzero(bodf, 2 * nl);
-    d.has_nudg = any_nonzero(nudg, 3 * n1h);
-    d.ngt = nullptr; d.ngt_nx = 0;
-    if (E->dense && d.has_nudg && getenv("BEOM_NO_NUDG_TILES") == nullptr) {
-        // which 64 x 4 tiles of the rectangle hold a non-zero relaxation rate at all (sponges are a few rows or columns)
-        const int ntx = (d.L + 63) / 64, nty = (d.M + 3) / 4;
-        std::vector<unsigned char> ngt((size_t)ntx * nty, 0);
-        for (size_t pk = 1; pk < n1h; ++pk) {
-            // (i, j) of the packed cell on the rectangle — local rows: subc(:, 2) of a band holds the global row
-            int ci, cj;
-            if (E->embedded) { const long long sl = slot_of[pk]; ci = (int)((sl - 1) % d.P) + 1; cj = (int)((sl - 1) / d.P) + 1; }
-            else { ci = (int)((pk - 1) % (size_t)d.L) + 1; cj = (int)((pk - 1) / (size_t)d.L) + 1; }
-            if (ci < 1 || ci > d.L || cj < 1 || cj > d.M) continue;
-            unsigned char &t = ngt[(size_t)((cj - 1) >> 2) * ntx + ((ci - 1) >> 6)];
-            for (int iv = 0; iv < 3; ++iv) if (nudg[pk + (size_t)iv * n1h] != 0.0) t |= (unsigned char)(1u << iv);
-        }
-        size_t flagged = 0;
-        for (unsigned char t : ngt) flagged += t != 0;
-        // (the look-up is one more dependent load in front of the rate: it pays where most tiles are free of nudging — carrier
-        //  beach 8192x1024x8 -2 % per step; a frame nudged over a third of its tiles goes without, wind case +1.5 % with it)
-        if (3 * flagged <= ngt.size()) {
-            unsigned char *r = nullptr;
-            if ((rc = dev_alloc(E, &r, ngt.size(), errm, errm_len, false))) { beom_destroy(E); return rc; }
-            HIP_TRY_E(hipMemcpyAsync(r, ngt.data(), ngt.size(), hipMemcpyHostToDevice, E->stream));
-            HIP_TRY_E(hipStreamSynchronize(E->stream));
-            d.ngt = r; d.ngt_nx = ntx;
-        }
-    }
-    d.has_hto = any_nonzero(h_to, n1h);
-    d.keep_diag = 0; d.lean_d2h = 0; E->lean_d2h = true;
-    E->fuse = getenv("BEOM_NO_FUSE") == nullptr;
-    E->fuse_uv = getenv("BEOM_NO_FUSE") == nullptr && getenv("BEOM_NO_FUSE_UV") == nullptr;
-    // frames of few rounds of workgroups: the 64 x 4 tile geometry, one row per thread (a workgroup's lifetime is what the
-    // step time is made of there).  Same box, us per step, 64 x 8 -> 64 x 4: stommel 128^2 31.2 -> 24.0, soliton 2048x256
-    // 53.5 -> 43.6, 1024x128x4 74.8 -> 56.3, sill 4096x512x4 614 -> 596; jet 2048^2 x 2 535 -> 557, 4096^2 x 4 and larger: slower
-    E->tile4 = E->dense && (long long)((d.L + 63) / 64) * ((d.M + 7) / 8) <= 5000;
-    if (getenv("BEOM_TILE4")) E->tile4 = E->dense && atoi(getenv("BEOM_TILE4")) != 0;      // (A/B switch)
-    if (E->lid) E->fuse = E->fuse_uv = false;      // the lid's flux rebuild reads the stored d2hx, d2hy of the last layer
-    d.edge_global = getenv("BEOM_EDGE_GLOBAL") != nullptr;
-    E->wind = false;
-    if (taus) for (size_t i = 0; i < 2 * n1h; ++i) if (std::fabs(taus[i]) > 1.e-7) { E->wind = true; break; }   // :1945
-    E->bot = prm->bdrg > 1.e-7;                                                                                  // :1969
-    E->top = prm->tdrg > 1.e-7;                                                                                  // :1991
-    d.has_wind = E->wind; d.has_bot = E->bot; d.has_top = E->top;
-    d.has_stress = E->wind || E->bot || E->top;
-    d.stress_fold = 0;
-    d.rho_top = prm->rhon[0]; d.rho_bot = prm->rhon[nl - 1];
-    {
-        bool neg0 = false;                         // a body force of exactly -0 would make the sign of a skipped +-0 visible
-        if (bodf) for (size_t i = 0; i < 2 * nl; ++i) if (bodf[i] == 0.0 && std::signbit(bodf[i])) neg0 = true;
-        E->fold_static_ok = E->dense && prm->ocrp < 0.5 && !E->lid && d.has_stress && !neg0 && getenv("BEOM_NO_FOLD_STRESS") == nullptr;
-    }
-#define AL(name, n) if ((rc = dev_alloc(E, &d.name, (size_t)(n), errm, errm_len))) { beom_destroy(E); return rc; }
-    AL(hlay, nl * n1) AL(u, nl * n1) AL(v, nl * n1) AL(h_u, nl * n1) AL(h_v, nl * n1)
-    AL(rs[0], nl * n1) AL(rs[1], nl * n1)
-    AL(dmx[0], nl * n1) AL(dmx[1], nl * n1) AL(dmx[2], nl * n1)
-    AL(dmy[0], nl * n1) AL(dmy[1], nl * n1) AL(dmy[2], nl * n1)
-    if (E->dense) {            // partners for the fused U+V sweep
-        AL(dmx[3], nl * n1) AL(dmy[3], nl * n1)
-        AL(u_alt, nl * n1) AL(v_alt, nl * n1) AL(hu_alt, nl * n1) AL(hv_alt, nl * n1)
-    }
-    AL(v_cc, nl * n1) AL(v_ll, nl * n1)
-    AL(tt3d, 2 * nl * n1) AL(tb3d, 2 * nl * n1) AL(tu3d, 2 * nl * n1)
-    AL(pcd, nl * n1) AL(qlr, nl * n1)
-    AL(mont, nl * n1) AL(rvor, nl * n1) AL(pvor, nl * n1) AL(dive, nl * n1) AL(d2hx, nl * n1) AL(d2hy, nl * n1)
-    if (prm->svis > 0.0) { AL(delu, nl * n1) AL(delv, nl * n1) AL(uu4, nl * n1) AL(vv4, nl * n1) }
-    if (E->lid) { AL(pi_s, n1) AL(pi_rhs, n1) AL(pi_prev, n1) }
-#undef AL
-    // initialize_variables: v_cc = v_ll = bvis everywhere, sentinel included (:276-277)
-    if (prm->bvis != 0.0) {
-        std::vector<double> b(nl * n1, prm->bvis);      // (padding slots too: never read)
-        HIP_TRY_E(hipMemcpyAsync(d.v_cc, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, E->stream));
-        HIP_TRY_E(hipMemcpyAsync(d.v_ll, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, E->stream));
-        HIP_TRY_E(hipStreamSynchronize(E->stream));
-    }
-    const unsigned gx = (unsigned)((d.ncell + BEOM_BLOCK - 1) / BEOM_BLOCK);          // launches over all cell slots
-    const unsigned gx0 = (unsigned)((d.ncell + 1 + BEOM_BLOCK - 1) / BEOM_BLOCK);
-    E->grid_cells_layers_flat = dim3(gx, (unsigned)prm->nlay, 1);
-    E->grid_cells0 = dim3(gx0, 1, 1);
-    HIP_TRY_E(hipStreamSynchronize(E->stream));
-#undef HIP_TRY_E
     *out = E;
     return 0;
 }
@@ -649,93 +554,22 @@ int beom_set_rigid_lid(beom_handle E, const double *Ow, const double *Os, const 
     int rc;
     if (!E->lid_ready) {
         if (!Ow || !Os || !Osum_) { set_err(errm, errm_len, "beom_set_rigid_lid: the operators Ow, Os, Osum_ are needed on the first call"); return -1; }
+        if ((long long)d.n1 >= (1ll << 29)) { set_err(errm, errm_len, "beom_set_rigid_lid: frame too large for the lid's tables"); return -3; }
+        const beom_dense::LidPlan lp = beom_dense::plan_lid(d.ndeg, d.lm, d.mm_glob, d.n1, E->subc_host, E->neig_host, E->dev_index);
         if ((rc = dev_upload(E, &d.Ow, Ow, 1, 1, errm, errm_len))) return rc;
         if ((rc = dev_upload(E, &d.Os, Os, 1, 1, errm, errm_len))) return rc;
         if ((rc = dev_upload(E, &d.Osum_, Osum_, 1, 1, errm, errm_len))) return rc;
-        // Levels of the serial sweep's dependency graph: a cell reads the NEW pressure of the neighbours before it in packed
-        // order (it comes after them) and the OLD pressure of those after it (they come after it).  On a plain frame the
-        // levels are the anti-diagonals i + j; the wrapped neighbours of an orphan column / row cell bend them.
-        const size_t n1h = (size_t)d.ndeg + 1;
-        std::vector<int32_t> level(n1h, 0), after(n1h, 0);
-        int nlevel = 1;
-        for (size_t p = 1; p < n1h; ++p) {
-            const int i = E->subc_host[p], j = E->subc_host[p + n1h];
-            const int32_t *nb = &E->neig_host[8 * p];
-            const int32_t reads[4] = {i < d.lm ? nb[0] : 0, j < d.mm_glob ? nb[2] : 0, i > 1 ? nb[4] : 0, j > 1 ? nb[6] : 0};
-            int32_t lv = after[p];
-            for (int32_t qn : reads)
-                if (qn > 0 && (size_t)qn < p) lv = std::max(lv, level[(size_t)qn] + 1);
-            level[p] = lv;
-            for (int32_t qn : reads)
-                if (qn > 0 && (size_t)qn > p) after[(size_t)qn] = std::max(after[(size_t)qn], lv + 1);
-            nlevel = std::max(nlevel, lv + 1);
-        }
-        // time between two sweeps of the pipeline: sweep s + 1 may touch a cell once every neighbour AFTER it in packed order has
-        // been updated by sweep s — 1 + the largest level difference along such an edge (2 on a plain frame; about lm where
-        // a periodic seam makes a cell read the far end of its row)
-        int dstep = 2;
-        for (size_t p = 1; p < n1h; ++p) {
-            const int i = E->subc_host[p], j = E->subc_host[p + n1h];
-            const int32_t *nb = &E->neig_host[8 * p];
-            const int32_t reads[4] = {i < d.lm ? nb[0] : 0, j < d.mm_glob ? nb[2] : 0, i > 1 ? nb[4] : 0, j > 1 ? nb[6] : 0};
-            for (int32_t qn : reads)
-                if (qn > 0 && (size_t)qn > p) dstep = std::max(dstep, level[(size_t)qn] - level[p] + 1);
-        }
-        E->lid_dstep = dstep;
-        const int ndiag = nlevel;
-        std::vector<int32_t> start((size_t)ndiag + 1, 0), order(n1h > 1 ? n1h - 1 : 1, 0);
-        for (size_t p = 1; p < n1h; ++p) ++start[(size_t)level[p] + 1];
-        for (int k = 0; k < ndiag; ++k) start[(size_t)k + 1] += start[k];
-        std::vector<int32_t> fill(start.begin(), start.end() - 1);
-        for (size_t p = 1; p < n1h; ++p) order[(size_t)fill[(size_t)level[p]]++] = E->dev_index[p];
-        int32_t *q = nullptr;
-        if ((rc = dev_alloc(E, &q, order.size(), errm, errm_len, false))) return rc;
-        HIP_TRY(hipMemcpyAsync(q, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
-        d.sor_order = q;
-        if ((rc = dev_alloc(E, &q, start.size(), errm, errm_len, false))) return rc;
-        HIP_TRY(hipMemcpyAsync(q, start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
-        d.sor_dstart = q;
-        d.sor_ndiag = ndiag;
-        E->lid_maxwidth = 1;
-        for (int k = 0; k < ndiag; ++k) E->lid_maxwidth = std::max(E->lid_maxwidth, (int)(start[(size_t)k + 1] - start[k]));
+        if ((rc = upload_table(E, &d.sor_order, lp.order, lp.order.size(), false, errm, errm_len))) return rc;
+        if ((rc = upload_table(E, &d.sor_dstart, lp.start, lp.start.size(), false, errm, errm_len))) return rc;
+        d.sor_ndiag = (int)lp.start.size() - 1;
+        E->lid_dstep = lp.dstep;
+        E->lid_maxwidth = lp.maxwidth;
         // one copy of the pressure per sweep in flight: up to kLidBatch of them within ~6 GB
         E->lid_nring = (int)std::max<long long>(17, std::min<long long>(kLidBatch, (6ll << 30) / ((long long)d.n1 * 8))) + 1;
         if ((rc = dev_alloc(E, &E->lid_ring, (size_t)E->lid_nring * d.n1, errm, errm_len, true))) return rc;      // zeroed: index 0 and every slot that is no cell stay 0
         if ((rc = dev_alloc(E, &E->lid_maxd, (size_t)kLidBatch, errm, errm_len, true))) return rc;
-        // the terms of every cell's right-hand side in the order of the serial scatter loops (:1727-1752): the x loop over
-        // the packed cells, then the y loop; a cell with i > 1 (j > 1) subtracts its transport from itself and adds it to neig(5)
-        // (neig(7)); what goes to the sentinel is dropped
-        if ((long long)d.n1 >= (1ll << 29)) { set_err(errm, errm_len, "beom_set_rigid_lid: frame too large for the lid's tables"); return -3; }
-        std::vector<int32_t> cnt((size_t)d.n1 + 2, 0);
-        for (int pass = 0; pass < 2; ++pass) {                       // pass 0: count, pass 1: fill
-            std::vector<int32_t> at;
-            std::vector<int32_t> ent;
-            if (pass) {
-                for (size_t k = 1; k < cnt.size(); ++k) cnt[k] += cnt[k - 1];          // cnt[dev] = first entry of cell dev
-                at.assign(cnt.begin(), cnt.end());
-                ent.assign((size_t)cnt.back() + 1, 0);
-            }
-            for (int dir = 0; dir < 2; ++dir)
-                for (size_t qk = 1; qk < n1h; ++qk) {
-                    if (E->subc_host[qk + dir * n1h] <= 1) continue;
-                    const int32_t src = E->dev_index[qk], tgt = E->neig_host[8 * qk + (dir ? 6 : 4)];
-                    if (!pass) { ++cnt[(size_t)src + 1]; if (tgt > 0) ++cnt[(size_t)E->dev_index[(size_t)tgt] + 1]; }
-                    else {
-                        ent[(size_t)at[src]++] = 4 * src + 2 * dir;
-                        if (tgt > 0) ent[(size_t)at[E->dev_index[(size_t)tgt]]++] = 4 * src + 2 * dir + 1;
-                    }
-                }
-            if (pass) {
-                if ((rc = dev_alloc(E, &q, cnt.size(), errm, errm_len, false))) return rc;
-                HIP_TRY(hipMemcpyAsync(q, cnt.data(), cnt.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
-                d.lid_rhs_start = q;
-                if ((rc = dev_alloc(E, &q, ent.size(), errm, errm_len, false))) return rc;
-                HIP_TRY(hipMemcpyAsync(q, ent.data(), ent.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
-                d.lid_rhs_ent = q;
-                HIP_TRY(hipStreamSynchronize(E->stream));
-            }
-        }
-        HIP_TRY(hipStreamSynchronize(E->stream));       // (order, start are host temporaries)
+        if ((rc = upload_table(E, &d.lid_rhs_start, lp.rhs_start, lp.rhs_start.size(), false, errm, errm_len))) return rc;
+        if ((rc = upload_table(E, &d.lid_rhs_ent, lp.rhs_ent, lp.rhs_ent.size(), false, errm, errm_len))) return rc;
         E->lid_ready = true;
     }
     if (pi_s && (rc = slice_to_device<double>(E, d.pi_s, pi_s, 1, 1, 0, errm, errm_len))) return rc;
@@ -993,45 +827,53 @@ static bool stress_folds(const beom_engine *E, const StepScalars &s) {
            (E->wind || !E->up_tt) && (E->bot || !E->up_tb) && (E->top || !E->up_tu);
 }
 
-static void one_step(beom_engine *E, int tstp, const StepScalars &s) {
+// the start of a step, and of each part of a split step: its timer if the step is sampled, whether its stress folds
+static StepTimer *begin_step(beom_engine *E, int tstp, const StepScalars &s) {
     StepTimer *T = (E->timer && tstp % E->timer->stride == 0) ? E->timer : nullptr;
     if (T) { T->st = E->stream; T->step(tstp); }
     E->d.stress_fold = stress_folds(E, s) ? 1 : 0;
     E->last_folded = E->d.stress_fold != 0;
+    return T;
+}
+// launches f, bracketed as kernel class c when the step is sampled
+template <class F>
+static void timed(StepTimer *T, int c, F &&f) {
+    if (T) T->begin(c);
+    f();
+    if (T) T->end();
+}
+
+// The step up to the momentum sweeps: stress, the rebuild of steps 1-3, update_h, Montgomery + Leith.  Returns prod: the
+// Montgomery sweep formed the viscous products for the fused u+v sweep (s.fused_uv) that follows.
+static bool step_front(beom_engine *E, const StepScalars &s, StepTimer *T) {
     if (s.stress && !E->d.stress_fold) launch_stress(E);
     if (E->lid) launch_lid_fluxes(E, s.first3);
     else if (s.first3) launch_rebuild(E);                          // :2166-2177
-    if (T) T->begin(0);
-    launch_h(E, s.gene, s.ramp, s.ctim);                           // :2181,2259
-    if (E->lid) launch_lid_h_epilogue(E);                          // :1648-1700
+    timed(T, 0, [&] {
+        launch_h(E, s.gene, s.ramp, s.ctim);                       // :2181,2259
+        if (E->lid) launch_lid_h_epilogue(E);                      // :1648-1700
+    });
     const bool leith = E->P.dvis > 1.e-3 && s.upst;
+    bool prod = false;
+    timed(T, s.fused ? 5 : 1, [&] {
+        prod = s.fused && launch_mont_visc(E, s.fused_uv, leith, leith && s.n_3d > 1);     // :2187-2188, 2266-2269 in one sweep
+        if (!prod) launch_mont(E, 0);
+    });
+    if (!prod && (s.first3 || leith || E->P.svis > 0.0)) timed(T, 2, [&] { launch_visc(E, 0); });     // :2188,2268
+    return prod;
+}
+
+static void one_step(beom_engine *E, int tstp, const StepScalars &s) {
+    StepTimer *T = begin_step(E, tstp, s);
+    const bool prod = step_front(E, s, T);
     const bool u_first = tstp % 2 == 0;                            // :2193-2199,2276-2282
-    if (T) { T->end(); T->begin(s.fused ? 5 : 1); }
-    const bool prod = s.fused && launch_mont_visc(E, s.fused_uv, leith, leith && s.n_3d > 1);              // :2187-2188, 2266-2269 in one sweep
-    if (!prod) launch_mont(E, 0);
-    if (T) T->end();
-    if (!prod && (s.first3 || (E->P.dvis > 1.e-3 && s.upst) || E->P.svis > 0.0)) {     // :2188,2268
-        if (T) T->begin(2);
-        launch_visc(E, 0);
-        if (T) T->end();
-    }
-    if (s.fused_uv) {
-        if (T) T->begin(6);
-        launch_uv_fused(E, u_first, prod, s.gene, s.ramp, s.ctim);
-        if (T) T->end();
-    } else if (u_first) {
-        if (T) T->begin(3);
-        launch_uv<true>(E, 0, s.gene, s.ramp, s.ctim, prod);
-        if (T) { T->end(); T->begin(4); }
-        launch_uv<false>(E, 0, s.gene, s.ramp, s.ctim, prod);
-        if (T) T->end();
-    } else {
-        if (T) T->begin(4);
-        launch_uv<false>(E, 0, s.gene, s.ramp, s.ctim, prod);
-        if (T) { T->end(); T->begin(3); }
-        launch_uv<true>(E, 0, s.gene, s.ramp, s.ctim, prod);
-        if (T) T->end();
-    }
+    if (s.fused_uv) timed(T, 6, [&] { launch_uv_fused(E, u_first, prod, s.gene, s.ramp, s.ctim); });
+    else
+        for (const bool x : {u_first, !u_first})
+            timed(T, x ? 3 : 4, [&] {
+                if (x) launch_uv<true>(E, 0, s.gene, s.ramp, s.ctim, prod);
+                else launch_uv<false>(E, 0, s.gene, s.ramp, s.ctim, prod);
+            });
     if (E->obc) {                                                  // :2201-2204, 2285-2288
         const dim3 g((unsigned)((E->d.nseg + BEOM_BLOCK - 1) / BEOM_BLOCK), (unsigned)E->d.nlay, 1);
         hipLaunchKernelGGL(k_no_gradient_obc, g, dim3(BEOM_BLOCK), 0, E->stream, E->d, 0);
@@ -1139,38 +981,18 @@ int beom_step_phase(beom_handle E, int tstp, double tres, double dtd8, double dt
     }
     const int M = d.M;
     const bool u_first = tstp % 2 == 0;
-    StepTimer *T = (E->timer && tstp % E->timer->stride == 0) ? E->timer : nullptr;
-    if (T) { T->st = E->stream; T->step(tstp); }
-    E->d.stress_fold = stress_folds(E, s) ? 1 : 0;
-    E->last_folded = E->d.stress_fold != 0;
-    if (phase == 1) {                                                  // one_step up to the momentum sweeps
-        if (s.stress && !E->d.stress_fold) launch_stress(E);
-        if (s.first3) launch_rebuild(E);                               // :2166-2177
-        if (T) T->begin(0);
-        launch_h(E, s.gene, s.ramp, s.ctim);                           // :2181,2259
-        const bool leith = E->P.dvis > 1.e-3 && s.upst;
-        if (T) { T->end(); T->begin(s.fused ? 5 : 1); }
-        E->split_prod = s.fused && launch_mont_visc(E, true, leith, leith && s.n_3d > 1);
-        if (!E->split_prod) launch_mont(E, 0);
-        if (T) T->end();
-        if (!E->split_prod && (s.first3 || (E->P.dvis > 1.e-3 && s.upst) || E->P.svis > 0.0)) {     // :2188,2268
-            if (T) T->begin(2);
-            launch_visc(E, 0);
-            if (T) T->end();
-        }
+    StepTimer *T = begin_step(E, tstp, s);
+    if (phase == 1) {
+        E->split_prod = step_front(E, s, T);      // (s.fused_uv holds: parts 2 and 3 are the fused u+v sweep it prepares)
     } else if (phase == 2) {
         // a side without a neighbour has no strip (its rows belong to part 3)
         if (south && north) set_rows(d, 2, 1, kEdgeRows, M - kEdgeRows + 1, M);
         else if (south) set_rows(d, 1, 1, kEdgeRows);
         else set_rows(d, 1, M - kEdgeRows + 1, M);
-        if (T) T->begin(6);
-        launch_uv_fused(E, u_first, E->split_prod, s.gene, s.ramp, s.ctim, false);
-        if (T) T->end();
+        timed(T, 6, [&] { launch_uv_fused(E, u_first, E->split_prod, s.gene, s.ramp, s.ctim, false); });
     } else {
         set_rows(d, 1, south ? kEdgeRows + 1 : 1, north ? M - kEdgeRows : M);
-        if (T) T->begin(6);
-        launch_uv_fused(E, u_first, E->split_prod, s.gene, s.ramp, s.ctim, true);
-        if (T) T->end();
+        timed(T, 6, [&] { launch_uv_fused(E, u_first, E->split_prod, s.gene, s.ramp, s.ctim, true); });
     }
     set_rows(d, 1, 1, M);
     d.stress_fold = 0;

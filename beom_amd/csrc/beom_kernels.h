@@ -981,9 +981,9 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
     }
 }
 
-// Every other workgroup — boundary tiles (wraps, sentinel, masks), and all tiles of the v_cc/v_ll
-// form (PROD = false) — reads global memory as the unfused sweeps do.
-template <int Q, bool FIRST_X, bool PROD, bool INT, bool SF>
+// The v_cc/v_ll form (PROD = false), interior (INT) and boundary tiles alike, reads global memory as the unfused
+// sweeps do.
+template <int Q, bool FIRST_X, bool INT, bool SF>
 __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, int ilay, double gene,
                                               double ramp, double ctim, double (*s_h)[TileGeom<Q>::LDX]) {
     using G = TileGeom<Q>;
@@ -1007,10 +1007,10 @@ __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, 
             const int cb = FIRST_X ? c[q].template nb<5>() : c[q].template nb<7>();
             const int ca = FIRST_X ? c[q].template nb<3>() : c[q].template nb<1>();
             const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
-            hnew = uv_first_eval<FIRST_X, PROD, true, INT, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
+            hnew = uv_first_eval<FIRST_X, false, true, INT, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
             if (!INT) {     // orphan column/row are wrap TARGETS: stage what a neighbour lookup returns
                 if ((d.xper && i == d.L) || (d.yper && !d.slab && j == d.M))
-                    hnew = uv_first_halo<FIRST_X, PROD, SF>(d, i, j, ilay, gene, ramp, ctim);
+                    hnew = uv_first_halo<FIRST_X, false, SF>(d, i, j, ilay, gene, ramp, ctim);
             }
         }
         s_h[r + ROFF][lx + COFF] = hnew;
@@ -1026,7 +1026,7 @@ __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, 
         if (rr >= 0) {
             const int a = (FIRST_X ? x0 : x0 - 1) + cc;
             const int b = (FIRST_X ? y0 - 1 : y0) + rr;
-            s_h[rr][cc] = uv_first_halo<FIRST_X, PROD, SF>(d, a, b, ilay, gene, ramp, ctim);
+            s_h[rr][cc] = uv_first_halo<FIRST_X, false, SF>(d, a, b, ilay, gene, ramp, ctim);
         }
     }
     __syncthreads();
@@ -1049,7 +1049,7 @@ __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, 
         const int cb = !FIRST_X ? c[q].template nb<5>() : c[q].template nb<7>();
         const int ca = !FIRST_X ? c[q].template nb<3>() : c[q].template nb<1>();
         const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
-        uv_core<!FIRST_X, PROD, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
+        uv_core<!FIRST_X, false, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
     }
 }
 
@@ -1211,17 +1211,18 @@ __device__ __forceinline__ void uv_fused_workgroup(const DevView &d, double gene
     const bool interior = x0 - 1 >= 2 && x0 + G::TX <= d.L - 2 && y0 - 1 >= 2 && y0 + G::TY <= d.M - 2
                           && y0 - 1 + d.joff >= 2 && y0 + G::TY + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, G::TY);
     if (interior && PROD) body_uv_fused_staged<Q, FIRST_X, ZV, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
-    else if (interior) body_uv_fused<Q, FIRST_X, PROD, true, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
-    else if (PROD && !d.edge_global) body_uv_fused_edge<Q, FIRST_X, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
-    else body_uv_fused<Q, FIRST_X, PROD, false, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
+    else if (interior) body_uv_fused<Q, FIRST_X, true, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
+    else if (PROD) body_uv_fused_edge<Q, FIRST_X, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
+    else body_uv_fused<Q, FIRST_X, false, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
 }
 template <int Q, bool FIRST_X, bool PROD, bool ZV = false>
 __global__ __launch_bounds__(TileGeom<Q>::BLOCK) void k_uv_fused(DevView d, double gene, double ramp, double ctim) {
     uv_fused_workgroup<Q, FIRST_X, PROD, ZV, false>(d, gene, ramp, ctim);
 }
 // ... with distribute_stress formed inside (SF): its own kernels, so that the unforced ones do not carry its registers.  Their
-// zero-viscosity form takes 129 VGPRs; capped for four waves per SIMD it is slower than left at three (wind-driven
-// 4096x2048x2, same box: u+v 730 vs 714 us)
+// 64 x 8 u-first zero-viscosity form takes 128 VGPRs and runs four waves per SIMD: wind-driven 4096x2048x2, same box, u+v
+// 737 -> 699 us against three waves at 129 VGPRs (that build still had a global-memory rim body; an older one capped for
+// four waves had measured slower, 730 vs 714 us)
 template <int Q, bool FIRST_X, bool PROD, bool ZV = false>
 __global__ __launch_bounds__(TileGeom<Q>::BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void k_uv_fused_sf(DevView d, double gene, double ramp, double ctim) {
     uv_fused_workgroup<Q, FIRST_X, PROD, ZV, true>(d, gene, ramp, ctim);

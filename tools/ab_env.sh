@@ -1,7 +1,7 @@
 #!/bin/bash
-# A/B of an environment switch of the engine (e.g. BEOM_NO_PITCH=1) on tools/bench_case.py cases, same box, alternating
+# A/B of an environment switch of the engine (e.g. BEOM_TILE4=1) on tools/bench_case.py cases, same box, alternating
 R=${GRAFT_REPO_ROOT:-$PWD}
-VAR=${1:-BEOM_NO_PITCH}
+VAR=${1:-BEOM_TILE4}
 for rep in 1 2; do
   for c in ${CASES:-sill jet soliton}; do
     for which in off on; do

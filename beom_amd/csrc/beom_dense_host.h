@@ -179,7 +179,7 @@ inline Layout plan_layout(const beom_params &prm, int L, int M, int joff, int Mg
                     lay.dense = true; lay.xper = xp; lay.yper = yp;
                 }
             }
-    if (!lay.dense && prm.dense_hint && prm.svis == 0.0 &&      // (a band of a frame with land too: slab)
+    if (!lay.dense && prm.dense_hint &&      // (a band of a frame with land too: slab)
         (long long)L * M < 2000000000ll && (long long)prm.ndeg * 10 >= (long long)L * M * 3 &&     // (at least 30 % of the rectangle in use)
         embed(lay, L, M, slab, prm.ndeg, g)) {
         lay.embedded = lay.dense = true;      // the dense kernels, with masks from arrays where a tile is not regular

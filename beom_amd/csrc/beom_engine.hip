@@ -82,6 +82,7 @@ struct beom_engine {
     bool fold_stress = true, fold_static_ok = false;
     bool up_tt = false, up_tb = false, up_tu = false;   // a non-zero tt3d / tb3d / tu3d has been uploaded
     bool last_folded = false;          // the last step formed its stress inside the momentum sweep (beom_info "stress_folded")
+    bool last_uv_fused = false;        // the last step's momentum ran as the fused u+v sweep (beom_info "uv_fused")
     float *h0r4_dev = nullptr, *out4[3] = {nullptr, nullptr, nullptr};   // device-side output staging
     float *diag4[3] = {nullptr, nullptr, nullptr};
     double *scan_dev = nullptr;
@@ -642,10 +643,15 @@ static void launch_mont(beom_engine *E, int ilay) {
     const int nz = ilay ? 1 : E->d.nlay;
     LAUNCH_CTX(k_update_mont<CellGather>, k_update_mont<CellDense>, nz, E->d, ilay);
 }
+// update_viscosity's biharmonic part runs as the tiled sweep (k_biharm_tiled): every dense or embedded handle with svis > 0
+static bool biharm_tiled(const beom_engine *E) { return E->dense && E->P.svis > 0.0; }
 static void launch_visc(beom_engine *E, int ilay) {
     const int nz = ilay ? 1 : E->d.nlay;
     LAUNCH_CTX(k_update_visc<CellGather>, k_update_visc<CellDense>, nz, E->d, ilay);
-    if (E->d.svis > 0.0) {                         // biharmonic part of update_viscosity (:2508-2599)
+    if (E->d.svis > 0.0 && biharm_tiled(E) && ilay == 0) {      // biharmonic part of update_viscosity (:2508-2599), one tiled sweep
+        if (E->tile4) hipLaunchKernelGGL(k_biharm_tiled<1>, biharm_tiled_grid<1>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d);
+        else hipLaunchKernelGGL(k_biharm_tiled<2>, biharm_tiled_grid<2>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d);
+    } else if (E->d.svis > 0.0) {                  // packed handles, single-layer calls: the two table kernels
         const dim3 g = ilay ? E->grid_cells0 : E->grid_cells_layers_flat;
         hipLaunchKernelGGL(k_biharm_lap, g, dim3(BEOM_BLOCK), 0, E->stream, E->d, ilay);
         hipLaunchKernelGGL(k_biharm_flux, g, dim3(BEOM_BLOCK), 0, E->stream, E->d, ilay);
@@ -814,7 +820,7 @@ static StepScalars step_scalars(const beom_engine *E, int tstp, double tres, dou
     s.gene = (s.first3 || (E->lid && E->P.g_fb > 0.5)) ? 0.0 : E->P.g_fb;      // :1859,1877; :1880-1884: no multistep with a lid
     s.n_3d = n_3d;
     s.fused = can_fuse(E, n_3d, s.first3);
-    s.fused_uv = E->dense && E->fuse_uv && !(E->P.svis > 0.0);
+    s.fused_uv = E->dense && E->fuse_uv;           // (svis > 0: the v_cc / v_ll form, uu4 and vv4 read through L2)
     return s;
 }
 
@@ -867,6 +873,7 @@ static void one_step(beom_engine *E, int tstp, const StepScalars &s) {
     StepTimer *T = begin_step(E, tstp, s);
     const bool prod = step_front(E, s, T);
     const bool u_first = tstp % 2 == 0;                            // :2193-2199,2276-2282
+    E->last_uv_fused = s.fused_uv;
     if (s.fused_uv) timed(T, 6, [&] { launch_uv_fused(E, u_first, prod, s.gene, s.ramp, s.ctim); });
     else
         for (const bool x : {u_first, !u_first})
@@ -975,13 +982,15 @@ int beom_step_phase(beom_handle E, int tstp, double tres, double dtd8, double dt
     if (E->P.flag_nudging && E->P.mcbc < 0.5 && !E->obc && !E->obc_set) { set_err(errm, errm_len, "beom_step_phase: mcbc = 0 with nudging needs beom_set_open_boundaries (no_gradient_obc, private_mod.f95:2613-2679)"); return -6; }
     const StepScalars s = step_scalars(E, tstp, tres, dtd8, dt_r, rsta, n_3d);
     const bool south = d.slab && d.joff > 0, north = d.slab && d.joff + d.M < d.Mg;
-    if (!s.fused_uv || !(south || north) || d.M < 4 * kEdgeRows || phase < 1 || phase > 3 || E->obc || E->lid) {
+    // (svis > 0: a band's step stays whole)
+    if (!s.fused_uv || !(south || north) || d.M < 4 * kEdgeRows || phase < 1 || phase > 3 || E->obc || E->lid || E->P.svis > 0.0) {
         set_err(errm, errm_len, "beom_step_phase: split step not available for this step/configuration");
         return -20;
     }
     const int M = d.M;
     const bool u_first = tstp % 2 == 0;
     StepTimer *T = begin_step(E, tstp, s);
+    E->last_uv_fused = true;
     if (phase == 1) {
         E->split_prod = step_front(E, s, T);      // (s.fused_uv holds: parts 2 and 3 are the fused u+v sweep it prepares)
     } else if (phase == 2) {
@@ -1143,6 +1152,8 @@ int beom_info(beom_handle E, const char *what) {
     if (!E || !what) return -1;
     if (!strcmp(what, "stress_folded")) return E->last_folded ? 1 : 0;
     if (!strcmp(what, "tile_rows")) return E->dense ? (E->tile4 ? 4 : 8) : 0;
+    if (!strcmp(what, "biharm_tiled")) return biharm_tiled(E) ? 1 : 0;
+    if (!strcmp(what, "uv_fused")) return E->last_uv_fused ? 1 : 0;
     if (!strcmp(what, "lid_sweeps")) return (int)std::min<long long>(E->lid_sweeps, 2000000000ll);        // Gauss-Seidel sweeps kept, all steps so far
     if (!strcmp(what, "lid_solves")) return (int)std::min<long long>(E->lid_solves, 2000000000ll);
     if (!strcmp(what, "lid_launches")) return (int)std::min<long long>(E->lid_launches, 2000000000ll);

@@ -1623,9 +1623,227 @@ __global__ __launch_bounds__(BEOM_BLOCK) void k_rgld_correct(DevView d) {       
 }
 
 // ---- biharmonic viscosity, update_viscosity's svis > 0 part (private_mod.f95:2508-2599).
-//      A fork-specific option outside every BASELINE configuration: always via the neig/mask
-//      tables, five separate sweeps.  The reference rounds two expressions to DEFAULT real
-//      (`real(x)` without a kind, :2565 and :1472); so do we. ------------------------------------
+//      A fork-specific option outside every BASELINE configuration.  The reference rounds two
+//      expressions to DEFAULT real (`real(x)` without a kind, :2565 and :1472); so do we.
+//      The arithmetic of one cell as the tiled sweep uses it — statement by statement what the
+//      table kernels further down do: m* are the masks of the E, N, W, S neighbours (slots 1, 3,
+//      5, 7), x* their values. ------------------------------------------------------------------
+__device__ __forceinline__ double biharm_lap(double dl, double mself, double m1, double m3, double m5, double m7,
+                                             double x1, double x3, double x5, double x7, double x0) {      // :2508-2550
+    double r = 0.0;
+    if (mself > 0.5) {
+        r = r + 1.0 / (dl * dl) * (m1 * x1 + m3 * x3 + m5 * x5 + m7 * x7);
+        r = r - 1.0 / (dl * dl) * (m1 + m3 + m5 + m7) * x0;
+    }
+    return r;
+}
+// hh_q: the thickness at the vorticity point, numerator rounded to default real (:2565); m5, m6, m7 = mk_n of W, SW, S
+__device__ __forceinline__ double biharm_hq(double h, double m5, double m6, double m7, double h5, double h6, double h7) {
+    return (double)(float)(h + m5 * h5 + m6 * h6 + m7 * h7) / (1.0 + m5 + m6 + m7);
+}
+// uu4, vv4 of a cell (:2557-2598).  cE .. cS: the four conditions on the cell's GLOBAL coordinates (si <= lm - 1,
+// sj <= mm_glob - 1, si > 1, sj > 1); mkuv = mk_u * mk_v of the cell
+__device__ __forceinline__ void biharm_flux(double dl, double h, double hh_q, double du0, double dv0, double duE,
+                                            double dvN, double dvW, double duS, bool cE, bool cN, bool cW, bool cS,
+                                            double mkuv, double &uu, double &vv) {
+    uu = 0.0; vv = 0.0;
+    uu = uu - 1.0 / dl * h * du0 + 1.0 / dl * h * dv0;
+    vv = vv + 1.0 / dl * hh_q * du0 + 1.0 / dl * hh_q * dv0;
+    if (cE) uu = uu + 1.0 / dl * h * duE;
+    if (cN) uu = uu - 1.0 / dl * h * dvN;
+    if (cW) vv = vv - 1.0 / dl * hh_q * dvW;
+    if (cS) vv = vv - 1.0 / dl * hh_q * duS;
+    if (mkuv < 0.5) vv = 0.0;
+}
+
+// ---- the tiled sweep (dense and embedded handles, all layers: grid y): both halves of the biharmonic part in one
+//      launch.  u, v of a 64 x TY tile plus a ring of two and hlay plus a ring of one are staged in LDS, delu, delv
+//      are formed on the tile plus a ring of one IN LDS ONLY (over the image of u, v: nothing outside
+//      update_viscosity reads them), and uu4, vv4 of the tile's own cells go to global memory.  Algorithmic traffic
+//      24 B read + 16 B written per cell-layer (about 52 B with the ring over-fetch) against about 84 B for the two
+//      table launches.
+//      Interior tiles (tile and its ring of two inside 2..lm-1 x 2..mm_glob-1, regular on embedded frames): every
+//      mask is 1, every neighbour a plain offset, all four conditions hold.  All other tiles (the frame's rim, wraps,
+//      bands' edges, coasts) form delu, delv of each staged position BY LOOKUP: the entry at a geometric position is
+//      what a neighbour lookup of that position returns — wraps applied, 0 outside the frame and at land slots,
+//      which is what the table kernels read at packed cell 0 (delu(0) = delv(0) = 0, never written).
+template <int Q>
+struct BiharmGeom {
+    using G = TileGeom<Q>;
+    static constexpr int UR = G::TY + 4, UC = G::TX + 4;     // u, v: tile + ring of two
+    static constexpr int HR = G::TY + 2, HC = G::TX + 2;     // hlay, delu, delv: tile + ring of one
+};
+// local target (a, b) as a neighbour lookup resolves it: its slot (a, b become the wrapped coordinates), or 0 outside the
+// frame and at a land slot of an embedded frame (as k_mont_visc treats its land neighbours)
+__device__ __forceinline__ int biharm_lookup(const DevView &d, int &a, int &b) {
+    if (!halo_target<false>(d, a, b)) return 0;
+    const int t = a + (b - 1) * d.P;
+    return slot_is_cell(d, t) ? t : 0;
+}
+__device__ __forceinline__ void biharm_masks(const DevView &d, int t, int a, int b, double &mu, double &mv) {
+    if (d.embedded) { mu = d.mk_u[t]; mv = d.mk_v[t]; return; }      // (index 0: the caller's sentinel)
+    mu = 0.0; mv = 0.0;
+    if (t == 0) return;
+    CellDenseT<false> c;
+    c.set_cell(d, a, b);
+    mu = c.mk_u(); mv = c.mk_v();
+}
+// delu, delv of the cell at local (a, b) (a real cell of the frame), everything from global memory
+__device__ __forceinline__ void biharm_lap_at(const DevView &d, int a, int b, int ilay, double &du, double &dv) {
+    CellDenseT<false> c;
+    c.set_cell(d, a, b);
+    double mu[4], mv[4], xu[4], xv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                    // E, N, W, S
+        int ta = a + (k == 0 ? 1 : (k == 2 ? -1 : 0)), tb = b + (k == 1 ? 1 : (k == 3 ? -1 : 0));
+        const int t = biharm_lookup(d, ta, tb);
+        biharm_masks(d, t, ta, tb, mu[k], mv[k]);
+        xu[k] = LL(d.u, t, ilay); xv[k] = LL(d.v, t, ilay);
+    }
+    du = biharm_lap(d.dl, c.mk_u(), mu[0], mu[1], mu[2], mu[3], xu[0], xu[1], xu[2], xu[3], LL(d.u, c.ipnt, ilay));
+    dv = biharm_lap(d.dl, c.mk_v(), mv[0], mv[1], mv[2], mv[3], xv[0], xv[1], xv[2], xv[3], LL(d.v, c.ipnt, ilay));
+}
+
+template <int Q>
+__device__ __forceinline__ void body_biharm_int(const DevView &d, int x0, int y0, int ilay,
+                                                double (*s_u)[BiharmGeom<Q>::UC], double (*s_v)[BiharmGeom<Q>::UC],
+                                                double (*s_h)[BiharmGeom<Q>::HC]) {
+    using G = TileGeom<Q>;
+    using B = BiharmGeom<Q>;
+    const int tid = threadIdx.x;
+    const int lx = tid & 63, wy = tid >> 6;
+    const long long lay = d.n1 * (long long)(ilay - 1);
+    constexpr int NU = B::UR * B::UC, NUI = (NU + G::BLOCK - 1) / G::BLOCK;
+    constexpr int NH = B::HR * B::HC, NHI = (NH + G::BLOCK - 1) / G::BLOCK;
+    // ---- stage: every load first
+    double fu[NUI], fv[NUI], fh[NHI];
+    int ur[NUI], uc[NUI], hr[NHI], hc[NHI];
+#pragma unroll
+    for (int k = 0; k < NUI; ++k) {
+        const int idx = tid + k * G::BLOCK;
+        const int idc = idx < NU ? idx : tid;            // clamped: the load is harmless, the store is skipped
+        ur[k] = idc / B::UC; uc[k] = idc - ur[k] * B::UC;
+        const long long ip = (long long)(x0 - 2 + uc[k]) + (long long)(y0 - 3 + ur[k]) * d.P + lay;
+        fu[k] = d.u[ip]; fv[k] = d.v[ip];
+    }
+#pragma unroll
+    for (int k = 0; k < NHI; ++k) {
+        const int idx = tid + k * G::BLOCK;
+        const int idc = idx < NH ? idx : tid;
+        hr[k] = idc / B::HC; hc[k] = idc - hr[k] * B::HC;
+        fh[k] = d.hlay[(long long)(x0 - 1 + hc[k]) + (long long)(y0 - 2 + hr[k]) * d.P + lay];
+    }
+#pragma unroll
+    for (int k = 0; k < NUI; ++k)
+        if (tid + k * G::BLOCK < NU) { s_u[ur[k]][uc[k]] = fu[k]; s_v[ur[k]][uc[k]] = fv[k]; }
+#pragma unroll
+    for (int k = 0; k < NHI; ++k)
+        if (tid + k * G::BLOCK < NH) s_h[hr[k]][hc[k]] = fh[k];
+    __syncthreads();
+    // ---- delu, delv on the tile plus a ring of one (all masks 1), then over the image of u, v
+    double du[NHI], dv[NHI];
+#pragma unroll
+    for (int k = 0; k < NHI; ++k) {
+        const int r = hr[k] + 1, c = hc[k] + 1;          // position in the u, v image
+        du[k] = biharm_lap(d.dl, 1.0, 1.0, 1.0, 1.0, 1.0, s_u[r][c + 1], s_u[r + 1][c], s_u[r][c - 1], s_u[r - 1][c], s_u[r][c]);
+        dv[k] = biharm_lap(d.dl, 1.0, 1.0, 1.0, 1.0, 1.0, s_v[r][c + 1], s_v[r + 1][c], s_v[r][c - 1], s_v[r - 1][c], s_v[r][c]);
+    }
+    __syncthreads();
+    double (*s_du)[B::HC] = (double (*)[B::HC])s_u, (*s_dv)[B::HC] = (double (*)[B::HC])s_v;
+#pragma unroll
+    for (int k = 0; k < NHI; ++k)
+        if (tid + k * G::BLOCK < NH) { s_du[hr[k]][hc[k]] = du[k]; s_dv[hr[k]][hc[k]] = dv[k]; }
+    __syncthreads();
+    // ---- uu4, vv4 of the own cells
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int rr = wy + G::WAVES * q, j = y0 + rr;
+        if (!row_selected(d, j)) continue;
+        const int r = rr + 1, c = lx + 1;
+        const double h = s_h[r][c];
+        const double hh_q = biharm_hq(h, 1.0, 1.0, 1.0, s_h[r][c - 1], s_h[r - 1][c - 1], s_h[r - 1][c]);
+        double uu, vv;
+        biharm_flux(d.dl, h, hh_q, s_du[r][c], s_dv[r][c], s_du[r][c + 1], s_dv[r + 1][c], s_dv[r][c - 1], s_du[r - 1][c],
+                    true, true, true, true, 1.0, uu, vv);
+        const long long ip = (long long)(x0 + lx) + (long long)(j - 1) * d.P + lay;
+        d.uu4[ip] = uu; d.vv4[ip] = vv;
+    }
+}
+
+template <int Q>
+__device__ __forceinline__ void body_biharm_edge(const DevView &d, int x0, int y0, int ilay,
+                                                 double (*s_du)[BiharmGeom<Q>::HC], double (*s_dv)[BiharmGeom<Q>::HC]) {
+    using G = TileGeom<Q>;
+    using B = BiharmGeom<Q>;
+    const int tid = threadIdx.x;
+    const int lx = tid & 63, wy = tid >> 6;
+    constexpr int NH = B::HR * B::HC, NHI = (NH + G::BLOCK - 1) / G::BLOCK;
+    for (int k = 0; k < NHI; ++k) {
+        const int idx = tid + k * G::BLOCK;
+        if (idx >= NH) break;
+        const int r = idx / B::HC, c = idx - r * B::HC;
+        int a = x0 - 1 + c, b = y0 - 1 + r;
+        double du = 0.0, dv = 0.0;                       // delu(0), delv(0)
+        if (biharm_lookup(d, a, b) != 0) biharm_lap_at(d, a, b, ilay, du, dv);
+        s_du[r][c] = du; s_dv[r][c] = dv;
+    }
+    __syncthreads();
+    const int i = x0 + lx;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int rr = wy + G::WAVES * q, j = y0 + rr;
+        if (!(i <= d.L && j <= d.M && row_selected(d, j))) continue;
+        CellDenseT<false> cc;
+        cc.set_cell(d, i, j);
+        if (!slot_is_cell(d, cc.ipnt)) continue;         // embedded: land slots are never written (they read as uu4(0) = vv4(0) = 0)
+        const int r = rr + 1, c = lx + 1;
+        double du0 = s_du[r][c], dv0 = s_dv[r][c];
+        // orphan column / row of a periodic frame: its staged position holds the WRAPPED cell's values (it is a wrap target)
+        if ((d.xper && i == d.L) || (d.yper && !d.slab && j == d.M)) biharm_lap_at(d, i, j, ilay, du0, dv0);
+        const double h = LL(d.hlay, cc.ipnt, ilay);
+        double mn[3], hn[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                    // W, SW, S
+            int a = i - (k < 2 ? 1 : 0), b = j - (k > 0 ? 1 : 0);
+            const int t = biharm_lookup(d, a, b);
+            mn[k] = d.embedded ? d.mk_n[t] : (t == 0 ? 0.0 : cc.mk_n_ij(a, b + d.joff));
+            hn[k] = LL(d.hlay, t, ilay);
+        }
+        const double hh_q = biharm_hq(h, mn[0], mn[1], mn[2], hn[0], hn[1], hn[2]);
+        const int sj = j + d.joff;
+        double uu, vv;
+        biharm_flux(d.dl, h, hh_q, du0, dv0, s_du[r][c + 1], s_dv[r + 1][c], s_dv[r][c - 1], s_du[r - 1][c],
+                    i <= d.lm - 1, sj <= d.mm_glob - 1, i > 1, sj > 1, cc.mk_u() * cc.mk_v(), uu, vv);
+        LL(d.uu4, cc.ipnt, ilay) = uu; LL(d.vv4, cc.ipnt, ilay) = vv;
+    }
+}
+
+// 18 KB of LDS in the 64 x 8 geometry (12 KB in 64 x 4): eight workgroups per CU, so registers set the occupancy
+template <int Q>
+__global__ __launch_bounds__(TileGeom<Q>::BLOCK) void k_biharm_tiled(DevView d) {
+    using G = TileGeom<Q>;
+    using B = BiharmGeom<Q>;
+    __shared__ double s_u[B::UR][B::UC];
+    __shared__ double s_v[B::UR][B::UC];
+    __shared__ double s_h[B::HR][B::HC];
+    const TileMap tm(d, G::TX, G::TY);
+    int ty, ch;
+    if (!tm.locate(blockIdx.x, ty, ch)) return;               // whole block: no barrier is skipped by part of it
+    const int x0 = ch * G::TX + 1, y0 = ty * G::TY + 1;
+    const int ilay = blockIdx.y + 1;
+    // block-uniform: the tile and its ring of two lie in 2..L-2 x 2..M-2 (global rows too)
+    const bool interior = x0 - 2 >= 2 && x0 + G::TX + 1 <= d.L - 2 && y0 - 2 >= 2 && y0 + G::TY + 1 <= d.M - 2
+                          && y0 - 2 + d.joff >= 2 && y0 + G::TY + 1 + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, G::TY);
+    if (interior) body_biharm_int<Q>(d, x0, y0, ilay, s_u, s_v, s_h);
+    else body_biharm_edge<Q>(d, x0, y0, ilay, (double (*)[B::HC])s_u, (double (*)[B::HC])s_v);
+}
+template <int Q>
+static inline dim3 biharm_tiled_grid(const DevView &d) {
+    return dim3(TileMap(d, TileGeom<Q>::TX, TileGeom<Q>::TY).blocks(), (unsigned)d.nlay, 1);
+}
+
+// The table kernels: packed (non-dense) handles and the per-layer entry point (beom_update_viscosity with ilay != 0),
+// one thread per packed cell, delu, delv through global memory between the two launches.
 __global__ __launch_bounds__(BEOM_BLOCK) void k_biharm_lap(DevView d, int ilay0) {             // :2508-2550
     const int ipnt = blockIdx.x * BEOM_BLOCK + threadIdx.x + 1;
     const int ilay = ilay0 ? ilay0 : (int)blockIdx.y + 1;

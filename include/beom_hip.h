@@ -218,7 +218,10 @@ int beom_unpack_rows2(beom_handle h, int nrows, int jlo_a, const void *buffer_a,
 int beom_set_option(beom_handle h, const char *name, int value);
 /* Introspection (>= 0, or -3 for an unknown name): "stress_folded" = the last step formed its stress inside the momentum
  * sweep (1) or through distribute_stress' own launch and the three arrays (0); "tile_rows" = rows of a tile of the tiled
- * sweeps (8 | 4; 0 on the table path). */
+ * sweeps (8 | 4; 0 on the table path); "biharm_tiled" = the biharmonic part of this handle's update_viscosity (svis > 0,
+ * private_mod.f95:2508-2599) runs as the tiled sweep k_biharm_tiled (1: every dense or embedded handle with svis > 0) or
+ * not (0: the table kernels of a packed handle, and every handle with svis = 0); "uv_fused" = the last step's update_u and
+ * update_v ran as the fused sweep (1) or as two sweeps (0; 0 before the first step). */
 int beom_info(beom_handle h, const char *what);
 
 /* Run all launches of this handle on the caller's HIP stream (e.g. the stream a

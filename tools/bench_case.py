@@ -16,6 +16,9 @@ def _case():
             "headline": lambda: I.case_headline(4096, 4096, 4),
             "headline_gather": lambda: I.case_headline(4096, 4096, 4),     # same frame through the neig tables
             "headline_land": lambda: with_land(I.case_headline(4096, 4096, 4)),
+            # biharmonic viscosity (the oracle stays finite with this svis at reduced size over the timed steps)
+            "headline_biharm": lambda: biharm(I.case_headline(4096, 4096, 4)),
+            "headline_land_biharm": lambda: biharm(with_land(I.case_headline(4096, 4096, 4))),
             "band8": lambda: I.case_headline(4096, 512, 4),                # what one of 8 / 4 / 2 bands of the headline frame holds
             "band4": lambda: I.case_headline(4096, 1024, 4),
             "band2": lambda: I.case_headline(4096, 2048, 4),
@@ -34,6 +37,10 @@ def with_land(pf):
     h[((x - 0.3 * lm) ** 2 + (y - 0.6 * mm) ** 2) < (0.126 * lm) ** 2] = 0.0
     files["init"][h == 0.0] = 0.0
     return p.replace(ndeg=I.get_nbr_deg_freedom(h)), files
+
+
+def biharm(pf):
+    return pf[0].replace(svis="1.e9"), pf[1]
 
 
 p, files = _case()

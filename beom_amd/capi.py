@@ -95,7 +95,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_dense_host.h",
                os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -195,6 +195,16 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.beom_multi_set_open_boundaries_local.argtypes = [MH, ci, C.POINTER(ci), ci, C.POINTER(ci), cp, ci]
     lib.beom_multi_upload_local.argtypes = [MH, C.POINTER(BeomState), C.POINTER(BeomState), cp, ci]
     lib.beom_multi_download_local.argtypes = [MH, C.POINTER(BeomState), C.POINTER(BeomState), cp, ci]
+    if hasattr(lib, "beom_integral_count"):      # (an older build named by BEOM_HIP_LIB for an A/B of the steps has no integrals)
+        lib.beom_integral_count.argtypes = [ci]
+        lib.beom_integral_rows.argtypes = [H, ci, ci, dpp, cp, ci]
+        lib.beom_integral_combine.argtypes = [dpp, ci, ci, dpp]
+        lib.beom_integrals.argtypes = [H, dpp, cp, ci]
+        lib.beom_multi_integrals.argtypes = [MH, dpp, cp, ci]
+        lib.beom_multi_integral_rows_local.argtypes = [MH, C.POINTER(ci), C.POINTER(ci), dpp, cp, ci]
+        for name in ("beom_integral_count", "beom_integral_rows", "beom_integral_combine", "beom_integrals",
+                     "beom_multi_integrals", "beom_multi_integral_rows_local"):
+            getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
                  "beom_multi_stats", "beom_multi_create_ex", "beom_multi_describe", "beom_multi_engine",
@@ -231,7 +241,9 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_download_outputs", "beom_multi_download_diag", "beom_multi_set_open_boundaries",
            "beom_multi_set_option", "beom_multi_profile_start", "beom_multi_profile_stop", "beom_rccl_unique_id", "beom_rccl_version",
            "beom_multi_window", "beom_multi_create_local", "beom_multi_create_local_ex", "beom_multi_set_open_boundaries_local",
-           "beom_multi_upload_local", "beom_multi_download_local")
+           "beom_multi_upload_local", "beom_multi_download_local",
+           "beom_integral_count", "beom_integral_rows", "beom_integral_combine", "beom_integrals",
+           "beom_multi_integrals", "beom_multi_integral_rows_local")
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -240,6 +252,36 @@ SCRATCH_NAMES = ("mont", "rvor", "pvor", "dive", "d2hx", "d2hy")
 
 class BeomError(RuntimeError):
     pass
+
+
+INTEGRAL_NAMES = ("vol", "ke", "ens", "circ")
+
+
+def combine_integral_rows(rows) -> np.ndarray:
+    """beom_integral_combine (host only, no device): rows[nrows, count] in global row order -> the count sums, by the
+    pairwise tree over rows (rows padded with +0.0 to a power of two)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise BeomError("combine_integral_rows: rows[nrows, count] expected, got shape %s" % (rows.shape,))
+    out = np.zeros(rows.shape[1])
+    rc = load().beom_integral_combine(_dp(rows), rows.shape[0], rows.shape[1], _dp(out))
+    if rc != 0:
+        raise BeomError("beom_integral_combine %d" % rc)
+    return out
+
+
+def scale_integrals(raw: np.ndarray, prm: BeomParams) -> dict:
+    """The raw sums of beom_integrals and the figures they stand for: volume_m3[l] = dl^2 * vol, kinetic_J[l] =
+    0.5 * rhon(l) * dl^2 * ke, enstrophy[l] and circulation[l] as the domain sums, potential_J = 0.5 * rhon(1) * grav * dl^2 *
+    eta2 (the barotropic part only; with a rigid lid eta is the column misfit)."""
+    nl = prm.nlay
+    q = np.asarray(raw[:4 * nl]).reshape(nl, 4)
+    dl2 = prm.dl * prm.dl
+    rhon = np.array(list(prm.rhon)[:nl])
+    return {"raw": np.array(raw), "vol": q[:, 0].copy(), "ke": q[:, 1].copy(), "ens": q[:, 2].copy(), "circ": q[:, 3].copy(),
+            "eta2": float(raw[4 * nl]),
+            "volume_m3": dl2 * q[:, 0], "kinetic_J": 0.5 * rhon * dl2 * q[:, 1], "enstrophy": q[:, 2].copy(),
+            "circulation": q[:, 3].copy(), "potential_J": 0.5 * rhon[0] * prm.grav * dl2 * float(raw[4 * nl])}
 
 
 class Engine:
@@ -324,6 +366,19 @@ class Engine:
 
     def sync(self):
         self._check(self.lib.beom_sync(self.h, self._err, ERRLEN))
+
+    def integrals(self) -> dict:
+        """Conservation integrals of the state as it stands (beom_integrals): the raw sums and the scaled figures
+        (scale_integrals).  Syncs the handle's stream."""
+        raw = np.zeros(self.lib.beom_integral_count(self.p.nlay))
+        self._check(self.lib.beom_integrals(self.h, _dp(raw), self._err, ERRLEN))
+        return scale_integrals(raw, self.prm)
+
+    def integral_rows(self, jlo: int, nrows: int) -> np.ndarray:
+        """Row sums [nrows, 4*nlay + 1] of local rows jlo .. jlo+nrows-1 (1-based); combine_integral_rows finishes them."""
+        rows = np.zeros((nrows, self.lib.beom_integral_count(self.p.nlay)))
+        self._check(self.lib.beom_integral_rows(self.h, jlo, nrows, _dp(rows), self._err, ERRLEN))
+        return rows
 
     def set_stream(self, hip_stream: Optional[int]):
         """hip_stream: integer handle (torch.cuda.current_stream().cuda_stream; 0 = the default
@@ -512,6 +567,12 @@ class MultiEngine:
     def sync(self):
         self._check(self.lib.beom_multi_sync(self.h, self._err, ERRLEN))
 
+    def integrals(self) -> dict:
+        """As Engine.integrals: every band forms the row sums of its owned rows; the same bits as the single handle's."""
+        raw = np.zeros(self.lib.beom_integral_count(self.p.nlay))
+        self._check(self.lib.beom_multi_integrals(self.h, _dp(raw), self._err, ERRLEN))
+        return scale_integrals(raw, self.prm)
+
     def stats(self) -> dict:
         a, b = C.c_longlong(), C.c_longlong()
         self.lib.beom_multi_stats(self.h, C.byref(a), C.byref(b))
@@ -658,6 +719,18 @@ class BandEngine(MultiEngine):
         so = self._state({k: getattr(self.orphan, k) for k in STATE_NAMES}) if self.orphan is not None else None
         self._check(self.lib.beom_multi_upload_local(self.h, C.byref(sw), C.byref(so) if so is not None else None,
                                                      self._err, ERRLEN))
+
+    def integrals(self) -> dict:
+        raise BeomError("a band holds a window: gather integral_rows() of all bands and combine_integral_rows them")
+
+    def integral_rows(self):
+        """(own0, own1, rows[own1-own0+1, 4*nlay + 1]): the row sums of this band's owned global rows.  The caller stacks the
+        bands' rows in global row order (row mm+1 of a frame periodic in y: zeros) for combine_integral_rows."""
+        w = self.band(0)
+        rows = np.zeros((w["own1"] - w["own0"] + 1, self.lib.beom_integral_count(self.pg.nlay)))
+        a, b = C.c_int(), C.c_int()
+        self._check(self.lib.beom_multi_integral_rows_local(self.h, C.byref(a), C.byref(b), _dp(rows), self._err, ERRLEN))
+        return a.value, b.value, rows
 
     def download(self, names=STATE_NAMES, orphan: bool = False) -> dict:
         out = {k: np.zeros_like(getattr(self.f, k)) for k in names}

@@ -16,6 +16,7 @@
 
 #include "beom_dev.h"
 #include "beom_kernels.h"
+#include "beom_integrals.h"
 #include "beom_dense_host.h"
 
 namespace {
@@ -108,6 +109,11 @@ struct beom_engine {
     bool profile_rotate = false;       // option "profile_rotate"
     bool split_prod = false;           // split steps: part 1's Montgomery sweep left the viscous products for parts 2 and 3
     bool tile4 = false;                // the tiled sweeps run the 64 x 4 geometry (frames of one or two rounds of workgroups)
+    // conservation integrals (beom_integral_rows): chunk sums and row sums of up to M rows, allocated on the first call; on
+    // the table path also the packed cell of every (i, j) and the wraps read off neig
+    double *integ_part = nullptr, *integ_rows = nullptr;
+    int32_t *integ_cellmap = nullptr;
+    int integ_xper = 0, integ_yper = 0;
     char last_err[512] = {0};
 };
 
@@ -1090,6 +1096,76 @@ int beom_download_diag(beom_handle E, float *pvor4, float *mont4, float *vcc4, c
     HIP_TRY(hipStreamSynchronize(E->stream));
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// ---- conservation integrals (beom_integrals.h) -----------------------------------------------------------------------
+static int pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+
+int beom_integral_count(int nlay) { return 4 * nlay + 1; }
+
+int beom_integral_rows(beom_handle E, int jlo, int nrows, double *rows, char *errm, int errm_len) {
+    if (!E || !rows) { set_err(errm, errm_len, "beom_integral_rows: null argument"); return -1; }
+    DevView &d = E->d;
+    if (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M) { set_err(errm, errm_len, "beom_integral_rows: rows %d..%d outside 1..%d", jlo, jlo + nrows - 1, d.M); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const int count = 4 * d.nlay + 1, nch = (d.L + 63) / 64, nchp2 = pow2_ceil(nch);
+    const int width = std::min(64, pow2_ceil(d.L));
+    if (nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "beom_integral_rows: rows of more than %d columns", 64 * 64 * kIntegralMaxGroups); return -4; }
+    if (!E->integ_part) {
+        HIP_TRY(hipMalloc((void **)&E->integ_part, (size_t)d.M * nch * count * sizeof(double)));
+        E->allocs.push_back(E->integ_part);
+        HIP_TRY(hipMalloc((void **)&E->integ_rows, (size_t)d.M * count * sizeof(double)));
+        E->allocs.push_back(E->integ_rows);
+        E->integ_xper = d.xper; E->integ_yper = d.yper;
+        if (!E->dense) {
+            int32_t *flags = nullptr;
+            HIP_TRY(hipMalloc((void **)&E->integ_cellmap, ((size_t)d.L * d.M + 2) * sizeof(int32_t)));
+            E->allocs.push_back(E->integ_cellmap);
+            HIP_TRY(hipMemsetAsync(E->integ_cellmap, 0, ((size_t)d.L * d.M + 2) * sizeof(int32_t), E->stream));
+            flags = E->integ_cellmap + (size_t)d.L * d.M;
+            hipLaunchKernelGGL(k_integral_cellmap, dim3((unsigned)((d.ndeg + BEOM_BLOCK - 1) / BEOM_BLOCK)), dim3(BEOM_BLOCK), 0, E->stream,
+                               d, E->integ_cellmap, flags);
+            int32_t fl[2] = {0, 0};
+            HIP_TRY(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, E->stream));
+            HIP_TRY(hipStreamSynchronize(E->stream));
+            E->integ_xper = fl[0]; E->integ_yper = fl[1];
+        }
+    }
+    const dim3 g((unsigned)nch, (unsigned)((nrows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
+    if (E->dense) hipLaunchKernelGGL(k_integral_rows<true>, g, b, 0, E->stream, d, jlo, nrows, width, E->integ_xper, E->integ_yper,
+                                     (const int32_t *)nullptr, E->integ_part);
+    else hipLaunchKernelGGL(k_integral_rows<false>, g, b, 0, E->stream, d, jlo, nrows, width, E->integ_xper, E->integ_yper,
+                            (const int32_t *)E->integ_cellmap, E->integ_part);
+    const long long nt = (long long)nrows * count;
+    hipLaunchKernelGGL(k_integral_chunks, dim3((unsigned)nrows), dim3(64), 0, E->stream,
+                       (const double *)E->integ_part, E->integ_rows, count, nch, nchp2);
+    HIP_TRY(hipMemcpyAsync(rows, E->integ_rows, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// host only: the tree over the row sums, rows padded with +0.0 to the next power of two
+int beom_integral_combine(const double *rows, int nrows_total, int count, double *out) {
+    if (!rows || !out || nrows_total < 1 || count < 1) return -1;
+    const int n2 = pow2_ceil(nrows_total);
+    std::vector<double> w((size_t)n2);
+    for (int k = 0; k < count; ++k) {
+        for (int r = 0; r < n2; ++r) w[(size_t)r] = r < nrows_total ? rows[(size_t)r * count + k] : 0.0;
+        for (int n = n2; n > 1; n >>= 1)
+            for (int m = 0; m < n / 2; ++m) w[(size_t)m] = w[(size_t)(2 * m)] + w[(size_t)(2 * m + 1)];
+        out[k] = w[0];
+    }
+    return 0;
+}
+
+int beom_integrals(beom_handle E, double *out, char *errm, int errm_len) {
+    if (!E || !out) { set_err(errm, errm_len, "beom_integrals: null argument"); return -1; }
+    const int count = 4 * E->d.nlay + 1, M = E->d.M;
+    std::vector<double> rows((size_t)M * count);
+    const int rc = beom_integral_rows(E, 1, M, rows.data(), errm, errm_len);
+    if (rc) return rc;
+    return beom_integral_combine(rows.data(), M, count, out);
 }
 
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)

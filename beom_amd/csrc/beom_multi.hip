@@ -1166,6 +1166,34 @@ int beom_multi_download_diag(beom_multi_handle M, float *pvor4, float *mont4, fl
     return 0;
 }
 
+// Conservation integrals of a frame cut into bands (beom_integrals.h): a band owns whole rows, so its row sums are the
+// frame's; the tree over rows (beom_integral_combine) does not care who formed them.
+static int band_integral_rows(beom_multi *M, int k, double *rows, char *errm, int errm_len) {
+    const Band &s = M->band[k];
+    return beom_integral_rows(M->eng[k], s.gs + 1, s.nown(), rows, errm, errm_len);
+}
+
+int beom_multi_integrals(beom_multi_handle M, double *out, char *errm, int errm_len) {
+    if (!M || !out) { m_err(errm, errm_len, "beom_multi_integrals: null argument"); return -1; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_integrals: this handle holds a window (beom_multi_integral_rows_local)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (M->nb == 1 && !M->ring) return beom_integrals(M->eng[0], out, errm, errm_len);
+    const int count = beom_integral_count(M->P.nlay), Mg = M->P.mm + 1;
+    // (a ring's orphan row mm+1 duplicates row 1: every sum of it is +0, the companion frame is not asked)
+    std::vector<double> rows((size_t)Mg * count, 0.0);
+    for (int k = 0; k < M->n; ++k)
+        M_RC(band_integral_rows(M, k, &rows[(size_t)(M->band[k].own0 - 1) * count], errm, errm_len));
+    return beom_integral_combine(rows.data(), Mg, count, out);
+}
+
+int beom_multi_integral_rows_local(beom_multi_handle M, int *own0, int *own1, double *rows, char *errm, int errm_len) {
+    if (!M || !rows || M->n != 1) { m_err(errm, errm_len, "beom_multi_integral_rows_local: needs a handle with one band"); return -1; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (own0) *own0 = M->band[0].own0;
+    if (own1) *own1 = M->band[0].own1;
+    return band_integral_rows(M, 0, rows, errm, errm_len);
+}
+
 int beom_multi_upload_local(beom_multi_handle M, const beom_state *win, const beom_state *orphan, char *errm, int errm_len) {
     if (!M || !win) { m_err(errm, errm_len, "null argument"); return -1; }
     if (!M->local_mode) { m_err(errm, errm_len, "beom_multi_upload_local: this handle was created from global arrays"); return -3; }

@@ -109,6 +109,23 @@ module beom_cabi
       integer(c_int)           :: rc
     end function beom_multi_download_outputs
 
+    ! conservation integrals: 4*nlay + 1 raw sums (include/beom_hip.h)
+    function beom_integrals(handle, sums, errm, errm_len) bind(C, name = 'beom_integrals') result(rc)
+      import :: c_int, c_ptr, c_char
+      type(c_ptr), value       :: handle, sums
+      character(kind = c_char) :: errm(*)
+      integer(c_int), value    :: errm_len
+      integer(c_int)           :: rc
+    end function beom_integrals
+
+    function beom_multi_integrals(handle, sums, errm, errm_len) bind(C, name = 'beom_multi_integrals') result(rc)
+      import :: c_int, c_ptr, c_char
+      type(c_ptr), value       :: handle, sums
+      character(kind = c_char) :: errm(*)
+      integer(c_int), value    :: errm_len
+      integer(c_int)           :: rc
+    end function beom_multi_integrals
+
     function beom_multi_download_diag(handle, pvor, mont, v_cc, errm, errm_len)                          &
              bind(C, name = 'beom_multi_download_diag') result(rc)
       import :: c_int, c_ptr, c_char

@@ -55,6 +55,10 @@ module private_mod
   integer     :: ngpu = 1
   integer  :: out_rec = 0
   logical  :: out_ready = .false.
+  ! BEOM_INTEGRALS=1: every output record also appends a line of conservation integrals to odir/integrals.txt
+  logical  :: integrals_on = .false.
+  real(c_double), allocatable, target :: isum(:)  ! 4*nlay + 1 raw sums (beom_integrals)
+  real(c_double) :: int_dl2, int_grav, int_rhon(nlay)
 
 contains
 
@@ -157,6 +161,7 @@ subroutine setup_state()
   end if
 
   call gpu_start()
+  if ( integrals_on .and. rsta < 0.5_rw ) call write_integrals( .true. )   ! the record write_outputs has just committed
   deallocate( h_2d, h_0 )
   if ( errc /= 0 ) call quit()
   errm = errm(1:lerm)
@@ -941,6 +946,7 @@ subroutine write_outputs_from_gpu()
   write( unum, * ) real(ctim, r8)
   close( unum )
   out_rec = out_rec + 1
+  if ( integrals_on ) call write_integrals( .false. )
   write(ioso, *) 'ctim = ', ctim, ' days; dt_s = ', dt_s, ' days; record = ', out_rec - 1
   do k = 1, nlay
     write(ioso, *) 'min/max h', k, '= ', real(mnmx(1, k), rw), real(mnmx(2, k), rw)
@@ -952,6 +958,43 @@ subroutine write_outputs_from_gpu()
     call fail( -int(thin), 'layer number ' // trim(txt) // ' has its thickness < hmin; Calculation halted.' )
   end if
 end subroutine write_outputs_from_gpu
+
+! One line of odir/integrals.txt per output record (BEOM_INTEGRALS=1): ctim, then per layer the volume (m^3), the kinetic
+! energy (J), the potential enstrophy and the circulation (domain sums), then the barotropic potential energy (J); es24.16
+! round-trips real*8.  The sums are formed on the device(s) (beom_integrals; same bits for one device or several).
+subroutine write_integrals(fresh)
+  logical, intent(in) :: fresh
+  character(kind = c_char) :: cmsg(lstr + 1)
+  character(32) :: fmt
+  integer(c_int) :: rc
+  integer  :: unum, ios, k
+  real(c_double) :: line(4 * nlay + 1)
+  if ( .not. allocated(isum) ) allocate( isum(4 * nlay + 1) )
+  cmsg = c_null_char
+  if ( ngpu > 1 ) then
+    rc = beom_multi_integrals( gpus, c_loc(isum), cmsg, int(lstr, c_int) )
+  else
+    rc = beom_integrals( gpu, c_loc(isum), cmsg, int(lstr, c_int) )
+  end if
+  call gpu_check( rc, cmsg, 'beom_integrals' )
+  do k = 1, nlay
+    line(4 * k - 3) = int_dl2 * isum(4 * k - 3)
+    line(4 * k - 2) = 0.5_c_double * int_rhon(k) * int_dl2 * isum(4 * k - 2)
+    line(4 * k - 1) = isum(4 * k - 1)
+    line(4 * k)     = isum(4 * k)
+  end do
+  line(4 * nlay + 1) = 0.5_c_double * int_rhon(1) * int_grav * int_dl2 * isum(4 * nlay + 1)
+  unum = get_un()
+  if ( fresh ) then
+    open( unit = unum, file = trim(odir) // 'integrals.txt', form = 'formatted', action = 'write', status = 'replace', iostat = ios )
+  else
+    open( unit = unum, file = trim(odir) // 'integrals.txt', form = 'formatted', action = 'write', status = 'unknown', &
+          position = 'append', iostat = ios )
+  end if
+  write( fmt, '(a,i0,a)' ) '(', 4 * nlay + 2, 'es24.16)'
+  write( unum, fmt ) real(ctim, r8), line
+  close( unum )
+end subroutine write_integrals
 
 subroutine write_field(var, fresh)                               ! write_array (:2817-3001)
   character(4), intent(in) :: var
@@ -1048,6 +1091,9 @@ subroutine gpu_start()
   if ( has_tide ) p_tide = c_loc(tide)
   if ( has_bodf ) p_bodf = c_loc(bodf)
   cmsg = c_null_char
+  call get_environment_variable( 'BEOM_INTEGRALS', envv, status = ios )
+  integrals_on = ios == 0 .and. trim(envv) == '1'
+  int_dl2 = prm%dl * prm%dl;  int_grav = prm%grav;  int_rhon(1:nlay) = prm%rhon(1:nlay)
   call get_environment_variable( 'BEOM_NGPU', envv, status = ios )
   ngpu = 1
   if ( ios == 0 ) read( envv, *, iostat = ios ) ngpu

@@ -260,6 +260,30 @@ int beom_profile_steps(beom_handle h, int tstp_first, int nsteps,
                        double tres, double dtd8, double dt_r, double rsta, int n_3d,
                        double *ms, int *launches, char *errm, int errm_len);
 
+/* ---- Conservation integrals of the state as it stands between two steps (no reference routine: the reference's test
+ * case 3 forms them from the output files, testcases/conservation.m:116-211).  All FP64, raw sums over the frame:
+ *   out[(l-1)*4 + 0]  vol   sum of mk_n*h                                    layer volume / dl^2
+ *   out[(l-1)*4 + 1]  ke    sum of mk_u*((u*u)*hcu) + mk_v*((v*v)*hcv)       kinetic energy = 0.5*rhon(l)*dl^2 * ke, the thickness
+ *                           at a velocity point being the momentum sweeps' own (private_mod.f95:1438, 1521)
+ *   out[(l-1)*4 + 2]  ens   sum of 0.5*(pvor*pvor)*(have/nm) where mkpi > 0.5 and nm > 0 (:2421-2433; conservation.m:203-206)
+ *   out[(l-1)*4 + 3]  circ  sum of rvor (:2388-2389)
+ *   out[4*nlay]       eta2  sum of mk_n*(eta*eta), eta = hcol - h_th (:2367-2373): ONLY the barotropic part of the potential
+ *                           energy, 0.5*rhon(1)*grav*dl^2 * eta2 (as conservation.m:147-150; the interface part needs the rest
+ *                           thicknesses, which the engine does not hold).  With a rigid lid (rgld = 1) eta is the column misfit.
+ * rvor and pvor are what update_mont_rvor_pvor_dive_kine would store for this state (recomputed, not the step's scratch).
+ * The duplicated column lm+1 of a frame periodic in x and row mm+1 of one periodic in y contribute +0 to every sum.
+ * Order of summation: the terms on the rectangle c = i-1, r = j-1 (+0.0 where there is no packed cell); each row by the pairwise
+ * tree over the aligned column index (level k+1 adds elements 2m and 2m+1 of level k, the row padded with +0.0 to a power of
+ * two), then the row sums by the same tree over rows.  No atomics: the results are the same bits for a dense handle, the table
+ * path and a frame cut into any number of bands. */
+int beom_integral_count(int nlay);                          /* 4*nlay + 1 */
+/* rows[(j-jlo)*count + k]: the row sums of local rows jlo..jlo+nrows-1; syncs the handle's stream */
+int beom_integral_rows(beom_handle h, int jlo, int nrows, double *rows, char *errm, int errm_len);
+/* host only, no device: the tree over rows; rows[r*count + k] in global row order */
+int beom_integral_combine(const double *rows, int nrows_total, int count, double *out);
+/* = beom_integral_rows(1..mm+1) + beom_integral_combine */
+int beom_integrals(beom_handle h, double *out, char *errm, int errm_len);
+
 /* ---- Several GPUs: the frame cut into bands of rows (SURVEY §8b "Threading", §8e) -------------
  * No reference counterpart (the reference is OpenMP only).  The whole DENSE frame (ndeg = (lm+1)(mm+1))
  * is cut into bands of rows, one band per HIP device, each an ordinary slab handle with 4 ghost rows
@@ -391,6 +415,13 @@ int beom_multi_upload_local(beom_multi_handle h, const beom_state *window, const
                             char *errm, int errm_len);
 int beom_multi_download_local(beom_multi_handle h, beom_state *window, beom_state *orphan,
                               char *errm, int errm_len);
+
+/* Conservation integrals (see beom_integrals).  Global-array handles: every band forms the row sums of its OWNED rows; a
+ * ring's row mm+1 duplicates row 1 and is all +0, so the companion frame is not asked; combined in global row order. */
+int beom_multi_integrals(beom_multi_handle m, double *out, char *errm, int errm_len);
+/* one band per process: the row sums of this band's owned rows own0..own1 (rows[(j-own0)*count + k]); the caller gathers the
+ * bands' rows in global row order (row mm+1 of a frame periodic in y: zeros) and combines with beom_integral_combine */
+int beom_multi_integral_rows_local(beom_multi_handle m, int *own0, int *own1, double *rows, char *errm, int errm_len);
 
 #ifdef __cplusplus
 }

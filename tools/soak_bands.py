@@ -30,7 +30,7 @@ for name, mk in (("headline 4096x1024x4", lambda: I.case_headline(4096, 1024, 4)
                  ("beach 4096x512x2 (no Leith)", lambda: I.case_carrier_beach(lm=4096, mm=512, nlay=2, dt_s=0.08))):
     p, files = mk()
     f = read_input_data(p, files=files)
-    one = capi.Engine(f); one.step(1, N); ref = one.download(("hlay", "u", "v", "h_u", "h_v")); one.close()
+    one = capi.Engine(f); one.step(1, N); ref = one.download(("hlay", "u", "v", "h_u", "h_v")); iref = one.integrals()["raw"]; one.close()
     for nb in (2, 5, 8):
         m = capi.MultiEngine(f, devices=[0] * nb)
         t = time.perf_counter()
@@ -38,6 +38,10 @@ for name, mk in (("headline 4096x1024x4", lambda: I.case_headline(4096, 1024, 4)
             m.step(1 + k, min(97, N - k), sync=False)
         got = m.download(("hlay", "u", "v", "h_u", "h_v")); dt = time.perf_counter() - t
         ok = all(np.array_equal(ref[k], got[k]) for k in ref)
-        print(json.dumps({"case": name, "bands": nb, "steps": N, "bitwise_equal": ok, "stats": m.stats(), "finite": bool(np.isfinite(got["hlay"]).all())}), flush=True)
+        ints = m.integrals()["raw"]                     # conservation integrals: finite, and the single handle's bits
+        iok = bool(np.isfinite(ints).all()) and bool(np.array_equal(ints.view(np.uint64), iref.view(np.uint64)))
+        print(json.dumps({"case": name, "bands": nb, "steps": N, "bitwise_equal": ok, "stats": m.stats(), "finite": bool(np.isfinite(got["hlay"]).all()),
+                          "integrals_finite_and_equal": iok}), flush=True)
+        ok = ok and iok
         m.close()
         assert ok

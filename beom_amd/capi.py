@@ -17,6 +17,7 @@ from .params import Params
 
 BEOM_MAX_LAYERS = 16
 BEOM_ABI_VERSION = 2
+BEOM_MAX_TRACERS = 8
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BEOM_HIP_LIB", os.path.join(_HERE, "csrc", "libbeom_hip.so"))
 
@@ -95,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_dense_host.h",
                os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -205,6 +206,17 @@ def load(path: Optional[str] = None) -> C.CDLL:
         for name in ("beom_integral_count", "beom_integral_rows", "beom_integral_combine", "beom_integrals",
                      "beom_multi_integrals", "beom_multi_integral_rows_local"):
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_tracers"):         # (likewise: an older build has no tracers)
+        lib.beom_set_tracers.argtypes = [H, ci, cp, ci]
+        lib.beom_upload_tracers.argtypes = [H, dpp, dpp, dpp, cp, ci]
+        lib.beom_download_tracers.argtypes = [H, dpp, dpp, cp, ci]
+        lib.beom_update_tracers.argtypes = [H, cd, cd, cd]
+        lib.beom_multi_set_tracers.argtypes = [MH, ci, cp, ci]
+        lib.beom_multi_upload_tracers.argtypes = [MH, dpp, dpp, dpp, cp, ci]
+        lib.beom_multi_download_tracers.argtypes = [MH, dpp, dpp, cp, ci]
+        for name in ("beom_set_tracers", "beom_upload_tracers", "beom_download_tracers", "beom_update_tracers",
+                     "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers"):
+            getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
                  "beom_multi_stats", "beom_multi_create_ex", "beom_multi_describe", "beom_multi_engine",
@@ -243,7 +255,9 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_window", "beom_multi_create_local", "beom_multi_create_local_ex", "beom_multi_set_open_boundaries_local",
            "beom_multi_upload_local", "beom_multi_download_local",
            "beom_integral_count", "beom_integral_rows", "beom_integral_combine", "beom_integrals",
-           "beom_multi_integrals", "beom_multi_integral_rows_local")
+           "beom_multi_integrals", "beom_multi_integral_rows_local",
+           "beom_set_tracers", "beom_upload_tracers", "beom_download_tracers", "beom_update_tracers",
+           "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers")
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -284,7 +298,50 @@ def scale_integrals(raw: np.ndarray, prm: BeomParams) -> dict:
             "circulation": q[:, 3].copy(), "potential_J": 0.5 * rhon[0] * prm.grav * dl2 * float(raw[4 * nl])}
 
 
-class Engine:
+class _Tracers:
+    """Passive tracers of a handle (beom_set_tracers, include/beom_hip.h): shared by Engine and MultiEngine, whose C calls
+    differ only by name.  Arrays: q, ctrg [ntrc, nlay, ndeg+1] (the layer CONTENT thickness x concentration, and the
+    relaxation concentration), rq [ntrc, nlay, ndeg+1, 2] (the tendency history, as rs_h per tracer)."""
+
+    _trc_prefix = "beom_"
+    ntrc = 0
+
+    def _trc(self, name):
+        return getattr(self.lib, self._trc_prefix + name)
+
+    def set_tracers(self, n: int):
+        """Allocates n tracers (q, rq, ctrg = 0); n = 0 frees them.  Between steps only."""
+        self._check(self._trc("set_tracers")(self.h, int(n), self._err, ERRLEN))
+        self.ntrc = int(n)
+
+    def _trc_array(self, a, tail=()):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        want = (self.ntrc, self.p.nlay, self.p.ndeg + 1) + tail
+        if a.shape != want:
+            raise BeomError("tracer array of shape %s, expected %s" % (a.shape, want))
+        return a
+
+    def upload_tracers(self, q=None, rq=None, ctrg=None):
+        q, rq, ctrg = self._trc_array(q), self._trc_array(rq, (2,)), self._trc_array(ctrg)
+        self._check(self._trc("upload_tracers")(self.h, _dp(q), _dp(rq), _dp(ctrg), self._err, ERRLEN))
+
+    def download_tracers(self) -> dict:
+        n = (self.ntrc, self.p.nlay, self.p.ndeg + 1)
+        out = {"q": np.zeros(n), "rq": np.zeros(n + (2,))}
+        self._check(self._trc("download_tracers")(self.h, _dp(out["q"]), _dp(out["rq"]), self._err, ERRLEN))
+        return out
+
+    def set_concentration(self, c):
+        """Uploads q = c * hlay with the handle's current hlay (multiplied on the host); c broadcasts to [ntrc, nlay, ndeg+1]."""
+        h = self.download(("hlay",))["hlay"]
+        q = np.ascontiguousarray(np.broadcast_to(np.asarray(c, dtype=np.float64), (self.ntrc,) + h.shape) * h[None])
+        self.upload_tracers(q=q)
+        return q
+
+
+class Engine(_Tracers):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
@@ -399,11 +456,17 @@ class Engine:
         self._check(rc)
         return True
 
+    def _rows_buffer(self, nrows: int, tensor):
+        need = (5 + self.ntrc) * self.p.nlay * nrows * (self.p.lm + 1)      # q of every tracer travels behind the five fields
+        if tensor.numel() < need:
+            raise BeomError("row buffer of %d elements, %d needed (%d fields)" % (tensor.numel(), need, 5 + self.ntrc))
+        return C.c_void_p(tensor.data_ptr())
+
     def pack_rows(self, jlo: int, nrows: int, tensor):
-        self._check(self.lib.beom_pack_rows(self.h, jlo, nrows, C.c_void_p(tensor.data_ptr())))
+        self._check(self.lib.beom_pack_rows(self.h, jlo, nrows, self._rows_buffer(nrows, tensor)))
 
     def unpack_rows(self, jlo: int, nrows: int, tensor):
-        self._check(self.lib.beom_unpack_rows(self.h, jlo, nrows, C.c_void_p(tensor.data_ptr())))
+        self._check(self.lib.beom_unpack_rows(self.h, jlo, nrows, self._rows_buffer(nrows, tensor)))
 
     def download_outputs(self, h0r4: Optional[np.ndarray]):
         """(eta, u, v) real*4 records [nlay, ndeg], minmax [nlay, 6], thin_layer — formed on the device."""
@@ -489,6 +552,7 @@ class Engine:
 
     # per-sweep entry points (parity tests)
     def update_h(self, gene, ramp, ctim): self._check(self.lib.beom_update_h(self.h, gene, ramp, ctim))
+    def update_tracers(self, gene, ramp, ctim): self._check(self.lib.beom_update_tracers(self.h, gene, ramp, ctim))
     def update_mont(self, ilay=0): self._check(self.lib.beom_update_mont_rvor_pvor_dive_kine(self.h, ilay))
     def update_viscosity(self, ilay=0): self._check(self.lib.beom_update_viscosity(self.h, ilay))
     def update_u(self, ilay, gene, ramp, ctim): self._check(self.lib.beom_update_u(self.h, ilay, gene, ramp, ctim))
@@ -497,7 +561,7 @@ class Engine:
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine:
+class MultiEngine(_Tracers):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""
@@ -525,6 +589,7 @@ class MultiEngine:
             self.upload(**{k: getattr(f, k) for k in STATE_NAMES})
 
     _check = Engine._check
+    _trc_prefix = "beom_multi_"
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:

@@ -17,6 +17,7 @@
 #include "beom_dev.h"
 #include "beom_kernels.h"
 #include "beom_integrals.h"
+#include "beom_tracers.h"
 #include "beom_dense_host.h"
 
 namespace {
@@ -114,6 +115,11 @@ struct beom_engine {
     double *integ_part = nullptr, *integ_rows = nullptr;
     int32_t *integ_cellmap = nullptr;
     int integ_xper = 0, integ_yper = 0;
+    // passive tracers (beom_set_tracers; beom_tracers.h): the contents and the partner the sweep writes them to, the two
+    // tendency levels (rotated by pointer), the relaxation concentration (allocated by its first upload)
+    int ntrc = 0;
+    double *trc_q = nullptr, *trc_q_alt = nullptr, *trc_rq[2] = {nullptr, nullptr}, *trc_ctrg = nullptr;
+    std::vector<void *> trc_allocs;
     char last_err[512] = {0};
 };
 
@@ -422,6 +428,7 @@ int beom_destroy(beom_handle E) {
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
     for (void *p : E->allocs) (void)hipFree(p);
+    for (void *p : E->trc_allocs) (void)hipFree(p);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -452,10 +459,12 @@ static int copy_out(beom_engine *E, double *dst, const double *src, size_t outer
 }
 
 // AoS history (m, 0:ndeg, nlay) <-> K separate (0:ndeg, nlay) device arrays, layer by layer
-static int hist_in(beom_engine *E, double *const *dev, int K, const double *src, char *errm, int errm_len) {
+// (outer: slices per level; 0 = nlay)
+static int hist_in(beom_engine *E, double *const *dev, int K, const double *src, char *errm, int errm_len, int outer = 0) {
     if (!src) return 0;
     const size_t n1h = (size_t)E->d.ndeg + 1;
-    for (int l = 0; l < E->d.nlay; ++l)
+    if (!outer) outer = E->d.nlay;
+    for (int l = 0; l < outer; ++l)
         for (int m = 0; m < K; ++m) {       // the layer's image is uploaded once, then one scatter per level
             const int rc = slice_to_device<double>(E, dev[m] + (size_t)l * E->d.n1, m == 0 ? src + (size_t)l * n1h * K : nullptr, 1, K, m,
                                                    errm, errm_len);
@@ -463,10 +472,11 @@ static int hist_in(beom_engine *E, double *const *dev, int K, const double *src,
         }
     return 0;
 }
-static int hist_out(beom_engine *E, double *const *dev, int K, double *dst, char *errm, int errm_len) {
+static int hist_out(beom_engine *E, double *const *dev, int K, double *dst, char *errm, int errm_len, int outer = 0) {
     if (!dst) return 0;
     const size_t n1h = (size_t)E->d.ndeg + 1;
-    for (int l = 0; l < E->d.nlay; ++l) {
+    if (!outer) outer = E->d.nlay;
+    for (int l = 0; l < outer; ++l) {
         for (int m = 0; m < K; ++m) slice_gather<double>(E, dev[m] + (size_t)l * E->d.n1, 1, K, m);
         const int rc = slice_to_host<double>(E, dev[0], dst + (size_t)l * n1h * K, 1, K, errm, errm_len);
         if (rc) return rc;
@@ -632,6 +642,16 @@ static void launch_h(beom_engine *E, double gene, double ramp, double ctim, bool
     else LAUNCH_CTX((k_update_h<CellGather, 0>), (k_update_h<CellDense, 0>), nz, E->d, gene, ramp, ctim, 0);
     if (rotate) rot2(E->d.rs);
 }
+// the tracer sweep of a step (beom_tracers.h): all tracers in one launch, in front of the step's update_h
+static void launch_tracers(beom_engine *E, double gene, double ramp, double ctim) {
+    TrcView tv{E->ntrc, E->trc_ctrg ? 1 : 0, E->trc_q, E->trc_q_alt, E->trc_rq[0], E->trc_rq[1], E->trc_ctrg};
+    const int nz = E->d.nlay;
+    if (E->d.has_nudg && E->d.has_tide) LAUNCH_CTX((k_tracers<CellGather, 2>), (k_tracers<CellDense, 2>), nz, E->d, tv, gene, ramp, ctim);
+    else if (E->d.has_nudg) LAUNCH_CTX((k_tracers<CellGather, 1>), (k_tracers<CellDense, 1>), nz, E->d, tv, gene, ramp, ctim);
+    else LAUNCH_CTX((k_tracers<CellGather, 0>), (k_tracers<CellDense, 0>), nz, E->d, tv, gene, ramp, ctim);
+    swp(E->trc_q, E->trc_q_alt);
+    rot2(E->trc_rq);
+}
 template <class CTX>
 static bool launch_mont_all(beom_engine *E) {
     const dim3 g = CTX::grid(E->d, 1), b(BEOM_BLOCK);
@@ -795,6 +815,7 @@ extern "C" {
 
 #define LAUNCHED() (hipGetLastError() == hipSuccess ? 0 : -10)
 int beom_update_h(beom_handle E, double gene, double ramp, double ctim) { NEED(E); launch_h(E, gene, ramp, ctim); return LAUNCHED(); }
+int beom_update_tracers(beom_handle E, double gene, double ramp, double ctim) { NEED(E); if (E->ntrc < 1) return -3; launch_tracers(E, gene, ramp, ctim); return LAUNCHED(); }
 int beom_update_mont_rvor_pvor_dive_kine(beom_handle E, int ilay) { NEED(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_mont(E, ilay); return LAUNCHED(); }
 int beom_update_viscosity(beom_handle E, int ilay) { NEED(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_visc(E, ilay); return LAUNCHED(); }
 int beom_update_u(beom_handle E, int ilay, double gene, double ramp, double ctim) { NEED(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_uv<true>(E, ilay, gene, ramp, ctim); return LAUNCHED(); }
@@ -861,6 +882,7 @@ static bool step_front(beom_engine *E, const StepScalars &s, StepTimer *T) {
     if (s.stress && !E->d.stress_fold) launch_stress(E);
     if (E->lid) launch_lid_fluxes(E, s.first3);
     else if (s.first3) launch_rebuild(E);                          // :2166-2177
+    if (E->ntrc > 0) timed(T, 7, [&] { launch_tracers(E, s.gene, s.ramp, s.ctim); });      // reads hlay, h_u, h_v as update_h is about to
     timed(T, 0, [&] {
         launch_h(E, s.gene, s.ramp, s.ctim);                       // :2181,2259
         if (E->lid) launch_lid_h_epilogue(E);                      // :1648-1700
@@ -906,6 +928,11 @@ static int rows_copy(beom_handle E, int jlo, int nrows, void *dbuf, int jlo2, vo
     const long long total = 5ll * E->d.nlay * nrows * E->d.L;
     hipLaunchKernelGGL((k_rows_copy<PACK>), dim3((unsigned)((total + BEOM_BLOCK - 1) / BEOM_BLOCK), dbuf2 ? 2u : 1u), dim3(BEOM_BLOCK),
                        0, E->stream, E->d, jlo, nrows, (double *)dbuf, jlo2, (double *)dbuf2);
+    if (E->ntrc > 0) {                  // the tracer contents behind the five fields
+        const long long tq = (long long)E->ntrc * E->d.nlay * nrows * E->d.L;
+        hipLaunchKernelGGL((k_rows_copy_q<PACK>), dim3((unsigned)((tq + BEOM_BLOCK - 1) / BEOM_BLOCK), dbuf2 ? 2u : 1u), dim3(BEOM_BLOCK),
+                           0, E->stream, E->d, E->trc_q, E->ntrc, jlo, nrows, (double *)dbuf + total, jlo2, dbuf2 ? (double *)dbuf2 + total : nullptr);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 extern "C" {
@@ -1168,6 +1195,69 @@ int beom_integrals(beom_handle E, double *out, char *errm, int errm_len) {
     return beom_integral_combine(rows.data(), M, count, out);
 }
 
+// ---- passive tracers (beom_tracers.h) -----------------------------------------------------------------------------------
+static void free_tracers(beom_engine *E) {
+    for (void *p : E->trc_allocs) (void)hipFree(p);
+    E->trc_allocs.clear();
+    E->ntrc = 0;
+    E->trc_q = E->trc_q_alt = E->trc_rq[0] = E->trc_rq[1] = E->trc_ctrg = nullptr;
+}
+// a zeroed array of the tracers' shape [ntrc][nlay][n1], cell 1 aligned as dev_alloc's
+static int alloc_tracer_array(beom_engine *E, double **p, char *errm, int errm_len) {
+    void *q = nullptr;
+    const size_t n = (size_t)E->ntrc * E->d.nlay * (size_t)E->d.n1 + 16;
+    HIP_TRY(hipMalloc(&q, n * sizeof(double)));
+    E->trc_allocs.push_back(q);
+    HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(double), E->stream));
+    *p = (double *)q + 15;
+    return 0;
+}
+
+int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (ntrc < 0 || ntrc > BEOM_MAX_TRACERS) { set_err(errm, errm_len, "beom_set_tracers: %d tracers (0..%d)", ntrc, BEOM_MAX_TRACERS); return -3; }
+    if (ntrc > 0 && E->P.variant == 1) { set_err(errm, errm_len, "beom_set_tracers: variant 1 changes the thickness in an epilogue (private_mod3d.f95:1635-1683) that the tracer scheme does not follow"); return -6; }
+    if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    free_tracers(E);
+    if (ntrc == 0) return 0;
+    E->ntrc = ntrc;
+    int rc = 0;
+    for (double **a : {&E->trc_q, &E->trc_q_alt, &E->trc_rq[0], &E->trc_rq[1]})
+        if ((rc = alloc_tracer_array(E, a, errm, errm_len))) { free_tracers(E); return rc; }
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int beom_upload_tracers(beom_handle E, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->ntrc < 1) { set_err(errm, errm_len, "beom_upload_tracers: the handle carries no tracer (beom_set_tracers)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const int outer = E->ntrc * E->d.nlay;
+    int rc;
+    if (ctrg && !E->trc_ctrg && (rc = alloc_tracer_array(E, &E->trc_ctrg, errm, errm_len))) return rc;
+    if ((rc = copy_in(E, E->trc_q, q, (size_t)outer, errm, errm_len))) return rc;
+    if ((rc = copy_in(E, E->trc_ctrg, ctrg, (size_t)outer, errm, errm_len))) return rc;
+    if ((rc = hist_in(E, E->trc_rq, 2, rq, errm, errm_len, outer))) return rc;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int beom_download_tracers(beom_handle E, double *q, double *rq, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->ntrc < 1) { set_err(errm, errm_len, "beom_download_tracers: the handle carries no tracer (beom_set_tracers)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const int outer = E->ntrc * E->d.nlay;
+    int rc;
+    if ((rc = copy_out(E, q, E->trc_q, (size_t)outer, errm, errm_len))) return rc;
+    if ((rc = hist_out(E, E->trc_rq, 2, rq, errm, errm_len, outer))) return rc;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)
 // of nudged open-boundary segments, Fortran storage.  Activates no_gradient_obc after the
 // momentum sweeps of every step when flag_nudging and mcbc < 0.5 (:2201-2204, 2285-2288).
@@ -1230,6 +1320,7 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tile_rows")) return E->dense ? (E->tile4 ? 4 : 8) : 0;
     if (!strcmp(what, "biharm_tiled")) return biharm_tiled(E) ? 1 : 0;
     if (!strcmp(what, "uv_fused")) return E->last_uv_fused ? 1 : 0;
+    if (!strcmp(what, "tracers")) return E->ntrc;
     if (!strcmp(what, "lid_sweeps")) return (int)std::min<long long>(E->lid_sweeps, 2000000000ll);        // Gauss-Seidel sweeps kept, all steps so far
     if (!strcmp(what, "lid_solves")) return (int)std::min<long long>(E->lid_solves, 2000000000ll);
     if (!strcmp(what, "lid_launches")) return (int)std::min<long long>(E->lid_launches, 2000000000ll);

@@ -346,6 +346,7 @@ struct beom_multi {
     bool loopback = false;         // BEOM_XCHG_LOOPBACK: this band receives what it sends (timing rehearsals)
     size_t xbytes = 0;
     long long n_split = 0, n_plain = 0;   // band-steps taken in two phases / in one piece
+    int ntrc = 0;                  // passive tracers carried by every band (beom_multi_set_tracers): q joins the exchange
     // companion frame of a y-periodic ring (lives with band 0): rows 1..kMiniLo, Mr-3..Mr, Mr+1
     beom_handle mini = nullptr;
     int mini_k = -1;               // local index of band 0, or -1 if band 0 is not here
@@ -949,6 +950,83 @@ int beom_multi_download_state(beom_multi_handle M, double *hlay, double *u, doub
         for (int f = 0; f < 13; ++f) {
             if (M->land) paste_v(dst[f], a.a[f], kState[f].outer(nl), kState[f].inner, n1g, n1l, M->band[k].lst, M->gst, j0, n, rows, k == 0);
             else paste(dst[f], a.a[f], kState[f].outer(nl), kState[f].inner, n1g, n1l, L, j0, n, rows, k == 0);
+        }
+    }
+    return 0;
+}
+
+// ---- passive tracers (beom_set_tracers) on the bands: global arrays cut and pasted as the state is; q travels with the
+//      five fields of the exchange (beom_pack_rows packs it behind them), so the buffers grow to 5 + ntrc fields ----
+static int tracers_refused(beom_multi *M, const char *who, char *errm, int errm_len) {
+    if (M->local_mode) { m_err(errm, errm_len, "%s: a handle that holds one band's window does not carry tracers (its exchange is sized at creation)", who); return -6; }
+    if (M->ring) { m_err(errm, errm_len, "%s: bands of a frame periodic in y do not carry tracers (the ring's companion frame has no q); use a single handle", who); return -6; }
+    return 0;
+}
+
+int beom_multi_set_tracers(beom_multi_handle M, int ntrc, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracers: an earlier step failed half way; destroy the handle"); return -30; }
+    if (ntrc < 0 || ntrc > BEOM_MAX_TRACERS) { m_err(errm, errm_len, "beom_multi_set_tracers: %d tracers (0..%d)", ntrc, BEOM_MAX_TRACERS); return -3; }
+    M_RC(tracers_refused(M, "beom_multi_set_tracers", errm, errm_len));
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    for (int k = 0; k < M->n; ++k) M_RC(beom_set_tracers(M->eng[k], ntrc, errm, errm_len));
+    M->ntrc = ntrc;
+    if (M->nb == 1) return 0;
+    // the exchange buffers for 5 + ntrc fields (nothing is in flight after the sync)
+    M->xbytes = (size_t)(kFields + ntrc) * M->P.nlay * kGhost * (M->P.lm + 1) * sizeof(double);
+    for (int k = 0; k < M->n; ++k) {
+        M_HIP(hipSetDevice(M->dev[k]));
+        M->pending[k] = 0;
+        for (auto *v : {&M->send_s, &M->recv_s, &M->send_n, &M->recv_n}) {
+            const bool south = v == &M->send_s || v == &M->recv_s;
+            if ((*v)[k]) { M_HIP(hipFree((*v)[k])); (*v)[k] = nullptr; }
+            if (south ? M->has_s(k) : M->has_n(k)) M_HIP(hipMalloc((void **)&(*v)[k], M->xbytes));
+        }
+    }
+    return 0;
+}
+
+int beom_multi_upload_tracers(beom_multi_handle M, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    M_RC(tracers_refused(M, "beom_multi_upload_tracers", errm, errm_len));
+    if (M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_upload_tracers: the handle carries no tracer (beom_multi_set_tracers)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (M->nb == 1) return beom_upload_tracers(M->eng[0], q, rq, ctrg, errm, errm_len);
+    const size_t outer = (size_t)M->ntrc * M->P.nlay, n1g = M->n1g;
+    const int L = M->P.lm + 1;
+    const double *src[3] = {q, rq, ctrg};
+    const size_t inner[3] = {1, 2, 1};
+    for (int k = 0; k < M->n; ++k) {
+        const std::vector<int> rows = M->band[k].row_list();
+        std::vector<double> a[3];
+        for (int f = 0; f < 3; ++f)
+            a[f] = M->land ? cut_v(src[f], outer, inner[f], n1g, rows, M->gst) : cut(src[f], outer, inner[f], n1g, rows, L);
+        M_RC(beom_upload_tracers(M->eng[k], ptr(a[0]), ptr(a[1]), ptr(a[2]), errm, errm_len));
+    }
+    return 0;
+}
+
+int beom_multi_download_tracers(beom_multi_handle M, double *q, double *rq, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    M_RC(tracers_refused(M, "beom_multi_download_tracers", errm, errm_len));
+    if (M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_download_tracers: the handle carries no tracer (beom_multi_set_tracers)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (M->nb == 1) return beom_download_tracers(M->eng[0], q, rq, errm, errm_len);
+    const size_t outer = (size_t)M->ntrc * M->P.nlay, n1g = M->n1g;
+    const int L = M->P.lm + 1;
+    double *dst[2] = {q, rq};
+    const size_t inner[2] = {1, 2};
+    for (int k = 0; k < M->n; ++k) {
+        const Band &s = M->band[k];
+        const size_t n1l = (size_t)s.n_loc() + 1;
+        std::vector<double> a[2];
+        for (int f = 0; f < 2; ++f) if (dst[f]) a[f].assign(outer * n1l * inner[f], 0.0);
+        M_RC(beom_download_tracers(M->eng[k], ptr(a[0]), ptr(a[1]), errm, errm_len));
+        std::vector<int> rows;
+        for (int j = 0; j < s.nown(); ++j) rows.push_back(s.own0 + j);
+        for (int f = 0; f < 2; ++f) {
+            if (M->land) paste_v(dst[f], a[f], outer, inner[f], n1g, n1l, s.lst, M->gst, s.gs + 1, s.nown(), rows, k == 0);
+            else paste(dst[f], a[f], outer, inner[f], n1g, n1l, L, s.gs + 1, s.nown(), rows, k == 0);
         }
     }
     return 0;

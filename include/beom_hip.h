@@ -40,6 +40,7 @@ extern "C" {
 
 #define BEOM_MAX_LAYERS 16
 #define BEOM_ABI_VERSION 2
+#define BEOM_MAX_TRACERS 8
 
 /* Constants of shared_mod.f95:41-99, passed BY VALUE from the host so that the
  * single-precision literals widened to double (grav = 9.8, beta = 0.281105, ...) keep
@@ -186,7 +187,8 @@ int beom_step_phase(beom_handle h, int tstp, double tres, double dtd8, double dt
                     int n_3d, int phase, char *errm, int errm_len);
 /* Rows [jlo, jlo+nrows) (local, 1-based) of hlay,u,v,h_u,h_v <-> one contiguous DEVICE buffer
  * of 5*nlay*nrows*(lm+1) doubles ([field][layer][row][column]); one launch each, on the
- * handle's stream. */
+ * handle's stream.  A handle that carries ntrc tracers (beom_set_tracers) moves their contents too: the buffer then holds
+ * (5 + ntrc)*nlay*nrows*(lm+1) doubles, q behind the five fields as [tracer][layer][row][column]. */
 int beom_pack_rows(beom_handle h, int jlo, int nrows, void *device_buffer);
 int beom_unpack_rows(beom_handle h, int jlo, int nrows, const void *device_buffer);
 /* two groups of nrows rows (a band's south and north side) <-> two buffers in ONE launch */
@@ -251,7 +253,7 @@ int beom_is_dense(beom_handle h);
 /* Per-kernel device time, measured with HIP events on the handle's stream around every
  * sweep launched by beom_step between start and stop (no host synchronisation in
  * between): ms[0..7] = update_h, update_mont, update_viscosity, update_u, update_v,
- * fused mont+viscosity, fused u+v, (unused) (sums over launches), launches[0..7] = number of
+ * fused mont+viscosity, fused u+v, the tracer sweep (sums over launches), launches[0..7] = number of
  * launches in each class.  Both arrays need 8 entries. */
 int beom_profile_start(beom_handle h);
 int beom_profile_stop(beom_handle h, double *ms, int *launches, char *errm, int errm_len);
@@ -259,6 +261,35 @@ int beom_profile_stop(beom_handle h, double *ms, int *launches, char *errm, int 
 int beom_profile_steps(beom_handle h, int tstp_first, int nsteps,
                        double tres, double dtd8, double dt_r, double rsta, int n_3d,
                        double *ms, int *launches, char *errm, int errm_len);
+
+/* ---- Passive tracers carried by the layer transports (no reference routine; DESIGN.md f-N6).  Per tracer t = 1..ntrc the
+ * handle holds the layer CONTENT q = thickness x concentration and two history levels of its tendency, stored as the other
+ * arrays with the tracer index slowest:
+ *   q(0:ndeg, nlay, ntrc)      -> q[ipnt + (ndeg+1)*((ilay-1) + nlay*(t-1))]             (ctrg alike)
+ *   rq(2, 0:ndeg, nlay, ntrc)  -> rq[(m-1) + 2*(ipnt + (ndeg+1)*((ilay-1) + nlay*(t-1)))]
+ * Index 0 (the land sentinel) is never written and is meant to hold 0.  One update per time step, immediately before that
+ * step's update_h, from the thicknesses and face transports update_h is about to read and with update_h's time scheme
+ * (E, N, W, S = neig(1|3|5|7, p); all FP64, in this order):
+ *   c(x)  = hlay(x,l) > 0 ? q(x,l) / hlay(x,l) : +0.0                 wet(x) = hlay(x,l) > 0
+ *   Fu(p) = h_u(p,l) * cf,  (a,b) = h_u(p,l) > 0 ? (W,p) : (p,W),  cf = wet(a) ? c(a) : c(b)      (Fv alike with h_v and S)
+ *   src   = hdot present ? hdot(p,l) * (hdot(p,l) > 0 ? ctrg(p,l) : c(p)) : +0.0
+ *   r3    = ((Fu(p) - Fu(E)) * i_dl + (Fv(p) - Fv(N)) * i_dl + src) * mk_n(p)
+ *   qh    = q + ((1.5+beta)*r3 - (0.5+2*beta)*rq(2) + beta*rq(1)) * dt * gene + r3 * dt * (1-gene)
+ *   q_new = (ctrg(p,l) * hfor) * nudg(p,1) + (1 - nudg(p,1)) * qh,   hfor = update_h's target thickness (fnud + tide)
+ *   rq(1) <- rq(2);  rq(2) <- r3
+ * First-order upstream with the no-gradient rule at an empty upwind cell: conservative, consistent with the continuity
+ * equation by construction (a tracer of concentration 1 with ctrg = 1 IS hlay, bit for bit), NOT monotone — small negative
+ * concentrations occur.  Water that a sponge or hdot > 0 brings in carries the relaxation concentration ctrg (+0.0 until
+ * uploaded); withdrawal carries the local concentration.
+ * beom_set_tracers allocates (q, rq, ctrg = 0; ntrc = 0 frees; between steps only) and refuses (-6) the configurations whose
+ * thickness is changed by something the scheme does not follow: variant = 1 and rgld = 1.  beom_step and beom_step_phase
+ * (phase 1) then run the tracer sweep; beom_update_tracers is the per-sweep entry (as beom_update_h; beom_update_h itself
+ * does not move tracers).  beom_info(h, "tracers") returns the count. */
+int beom_set_tracers(beom_handle h, int ntrc, char *errm, int errm_len);
+/* any pointer may be NULL = keep */
+int beom_upload_tracers(beom_handle h, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len);
+int beom_download_tracers(beom_handle h, double *q, double *rq, char *errm, int errm_len);
+int beom_update_tracers(beom_handle h, double gene, double ramp, double ctim);
 
 /* ---- Conservation integrals of the state as it stands between two steps (no reference routine: the reference's test
  * case 3 forms them from the output files, testcases/conservation.m:116-211).  All FP64, raw sums over the frame:
@@ -415,6 +446,15 @@ int beom_multi_upload_local(beom_multi_handle h, const beom_state *window, const
                             char *errm, int errm_len);
 int beom_multi_download_local(beom_multi_handle h, beom_state *window, beom_state *orphan,
                               char *errm, int errm_len);
+
+/* Passive tracers on a frame cut into bands (see beom_set_tracers): GLOBAL arrays, handles created from the global arrays
+ * (beom_multi_create[_ex]) of a frame not periodic in y.  q travels with hlay, u, v, h_u, h_v in the one exchange of a step
+ * (the sweep reaches one row; the exchange buffers are reallocated here); cut steps stay cut.  Refused with -6: a frame
+ * periodic in y (the ring's companion frame does not carry q yet) and handles that hold one band's window
+ * (beom_multi_create_local*: their shared-memory segment and RCCL counts are sized at creation). */
+int beom_multi_set_tracers(beom_multi_handle m, int ntrc, char *errm, int errm_len);
+int beom_multi_upload_tracers(beom_multi_handle m, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len);
+int beom_multi_download_tracers(beom_multi_handle m, double *q, double *rq, char *errm, int errm_len);
 
 /* Conservation integrals (see beom_integrals).  Global-array handles: every band forms the row sums of its OWNED rows; a
  * ring's row mm+1 duplicates row 1 and is all +0, so the companion frame is not asked; combined in global row order. */

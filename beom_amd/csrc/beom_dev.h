@@ -91,6 +91,11 @@ struct DevView {
     int stress_fold, has_bot, has_top;
     const double *taus_cells;
     double rho_top, rho_bot;
+    // kept Montgomery levels of the three steps before the one mont holds (mo0 oldest .. mo2 newest; null unless the handle
+    // keeps them): the engine rotates mont through four buffers once per step, and the history-from-Montgomery form of the
+    // fused u+v sweep re-forms the Adams-Bashforth history dmx / dmy from them instead of reading the six arrays.
+    // (scalars, never an array: an indexed kernel argument goes to scratch)
+    double *mo0, *mo1, *mo2;
 };
 
 // ---- tiles of the selected strips --------------------------------------------------------

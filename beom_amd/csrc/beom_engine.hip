@@ -110,6 +110,13 @@ struct beom_engine {
     bool profile_rotate = false;       // option "profile_rotate"
     bool split_prod = false;           // split steps: part 1's Montgomery sweep left the viscous products for parts 2 and 3
     bool tile4 = false;                // the tiled sweeps run the 64 x 4 geometry (frames of one or two rounds of workgroups)
+    // History from Montgomery (option "mont_history", default on): d.mont rotates through four buffers, once
+    // per step (rotate_mont), and the fused u+v sweep re-forms dmx / dmy from the three kept levels instead of reading them.
+    bool mont_history = true;
+    bool mont_keep = false;            // the handle has the three extra buffers (whole dense frame, no lid, g_fb != 0, fusable)
+    int mont_levels_valid = 0;         // consecutive steps, up to the last one, whose Montgomery potential the buffers hold
+    bool hist_stale = false;           // dmx, dmy lag behind: steps of the new form have left them alone (hist_sync)
+    bool last_mont_hist = false;       // the last step ran the new form (beom_info "mont_history")
     // conservation integrals (beom_integral_rows): chunk sums and row sums of up to M rows, allocated on the first call; on
     // the table path also the packed cell of every (i, j) and the wraps read off neig
     double *integ_part = nullptr, *integ_rows = nullptr;
@@ -122,6 +129,8 @@ struct beom_engine {
     std::vector<void *> trc_allocs;
     char last_err[512] = {0};
 };
+static int hist_sync(beom_engine *E);
+static int leave_mont_history(beom_engine *E);
 
 namespace {
 
@@ -335,6 +344,10 @@ int alloc_state(beom_engine *E, char *errm, int errm_len) {
     al({&d.v_cc, &d.v_ll}, n);
     al({&d.tt3d, &d.tb3d, &d.tu3d}, 2 * n);
     al({&d.pcd, &d.qlr, &d.mont, &d.rvor, &d.pvor, &d.dive, &d.d2hx, &d.d2hy}, n);
+    // kept Montgomery levels: handles whose steps can run the fused pair with the multistep term (zeroed like mont: slot 0
+    // and every slot that is no cell hold +0 in all four buffers and are never written)
+    E->mont_keep = E->dense && !E->lid && !d.slab && E->P.g_fb != 0.0 && d.nlay <= 8 && !(E->P.svis > 0.0);
+    if (E->mont_keep) al({&d.mo0, &d.mo1, &d.mo2}, n);
     if (E->P.svis > 0.0) al({&d.delu, &d.delv, &d.uu4, &d.vv4}, n);
     if (E->lid) al({&d.pi_s, &d.pi_rhs, &d.pi_prev}, (size_t)d.n1);
     if (rc) return rc;
@@ -493,6 +506,7 @@ int beom_upload_state(beom_handle E, const double *hlay, const double *u, const 
     DevView &d = E->d;
     const size_t nl = (size_t)d.nlay, n = ((size_t)d.ndeg + 1) * nl;
     int rc;
+    if ((rc = leave_mont_history(E))) { set_err(errm, errm_len, "beom_upload_state: the history arrays could not be brought up to date"); return rc; }
     if ((rc = copy_in(E, d.hlay, hlay, nl, errm, errm_len))) return rc;
     if ((rc = copy_in(E, d.u, u, nl, errm, errm_len))) return rc;
     if ((rc = copy_in(E, d.v, v, nl, errm, errm_len))) return rc;
@@ -527,6 +541,7 @@ int beom_download_state(beom_handle E, double *hlay, double *u, double *v, doubl
     DevView &d = E->d;
     const size_t nl = (size_t)d.nlay;
     int rc;
+    if ((rc = hist_sync(E))) { set_err(errm, errm_len, "beom_download_state: the history arrays could not be brought up to date"); return rc; }
     if ((rc = copy_out(E, hlay, d.hlay, nl, errm, errm_len))) return rc;
     if ((rc = copy_out(E, u, d.u, nl, errm, errm_len))) return rc;
     if ((rc = copy_out(E, v, d.v, nl, errm, errm_len))) return rc;
@@ -621,6 +636,30 @@ static inline void rot3(double *(&a)[4]) { double *t = a[0]; a[0] = a[1]; a[1] =
 static inline void rot4(double *(&a)[4]) { double *t = a[0]; a[0] = a[1]; a[1] = a[2]; a[2] = a[3]; a[3] = t; }
 static inline void swp(double *&a, double *&b) { double *t = a; a = b; b = t; }
 
+// ---- history from Montgomery: the state machine ---------------------------------------------------------------------
+// d.mont of the step about to run <- the oldest buffer; the three others are the levels of the three steps before it
+static void rotate_mont(beom_engine *E) {
+    if (!E->mont_keep) return;
+    DevView &d = E->d;
+    double *t = d.mo0; d.mo0 = d.mo1; d.mo1 = d.mo2; d.mo2 = d.mont; d.mont = t;
+}
+// dmx[0..2], dmy[0..2] brought up to date after steps of the new form (k_hist_from_mont: 3 words read, 6 written per
+// cell-layer).  Between steps only: d.mont is the last step's.  The kept levels stay valid.
+static int hist_sync(beom_engine *E) {
+    if (!E->hist_stale) return 0;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    hipLaunchKernelGGL(k_hist_from_mont, CellDense::grid(E->d, E->d.nlay), dim3(BEOM_BLOCK), 0, E->stream, E->d);
+    E->hist_stale = false;
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+// everything that works on the history arrays or writes d.mont outside beom_step: arrays first, and the levels no longer
+// line up with the history afterwards
+static int leave_mont_history(beom_engine *E) {
+    const int rc = hist_sync(E);
+    E->mont_levels_valid = 0;
+    return rc;
+}
+
 // LAUNCH(kernel-template-name, extra template args..., nz, args...) picks the cell context.
 #define LAUNCH_CTX(KERNEL_G, KERNEL_D, nz, ...)                                                            \
     do {                                                                                                  \
@@ -704,15 +743,18 @@ static bool raw_mont_visc(beom_engine *E, bool leith) {
     }
 }
 template <int Q>
-static void raw_uv_fused(beom_engine *E, bool first_x, bool prod, bool zv, double gene, double ramp, double ctim) {
+static void raw_uv_fused(beom_engine *E, bool first_x, bool prod, bool zv, bool hm, double gene, double ramp, double ctim) {
     const dim3 g = uv_fused_grid<Q>(E->d), b(TileGeom<Q>::BLOCK);
     DevView &d = E->d;
 #define UV_GO(kern, fx, pr, z) hipLaunchKernelGGL((kern<Q, fx, pr, z>), g, b, 0, E->stream, d, gene, ramp, ctim)
 #define UV_PICK(fx) do { \
-        if (d.stress_fold) { if (zv) UV_GO(k_uv_fused_sf, fx, true, true); else if (prod) UV_GO(k_uv_fused_sf, fx, true, false); else UV_GO(k_uv_fused_sf, fx, false, false); } \
+        if (hm) { if (zv) hipLaunchKernelGGL((k_uv_fused<Q, fx, true, true, true>), g, b, 0, E->stream, d, gene, ramp, ctim); \
+                  else hipLaunchKernelGGL((k_uv_fused<Q, fx, true, false, true>), g, b, 0, E->stream, d, gene, ramp, ctim); } \
+        else if (d.stress_fold) { if (zv) UV_GO(k_uv_fused_sf, fx, true, true); else if (prod) UV_GO(k_uv_fused_sf, fx, true, false); else UV_GO(k_uv_fused_sf, fx, false, false); } \
         else { if (zv) UV_GO(k_uv_fused, fx, true, true); else if (prod) UV_GO(k_uv_fused, fx, true, false); else UV_GO(k_uv_fused, fx, false, false); } \
     } while (0)
-    // (stress_fold: distribute_stress formed inside the sweep — its own instantiations, so that the unforced ones stay lean)
+    // (stress_fold: distribute_stress formed inside the sweep — its own instantiations, so that the unforced ones stay lean;
+    // hm: the history-from-Montgomery form, instantiated for the staged k_uv_fused only — mont_hist_step is its gate)
     if (first_x) UV_PICK(true); else UV_PICK(false);
 #undef UV_PICK
 #undef UV_GO
@@ -728,18 +770,21 @@ static bool launch_mont_visc(beom_engine *E, bool uv_fused_follows, bool leith, 
     return E->tile4 ? raw_mont_visc<1>(E, leith) : raw_mont_visc<2>(E, leith);
 }
 // fused U+V sweep (dense frames): first_x = update_u first (even tstp)
-static void uv_fused_swap(beom_engine *E, bool first_x) {
+static void uv_fused_swap(beom_engine *E, bool first_x, bool hm = false) {
     DevView &d = E->d;
     swp(d.u, d.u_alt); swp(d.v, d.v_alt);                 // both velocities are written out of place
-    if (first_x) { rot4(d.dmx); swp(d.h_v, d.hv_alt); rot3(d.dmy); }
-    else         { rot4(d.dmy); swp(d.h_u, d.hu_alt); rot3(d.dmx); }
+    if (first_x) swp(d.h_v, d.hv_alt); else swp(d.h_u, d.hu_alt);
+    if (hm) { E->hist_stale = true; return; }             // the history arrays were not touched: they lag from here on
+    if (first_x) { rot4(d.dmx); rot3(d.dmy); }
+    else         { rot4(d.dmy); rot3(d.dmx); }
 }
+// hm: the history-from-Montgomery form (needs prod; the caller has checked mont_hist_step)
 static void launch_uv_fused(beom_engine *E, bool first_x, bool prod, double gene, double ramp, double ctim,
-                            bool swap = true) {
+                            bool swap = true, bool hm = false) {
     const bool zv = prod && E->d.zero_visc;       // set by launch_mont_visc of this step
-    if (E->tile4) raw_uv_fused<1>(E, first_x, prod, zv, gene, ramp, ctim);
-    else raw_uv_fused<2>(E, first_x, prod, zv, gene, ramp, ctim);
-    if (swap) uv_fused_swap(E, first_x);
+    if (E->tile4) raw_uv_fused<1>(E, first_x, prod, zv, hm, gene, ramp, ctim);
+    else raw_uv_fused<2>(E, first_x, prod, zv, hm, gene, ramp, ctim);
+    if (swap) uv_fused_swap(E, first_x, hm);
 }
 static bool can_fuse(const beom_engine *E, int n_3d, bool first3) {
     // either every step refreshes the viscosity (dvis > 1e-3 and n_3d = 1, :2268) — Montgomery + Leith
@@ -814,14 +859,17 @@ extern "C" {
 #define NEED(E) do { if (!(E)) return -1; if (hipSetDevice((E)->device) != hipSuccess) return -9; } while (0)
 
 #define LAUNCHED() (hipGetLastError() == hipSuccess ? 0 : -10)
-int beom_update_h(beom_handle E, double gene, double ramp, double ctim) { NEED(E); launch_h(E, gene, ramp, ctim); return LAUNCHED(); }
-int beom_update_tracers(beom_handle E, double gene, double ramp, double ctim) { NEED(E); if (E->ntrc < 1) return -3; launch_tracers(E, gene, ramp, ctim); return LAUNCHED(); }
-int beom_update_mont_rvor_pvor_dive_kine(beom_handle E, int ilay) { NEED(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_mont(E, ilay); return LAUNCHED(); }
-int beom_update_viscosity(beom_handle E, int ilay) { NEED(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_visc(E, ilay); return LAUNCHED(); }
-int beom_update_u(beom_handle E, int ilay, double gene, double ramp, double ctim) { NEED(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_uv<true>(E, ilay, gene, ramp, ctim); return LAUNCHED(); }
-int beom_update_v(beom_handle E, int ilay, double gene, double ramp, double ctim) { NEED(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_uv<false>(E, ilay, gene, ramp, ctim); return LAUNCHED(); }
-int beom_rebuild_fluxes(beom_handle E) { NEED(E); launch_rebuild(E); return LAUNCHED(); }
-int beom_distribute_stress(beom_handle E) { NEED(E); launch_stress(E); return LAUNCHED(); }
+// (a sweep called on its own works on the history arrays and breaks the sequence of kept Montgomery levels: NEED_ARRAYS)
+#define NEED_ARRAYS(E) do { NEED(E); if (leave_mont_history(E)) return -10; } while (0)
+int beom_update_h(beom_handle E, double gene, double ramp, double ctim) { NEED_ARRAYS(E); launch_h(E, gene, ramp, ctim); return LAUNCHED(); }
+int beom_update_tracers(beom_handle E, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (E->ntrc < 1) return -3; launch_tracers(E, gene, ramp, ctim); return LAUNCHED(); }
+int beom_update_mont_rvor_pvor_dive_kine(beom_handle E, int ilay) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_mont(E, ilay); return LAUNCHED(); }
+int beom_update_viscosity(beom_handle E, int ilay) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_visc(E, ilay); return LAUNCHED(); }
+int beom_update_u(beom_handle E, int ilay, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_uv<true>(E, ilay, gene, ramp, ctim); return LAUNCHED(); }
+int beom_update_v(beom_handle E, int ilay, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_uv<false>(E, ilay, gene, ramp, ctim); return LAUNCHED(); }
+int beom_rebuild_fluxes(beom_handle E) { NEED_ARRAYS(E); launch_rebuild(E); return LAUNCHED(); }
+int beom_distribute_stress(beom_handle E) { NEED_ARRAYS(E); launch_stress(E); return LAUNCHED(); }
+#undef NEED_ARRAYS
 #undef LAUNCHED
 
 }  // extern "C"
@@ -897,12 +945,26 @@ static bool step_front(beom_engine *E, const StepScalars &s, StepTimer *T) {
     return prod;
 }
 
+// Does this step run the history-from-Montgomery form of the fused u+v sweep?  The option is on; the handle keeps the
+// levels (a whole dense frame, no lid); the step takes launch_uv_fused with the products staged (s.fused: k_mont_visc runs
+// for every nlay <= 8, which mont_keep implies) and the multistep term live; its stress does not fold (k_uv_fused_sf stays
+// on the arrays); and the buffers hold the three steps before this one.
+static bool mont_hist_step(const beom_engine *E, const StepScalars &s) {
+    return E->mont_history && E->mont_keep && s.fused && s.fused_uv && s.gene != 0.0 && !stress_folds(E, s) &&
+           E->mont_levels_valid >= 3;
+}
+
 static void one_step(beom_engine *E, int tstp, const StepScalars &s) {
+    const bool hm = mont_hist_step(E, s);
+    if (!hm) (void)hist_sync(E);                                   // a step on the arrays: bring them up to date first
+    rotate_mont(E);                                                // the one place d.mont moves to its next buffer
     StepTimer *T = begin_step(E, tstp, s);
     const bool prod = step_front(E, s, T);
     const bool u_first = tstp % 2 == 0;                            // :2193-2199,2276-2282
     E->last_uv_fused = s.fused_uv;
-    if (s.fused_uv) timed(T, 6, [&] { launch_uv_fused(E, u_first, prod, s.gene, s.ramp, s.ctim); });
+    E->last_mont_hist = hm;
+    if (E->mont_keep) E->mont_levels_valid = std::min(E->mont_levels_valid + 1, 3);      // this step's mont is in its buffer
+    if (s.fused_uv) timed(T, 6, [&] { launch_uv_fused(E, u_first, prod, s.gene, s.ramp, s.ctim, true, hm && prod); });
     else
         for (const bool x : {u_first, !u_first})
             timed(T, x ? 3 : 4, [&] {
@@ -1022,8 +1084,10 @@ int beom_step_phase(beom_handle E, int tstp, double tres, double dtd8, double dt
     }
     const int M = d.M;
     const bool u_first = tstp % 2 == 0;
+    if (leave_mont_history(E)) { set_err(errm, errm_len, "beom_step_phase: the history arrays could not be brought up to date"); return -10; }
     StepTimer *T = begin_step(E, tstp, s);
     E->last_uv_fused = true;
+    E->last_mont_hist = false;
     if (phase == 1) {
         E->split_prod = step_front(E, s, T);      // (s.fused_uv holds: parts 2 and 3 are the fused u+v sweep it prepares)
     } else if (phase == 2) {
@@ -1320,6 +1384,7 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tile_rows")) return E->dense ? (E->tile4 ? 4 : 8) : 0;
     if (!strcmp(what, "biharm_tiled")) return biharm_tiled(E) ? 1 : 0;
     if (!strcmp(what, "uv_fused")) return E->last_uv_fused ? 1 : 0;
+    if (!strcmp(what, "mont_history")) return E->last_mont_hist ? 1 : 0;
     if (!strcmp(what, "tracers")) return E->ntrc;
     if (!strcmp(what, "lid_sweeps")) return (int)std::min<long long>(E->lid_sweeps, 2000000000ll);        // Gauss-Seidel sweeps kept, all steps so far
     if (!strcmp(what, "lid_solves")) return (int)std::min<long long>(E->lid_solves, 2000000000ll);
@@ -1330,6 +1395,7 @@ int beom_info(beom_handle E, const char *what) {
 
 int beom_set_option(beom_handle E, const char *name, int value) {
     if (!E || !name) return -1;
+    if (!strncmp(name, "fuse", 4) && hist_sync(E)) return -10;      // fuse, fuse_mont_visc, fuse_uv: the other paths read the arrays
     if (!strcmp(name, "fuse")) { E->fuse = value != 0; E->fuse_uv = value != 0; }
     else if (!strcmp(name, "fuse_mont_visc")) E->fuse = value != 0 && !E->lid;      // (a lid handle keeps the separate sweeps)
     else if (!strcmp(name, "fuse_uv")) E->fuse_uv = value != 0 && !E->lid;
@@ -1339,6 +1405,7 @@ int beom_set_option(beom_handle E, const char *name, int value) {
     else if (!strcmp(name, "profile_rotate")) E->profile_rotate = value != 0;
     else if (!strcmp(name, "lean_d2h")) E->lean_d2h = value != 0;
     else if (!strcmp(name, "lean_visc")) E->lean_visc = value != 0;
+    else if (!strcmp(name, "mont_history")) E->mont_history = value != 0;
     else return -3;
     return 0;
 }

@@ -650,8 +650,16 @@ __device__ __forceinline__ double fold_drag(const C &c, const DevView &d, int il
     return tau * 0.5 * (1.0 + 1.0);
 }
 
+// The history level update_u / update_v stored in the step whose Montgomery potential was m_s at the cell and m_b at its b
+// neighbour (u: W, v: S): dmd4 of that step (below), formed again from the kept level
+__device__ __forceinline__ double hist_from_mont(const DevView &d, double m_b, double m_s, double mask) {
+    return (m_b - m_s) * d.i_dl * d.grav * mask;
+}
+
 // SF (stress fold): distribute_stress formed here (a template switch: the unforced sweeps must not carry its registers)
-template <bool XDIR, bool PROD, bool STORE, bool SF, class C, class SH>
+// HM (history from Montgomery): the three history levels are re-formed from the kept Montgomery levels d.mo0..2 (pre[5..7]
+// hold them already formed, or the cell and cb are read here); the history arrays are neither read nor written
+template <bool XDIR, bool PROD, bool STORE, bool SF, bool HM, class C, class SH>
 __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay, double gene, double ramp,
                                           double ctim, int copy_hist, const UVio &io,
                                           double q0, double qb, double qa, double qd, const SH &sh,
@@ -705,7 +713,18 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
     rhsi = rhsi + (d.has_bodf ? d.bodf[(ilay - 1) + d.nlay * (ID - 1)] : 0.0);   // + (+0) is not a no-op for -0
     // gene = 0 (steps 1-3, g_fb = 0): the term is (finite)*0 = +-0 and only matters for the sign of
     // an exactly-zero rhsi; fetch the history on those (rare) lanes only.
-    if (gene != 0.0 || rhsi == 0.0) {
+    if (HM) {
+        if (gene != 0.0 || rhsi == 0.0) {
+            double h0, h1, h2;                     // oldest .. newest
+            if (pre) { h0 = pre[5]; h1 = pre[6]; h2 = pre[7]; }      // (formed whatever gene is)
+            else {
+                h0 = hist_from_mont(d, LL(d.mo0, cb, ilay), LL(d.mo0, ipnt, ilay), mask);
+                h1 = hist_from_mont(d, LL(d.mo1, cb, ilay), LL(d.mo1, ipnt, ilay), mask);
+                h2 = hist_from_mont(d, LL(d.mo2, cb, ilay), LL(d.mo2, ipnt, ilay), mask);
+            }
+            rhsi = rhsi + (d.del1 * dmd4 + d.del2 * h2 + d.gamm * h1 + d.epsi * h0) * gene;
+        }
+    } else if (gene != 0.0 || rhsi == 0.0) {
         const bool p = pre && gene != 0.0;
         rhsi = rhsi + (d.del1 * dmd4 + d.del2 * (p ? pre[7] : LL(io.dm2, ipnt, ilay)) + d.gamm * (p ? pre[6] : LL(io.dm1, ipnt, ilay))
                        + d.epsi * (p ? pre[5] : LL(io.dm0, ipnt, ilay))) * gene;
@@ -775,7 +794,8 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
     if (STORE && do_store) {
         LL(io.vel_out, ipnt, ilay) = vold;
         if (d.rgld < 0.5) LL(io.hp_out, ipnt, ilay) = hnew;          // (:1491, :1577: with a lid the transports are rebuilt after the sweeps)
-        if (copy_hist) {                       // single-layer entry points: shift like the reference
+        if (HM) {                              // the kept Montgomery levels stand for the history
+        } else if (copy_hist) {                // single-layer entry points: shift like the reference
             const double m2 = LL(io.dm1, ipnt, ilay), m3 = LL(io.dm2, ipnt, ilay);
             LL(const_cast<double *>(io.dm0), ipnt, ilay) = m2;
             LL(const_cast<double *>(io.dm1), ipnt, ilay) = m3;
@@ -799,7 +819,7 @@ __device__ __forceinline__ void body_update_uv(const C &c, const DevView &d, int
     double *const *dm = XDIR ? d.dmx : d.dmy;
     const UVio io{XDIR ? d.u : d.v, XDIR ? d.u : d.v, XDIR ? d.h_u : d.h_v, dm[0], dm[1], dm[2], dm[0]};
     const ShGlobal sh{d, ipnt, cb, ca, ilay};
-    uv_core<XDIR, PROD, true, false>(c, d, ilay, gene, ramp, ctim, copy_hist, io,
+    uv_core<XDIR, PROD, true, false, false>(c, d, ilay, gene, ramp, ctim, copy_hist, io,
                               LL(hq, ipnt, ilay), LL(hq, cb, ilay), LL(hq, ca, ilay), LL(hq, cd, ilay), sh);
 }
 template <class CTX, bool XDIR, bool PROD = false>
@@ -824,7 +844,7 @@ __global__ __launch_bounds__(BEOM_BLOCK) void k_update_uv(DevView d, int ilay_on
 //      place as well (the first update of other workgroups still reads the old one).
 //      Algorithmic traffic: 22 words per cell-layer instead of 14 + 14.
 // first update at one cell; SH = where its shared fields come from
-template <bool FIRST_X, bool PROD, bool STORE, bool INT, bool SF, class SH>
+template <bool FIRST_X, bool PROD, bool STORE, bool INT, bool SF, bool HM = false, class SH>
 __device__ __forceinline__ double uv_first_eval(const DevView &d, const CellDenseT<INT> &c, int ilay, double gene,
                                                 double ramp, double ctim, const SH &sh, bool do_store = true,
                                                 const double *pre = nullptr, bool zv = false) {
@@ -835,16 +855,16 @@ __device__ __forceinline__ double uv_first_eval(const DevView &d, const CellDens
     const double *hq = FIRST_X ? d.h_v : d.h_u;
     double *const *dm = FIRST_X ? d.dmx : d.dmy;
     const UVio io{FIRST_X ? d.u : d.v, FIRST_X ? d.u_alt : d.v_alt, FIRST_X ? d.h_u : d.h_v,
-                  dm[0], dm[1], dm[2], dm[3]};
-    if (pre) return uv_core<FIRST_X, PROD, STORE, SF>(c, d, ilay, gene, ramp, ctim, 0, io, pre[1], pre[2], pre[3], pre[4],
-                                                  sh, do_store, pre, zv);
-    return uv_core<FIRST_X, PROD, STORE, SF>(c, d, ilay, gene, ramp, ctim, 0, io, LL(hq, ipnt, ilay),
-                                         LL(hq, cb, ilay), LL(hq, ca, ilay), LL(hq, cd, ilay), sh, do_store);
+                  HM ? nullptr : dm[0], HM ? nullptr : dm[1], HM ? nullptr : dm[2], HM ? nullptr : dm[3]};
+    if (pre) return uv_core<FIRST_X, PROD, STORE, SF, HM>(c, d, ilay, gene, ramp, ctim, 0, io, pre[1], pre[2], pre[3], pre[4],
+                                                      sh, do_store, pre, zv);
+    return uv_core<FIRST_X, PROD, STORE, SF, HM>(c, d, ilay, gene, ramp, ctim, 0, io, LL(hq, ipnt, ilay),
+                                             LL(hq, cb, ilay), LL(hq, ca, ilay), LL(hq, cd, ilay), sh, do_store);
 }
 
 // boundary workgroups: new first-component transport seen by a NEIGHBOUR lookup of the local
 // target (a, b) — wraps / sentinel applied, everything from global memory
-template <bool FIRST_X, bool PROD, bool SF>
+template <bool FIRST_X, bool PROD, bool SF, bool HM = false>
 __device__ __forceinline__ double uv_first_halo(const DevView &d, int a, int b, int ilay, double gene,
                                                 double ramp, double ctim) {
     if (d.xper) { if (a == 0) a = d.L - 1; else if (a == d.L) a = 1; }
@@ -856,7 +876,7 @@ __device__ __forceinline__ double uv_first_halo(const DevView &d, int a, int b, 
     const int cb = FIRST_X ? h.template nb<5>() : h.template nb<7>();
     const int ca = FIRST_X ? h.template nb<3>() : h.template nb<1>();
     const ShGlobal sh{d, h.ipnt, cb, ca, ilay};
-    return uv_first_eval<FIRST_X, PROD, false, false, SF>(d, h, ilay, gene, ramp, ctim, sh);
+    return uv_first_eval<FIRST_X, PROD, false, false, SF, HM>(d, h, ilay, gene, ramp, ctim, sh);
 }
 
 // Interior workgroups of the production pair (PROD, tile and ring strictly inside the wet interior):
@@ -864,7 +884,7 @@ __device__ __forceinline__ double uv_first_halo(const DevView &d, int a, int b, 
 // included, read them there.  All loads of a phase are issued before the first use — the
 // compiler keeps a load next to its use and would otherwise chain ~25 memory round trips
 // per workgroup (stage loop, then every cell's velocity / transports / history one after the other).
-template <bool FIRST_X>
+template <bool FIRST_X, bool HM = false>
 __device__ __forceinline__ void uv_pre_load(const DevView &d, const CellDenseT<true> &c, int ilay, double gene,
                                             bool with_q, double (&pre)[8]) {
     const int ipnt = c.ipnt;
@@ -877,10 +897,38 @@ __device__ __forceinline__ void uv_pre_load(const DevView &d, const CellDenseT<t
         const int cd = FIRST_X ? c.template nb<4>() : c.template nb<8>();
         pre[1] = LL(hq, ipnt, ilay); pre[2] = LL(hq, cb, ilay); pre[3] = LL(hq, ca, ilay); pre[4] = LL(hq, cd, ilay);
     }
-    if (gene != 0.0) { pre[5] = LL(dm[0], ipnt, ilay); pre[6] = LL(dm[1], ipnt, ilay); pre[7] = LL(dm[2], ipnt, ilay); }
+    if (!HM && gene != 0.0) { pre[5] = LL(dm[0], ipnt, ilay); pre[6] = LL(dm[1], ipnt, ilay); pre[7] = LL(dm[2], ipnt, ilay); }
+}
+// HM: the three kept Montgomery levels (oldest first) at slot ip of layer ilay
+__device__ __forceinline__ void hm_load(const DevView &d, int ip, int ilay, double (&m)[3]) {
+    m[0] = LL(d.mo0, ip, ilay); m[1] = LL(d.mo1, ip, ilay); m[2] = LL(d.mo2, ip, ilay);
+}
+// ... and the history levels pre[5..7] from the levels at a cell and at its b neighbour (interior cells: the mask is 1)
+__device__ __forceinline__ void hm_form(const DevView &d, const double (&ms)[3], const double (&mb)[3], double (&pre)[8]) {
+    pre[5] = hist_from_mont(d, mb[0], ms[0], 1.0); pre[6] = hist_from_mont(d, mb[1], ms[1], 1.0);
+    pre[7] = hist_from_mont(d, mb[2], ms[2], 1.0);
+}
+// ... for the u update of a tile cell: lane l - 1 holds the W neighbour's levels (the wave is a row of 64 cells), lane 0 finds
+// the column x0 - 1 in the side table col[level][tile row]
+template <int TY>
+__device__ __forceinline__ void hm_form_w(const DevView &d, const double (&ms)[3], const double (*col)[TY], int row, int lx,
+                                          double (&pre)[8]) {
+    double mw[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        mw[k] = __shfl_up(ms[k], 1, 64);
+        if (lx == 0) mw[k] = col[k][row];
+    }
+    hm_form(d, ms, mw, pre);
+}
+// the side table of the history-from-Montgomery form (a function-local array: only the kernels that call this carry it)
+template <int TY>
+__device__ __forceinline__ double (*hm_side_table())[TY] {
+    __shared__ double s_w[3][TY];
+    return s_w;
 }
 
-template <int Q, bool FIRST_X, bool ZV, bool SF>
+template <int Q, bool FIRST_X, bool ZV, bool SF, bool HM>
 __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, int y0, int ilay, double gene,
                                                      double ramp, double ctim, double (*s_h)[TileGeom<Q>::LDX], UVstage<Q> *s_f,
                                                      double (*s_hl)[TileGeom<Q>::HLDX]) {
@@ -922,7 +970,7 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
         const int j = y0 + wy + G::WAVES * q;
         wr[q] = row_selected(d, j);                  // cells outside the strips are evaluated, not stored
         c[q].set_cell(d, i, j);
-        uv_pre_load<FIRST_X>(d, c[q], ilay, gene, true, pre[q]);
+        uv_pre_load<FIRST_X, HM>(d, c[q], ilay, gene, true, pre[q]);
     }
     // ring cells of the first update: one row (65) + one column (TY); other threads load their own cell again
     int rr1 = -1, cc1 = -1;
@@ -933,7 +981,23 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
     CellDenseT<true> hc;
     hc.set_cell(d, ra, rb);
     double preR[8];
-    uv_pre_load<FIRST_X>(d, hc, ilay, gene, true, preR);
+    uv_pre_load<FIRST_X, HM>(d, hc, ilay, gene, true, preR);
+    // HM: the kept Montgomery levels at the own cells (both updates share them), at the ring cell and at its b neighbour.
+    // The u update takes the W levels of a tile cell from the lane next to it; the column x0 - 1 goes through a side table
+    // in LDS: u first, TY threads without a ring cell fetch it in the ring cell's place; v first, it is the ring column.
+    double ms[Q][3], mb[Q][3], msR[3], mbR[3];
+    double (*s_w)[G::TY] = nullptr;
+    const int wrow = tid - (G::TX + 1) - (FIRST_X ? G::TY : 0);          // the side table's row this thread fills
+    const bool wfill = wrow >= 0 && wrow < G::TY;
+    if constexpr (HM) {
+        s_w = hm_side_table<G::TY>();
+#pragma unroll
+        for (int q = 0; q < Q; ++q) hm_load(d, c[q].ipnt, ilay, ms[q]);
+        hm_load(d, hc.ipnt, ilay, msR);
+        int ib = FIRST_X ? hc.template nb<5>() : hc.template nb<7>();
+        if (FIRST_X && wfill) ib = (x0 - 1) + (y0 + wrow - 1) * d.P;
+        hm_load(d, ib, ilay, mbR);
+    }
     // ---- stage
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
@@ -944,32 +1008,57 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
         }
     }
     if (hrr >= 0) s_hl[hrr][hcc] = hring;
+    if constexpr (HM) {
+        if (wfill) { s_w[0][wrow] = FIRST_X ? mbR[0] : msR[0]; s_w[1][wrow] = FIRST_X ? mbR[1] : msR[1]; s_w[2][wrow] = FIRST_X ? mbR[2] : msR[2]; }
+        // v first: the S levels of the own cells, issued now that the stage registers are free (rows other waves just read)
+        if (!FIRST_X) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) hm_load(d, c[q].template nb<7>(), ilay, mb[q]);
+        }
+    }
     __syncthreads();
     // ---- phase B loads (second update): in flight while the first update is evaluated
     double pre2[Q][8];
 #pragma unroll
-    for (int q = 0; q < Q; ++q) uv_pre_load<!FIRST_X>(d, c[q], ilay, gene, false, pre2[q]);
-    // ---- first update: own cells, then the ring cell
+    for (int q = 0; q < Q; ++q) {
+        uv_pre_load<!FIRST_X, HM>(d, c[q], ilay, gene, false, pre2[q]);
+        if (HM && FIRST_X) hm_load(d, c[q].template nb<7>(), ilay, mb[q]);      // (v second: its S levels)
+    }
+    // ---- first update: own cells, then the ring cell (HM: the ring cell first — its eleven loaded values are then dead
+    // while the own cells are evaluated, which is what keeps that form at four waves per SIMD)
     const double hs2 = 2.0 * d.hsal;
+    auto ring_cell = [&]() {
+        if (rr1 >= 0) {
+            const ShLds<Q, FIRST_X> sh{s_f, s_hl, rb - (y0 - 1), ra - (x0 - 1), d.ocrp, hs2};
+            if (HM) hm_form(d, msR, mbR, preR);
+            s_h[rr1][cc1] = uv_first_eval<FIRST_X, true, false, true, SF, HM>(d, hc, ilay, gene, ramp, ctim, sh, true, preR, ZV);
+        }
+    };
+    if (HM) ring_cell();
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int r = wy + G::WAVES * q;
         const ShLds<Q, FIRST_X> sh{s_f, s_hl, r + 1, lx + 1, d.ocrp, hs2};
-        s_h[r + ROFF][lx + COFF] = uv_first_eval<FIRST_X, true, true, true, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q], pre[q], ZV);
+        if constexpr (HM) {
+            if (FIRST_X) hm_form_w<G::TY>(d, ms[q], s_w, r, lx, pre[q]);
+            else hm_form(d, ms[q], mb[q], pre[q]);
+        }
+        s_h[r + ROFF][lx + COFF] = uv_first_eval<FIRST_X, true, true, true, SF, HM>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q], pre[q], ZV);
     }
-    if (rr1 >= 0) {
-        const ShLds<Q, FIRST_X> sh{s_f, s_hl, rb - (y0 - 1), ra - (x0 - 1), d.ocrp, hs2};
-        s_h[rr1][cc1] = uv_first_eval<FIRST_X, true, false, true, SF>(d, hc, ilay, gene, ramp, ctim, sh, true, preR, ZV);
-    }
+    if (!HM) ring_cell();
     __syncthreads();
     // ---- second component, transport of the first from LDS
     double *const *dm = FIRST_X ? d.dmy : d.dmx;
     const UVio io{FIRST_X ? d.v : d.u, FIRST_X ? d.v_alt : d.u_alt, FIRST_X ? d.hv_alt : d.hu_alt,
-                  dm[0], dm[1], dm[2], dm[0]};
+                  HM ? nullptr : dm[0], HM ? nullptr : dm[1], HM ? nullptr : dm[2], HM ? nullptr : dm[0]};
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-        if (!wr[q]) continue;
         const int r = wy + G::WAVES * q;
+        if constexpr (HM) {
+            if (FIRST_X) hm_form(d, ms[q], mb[q], pre2[q]);
+            else hm_form_w<G::TY>(d, ms[q], s_w, r, lx, pre2[q]);
+        }
+        if (!wr[q]) continue;
         double q0, qb, qa, qd;
         if (FIRST_X) {   // v: self, S, E, SE of h_u
             q0 = s_h[r + 1][lx]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r][lx + 1];
@@ -977,7 +1066,7 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
             q0 = s_h[r][lx + 1]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r + 1][lx];
         }
         const ShLds<Q, !FIRST_X> sh{s_f, s_hl, r + 1, lx + 1, d.ocrp, hs2};
-        uv_core<!FIRST_X, true, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh, true, pre2[q], ZV);
+        uv_core<!FIRST_X, true, true, SF, HM>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh, true, pre2[q], ZV);
     }
 }
 
@@ -1049,7 +1138,7 @@ __device__ __forceinline__ void body_uv_fused(const DevView &d, int x0, int y0, 
         const int cb = !FIRST_X ? c[q].template nb<5>() : c[q].template nb<7>();
         const int ca = !FIRST_X ? c[q].template nb<3>() : c[q].template nb<1>();
         const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
-        uv_core<!FIRST_X, false, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
+        uv_core<!FIRST_X, false, true, SF, false>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
     }
 }
 
@@ -1080,7 +1169,7 @@ struct ShLdsEdge {                                   // field order in the stage
     template <bool X> __device__ __forceinline__ double d2h_b() const { return LL(X ? d.d2hx : d.d2hy, cb, ilay); }
 };
 
-template <int Q, bool FIRST_X, bool SF>
+template <int Q, bool FIRST_X, bool SF, bool HM>
 __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int y0, int ilay, double gene, double ramp,
                                                    double ctim, double (*s_h)[TileGeom<Q>::LDX], UVstage<Q> *s_f,
                                                    double (*s_hl)[TileGeom<Q>::HLDX]) {
@@ -1139,11 +1228,11 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
                 // so the cell's own update reads global memory; and what it stages is what a lookup of it returns
                 const int ca = FIRST_X ? c[q].template nb<3>() : c[q].template nb<1>();
                 const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
-                (void)uv_first_eval<FIRST_X, true, true, false, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
-                hnew = uv_first_halo<FIRST_X, true, SF>(d, i, j, ilay, gene, ramp, ctim);
+                (void)uv_first_eval<FIRST_X, true, true, false, SF, HM>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
+                hnew = uv_first_halo<FIRST_X, true, SF, HM>(d, i, j, ilay, gene, ramp, ctim);
             } else {
                 const ShLdsEdge<Q, FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
-                hnew = uv_first_eval<FIRST_X, true, true, false, SF>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
+                hnew = uv_first_eval<FIRST_X, true, true, false, SF, HM>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
             }
         }
         s_h[r + ROFF][lx + COFF] = hnew;
@@ -1160,13 +1249,13 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
                 if (a != ga || b != gb) {
                     // a ring position beyond the periodic seam: the image around it is not the neighbourhood of the
                     // cell it stands for (the wraps act on every lookup anew) — the rare global path
-                    val = uv_first_halo<FIRST_X, true, SF>(d, ga, gb, ilay, gene, ramp, ctim);
+                    val = uv_first_halo<FIRST_X, true, SF, HM>(d, ga, gb, ilay, gene, ramp, ctim);
                 } else {
                     CellDenseT<false> h;
                     h.set_cell(d, a, b);
                     const int cb = FIRST_X ? h.template nb<5>() : h.template nb<7>();
                     const ShLdsEdge<Q, FIRST_X> sh{s_f, s_hs, gb - (y0 - 1), ga - (x0 - 1), d, h.ipnt, cb, ilay};
-                    val = uv_first_eval<FIRST_X, true, false, false, SF>(d, h, ilay, gene, ramp, ctim, sh);
+                    val = uv_first_eval<FIRST_X, true, false, false, SF, HM>(d, h, ilay, gene, ramp, ctim, sh);
                 }
             }
             s_h[rr][cc] = val;
@@ -1176,7 +1265,7 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
     // ---- second component, transport of the first from LDS
     double *const *dm = FIRST_X ? d.dmy : d.dmx;
     const UVio io{FIRST_X ? d.v : d.u, FIRST_X ? d.v_alt : d.u_alt, FIRST_X ? d.hv_alt : d.hu_alt,
-                  dm[0], dm[1], dm[2], dm[0]};
+                  HM ? nullptr : dm[0], HM ? nullptr : dm[1], HM ? nullptr : dm[2], HM ? nullptr : dm[0]};
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         if (!wr[q]) continue;
@@ -1188,17 +1277,19 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
         if ((d.xper && i == d.L) || (d.yper && !d.slab && y0 + r == d.M)) {      // orphan column / row: see above
             const int ca = !FIRST_X ? c[q].template nb<3>() : c[q].template nb<1>();
             const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
-            uv_core<!FIRST_X, true, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
+            uv_core<!FIRST_X, true, true, SF, HM>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
         } else {
             const ShLdsEdge<Q, !FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
-            uv_core<!FIRST_X, true, true, SF>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
+            uv_core<!FIRST_X, true, true, SF, HM>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
         }
     }
 }
 
 // ZV (with PROD): v_cc = v_ll = +0 everywhere — interior workgroups drop the viscous products
-template <int Q, bool FIRST_X, bool PROD, bool ZV, bool SF>
+// HM (with PROD): the history-from-Montgomery form — dmx, dmy are not touched (uv_core)
+template <int Q, bool FIRST_X, bool PROD, bool ZV, bool SF, bool HM = false>
 __device__ __forceinline__ void uv_fused_workgroup(const DevView &d, double gene, double ramp, double ctim) {
+    static_assert(PROD || !HM, "the history-from-Montgomery form exists for the staged (PROD) bodies only");
     using G = TileGeom<Q>;
     __shared__ double s_h[G::TY + 1][G::LDX];
     __shared__ UVstage<Q> s_f[PROD ? 4 : 1];                    // (ZV: the interior workgroups use two of them, the edge ones all four)
@@ -1210,14 +1301,14 @@ __device__ __forceinline__ void uv_fused_workgroup(const DevView &d, double gene
     const int ilay = blockIdx.y + 1;
     const bool interior = x0 - 1 >= 2 && x0 + G::TX <= d.L - 2 && y0 - 1 >= 2 && y0 + G::TY <= d.M - 2
                           && y0 - 1 + d.joff >= 2 && y0 + G::TY + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, G::TY);
-    if (interior && PROD) body_uv_fused_staged<Q, FIRST_X, ZV, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
+    if (interior && PROD) body_uv_fused_staged<Q, FIRST_X, ZV, SF, HM>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
     else if (interior) body_uv_fused<Q, FIRST_X, true, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
-    else if (PROD) body_uv_fused_edge<Q, FIRST_X, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
+    else if (PROD) body_uv_fused_edge<Q, FIRST_X, SF, HM>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
     else body_uv_fused<Q, FIRST_X, false, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
 }
-template <int Q, bool FIRST_X, bool PROD, bool ZV = false>
+template <int Q, bool FIRST_X, bool PROD, bool ZV = false, bool HM = false>
 __global__ __launch_bounds__(TileGeom<Q>::BLOCK) void k_uv_fused(DevView d, double gene, double ramp, double ctim) {
-    uv_fused_workgroup<Q, FIRST_X, PROD, ZV, false>(d, gene, ramp, ctim);
+    uv_fused_workgroup<Q, FIRST_X, PROD, ZV, false, HM>(d, gene, ramp, ctim);
 }
 // ... with distribute_stress formed inside (SF): its own kernels, so that the unforced ones do not carry its registers.  Their
 // 64 x 8 u-first zero-viscosity form takes 128 VGPRs and runs four waves per SIMD: wind-driven 4096x2048x2, same box, u+v
@@ -1227,6 +1318,26 @@ template <int Q, bool FIRST_X, bool PROD, bool ZV = false>
 __global__ __launch_bounds__(TileGeom<Q>::BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void k_uv_fused_sf(DevView d, double gene, double ramp, double ctim) {
     uv_fused_workgroup<Q, FIRST_X, PROD, ZV, true>(d, gene, ramp, ctim);
 }
+// The history arrays after steps of the history-from-Montgomery form, which leave them alone: dmx[0..2], dmy[0..2] at every
+// real cell from the Montgomery potential of the last three steps (d.mo1, d.mo2, d.mont), by the lookups and mask predicates
+// of the general dense context — what k_update_uv<CellDense> would have stored in those steps.
+__global__ __launch_bounds__(BEOM_BLOCK) void k_hist_from_mont(DevView d) {
+    CellDense c;
+    if (!c.init(d)) return;
+    const int ipnt = c.ipnt, ilay = blockIdx.y + 1;
+    const int c5 = c.template nb<5>(), c7 = c.template nb<7>();
+    const double mku = c.mk_u(), mkv = c.mk_v();
+    const double s0 = LL(d.mo1, ipnt, ilay), s1 = LL(d.mo2, ipnt, ilay), s2 = LL(d.mont, ipnt, ilay);
+    const double w0 = LL(d.mo1, c5, ilay), w1 = LL(d.mo2, c5, ilay), w2 = LL(d.mont, c5, ilay);
+    const double t0 = LL(d.mo1, c7, ilay), t1 = LL(d.mo2, c7, ilay), t2 = LL(d.mont, c7, ilay);
+    LL(d.dmx[0], ipnt, ilay) = hist_from_mont(d, w0, s0, mku);
+    LL(d.dmx[1], ipnt, ilay) = hist_from_mont(d, w1, s1, mku);
+    LL(d.dmx[2], ipnt, ilay) = hist_from_mont(d, w2, s2, mku);
+    LL(d.dmy[0], ipnt, ilay) = hist_from_mont(d, t0, s0, mkv);
+    LL(d.dmy[1], ipnt, ilay) = hist_from_mont(d, t1, s1, mkv);
+    LL(d.dmy[2], ipnt, ilay) = hist_from_mont(d, t2, s2, mkv);
+}
+
 template <int Q>
 static inline dim3 uv_fused_grid(const DevView &d) {
     return dim3(TileMap(d, TileGeom<Q>::TX, TileGeom<Q>::TY).blocks(), (unsigned)d.nlay, 1);

@@ -502,7 +502,8 @@ class Engine(_Tracers):
     def info(self, what: str) -> int:
         """beom_info: "stress_folded" (the last step formed its stress inside the momentum sweep: tt3d, tb3d, tu3d are
         then not kept current), "tile_rows", "biharm_tiled" (1: the handle's biharmonic viscosity, svis > 0, runs as the tiled
-        sweep; 0 on the table path and with svis = 0), "uv_fused" (1: the last step's momentum ran as the fused u+v sweep)."""
+        sweep; 0 on the table path and with svis = 0), "uv_fused" (1: the last step's momentum ran as the fused u+v sweep),
+        "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did)."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))

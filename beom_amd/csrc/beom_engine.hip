@@ -117,6 +117,11 @@ struct beom_engine {
     int mont_levels_valid = 0;         // consecutive steps, up to the last one, whose Montgomery potential the buffers hold
     bool hist_stale = false;           // dmx, dmy lag behind: steps of the new form have left them alone (hist_sync)
     bool last_mont_hist = false;       // the last step ran the new form (beom_info "mont_history")
+    // Plain sweeps (option "plain_sweeps", default on): a launch of the fused u+v sweep resp. of the Montgomery
+    // sweep whose handle has none of the optional forcing takes the instantiation with that forcing compiled out.  Decided
+    // per launch from the flags of the moment (keep_diag, uploaded stress and options change between steps).
+    bool plain_sweeps = true;
+    int last_plain = 0;                // bit 0: the last step's u+v sweep ran plain, bit 1: its Montgomery sweep (beom_info "plain_sweeps")
     // conservation integrals (beom_integral_rows): chunk sums and row sums of up to M rows, allocated on the first call; on
     // the table path also the packed cell of every (i, j) and the wraps read off neig
     double *integ_part = nullptr, *integ_rows = nullptr;
@@ -732,31 +737,38 @@ static void launch_uv(beom_engine *E, int ilay, double gene, double ramp, double
 }
 // the tiled sweeps in the tile geometry Q (beom_kernels.h: TileGeom)
 template <int Q>
-static bool raw_mont_visc(beom_engine *E, bool leith) {
+static bool raw_mont_visc(beom_engine *E, bool leith, bool plain) {
     const dim3 g = mont_visc_grid<Q>(E->d), b(BEOM_BLOCK);
     switch (E->d.nlay) {
-#define CASE_NL(n) case n: if (leith) hipLaunchKernelGGL((k_mont_visc<Q, n, true>), g, b, 0, E->stream, E->d); \
-                           else hipLaunchKernelGGL((k_mont_visc<Q, n, false>), g, b, 0, E->stream, E->d); return true;
+#define MV_GO(n, le, pl) hipLaunchKernelGGL((k_mont_visc<Q, n, le, pl>), g, b, 0, E->stream, E->d)
+#define CASE_NL(n) case n: if (plain) { if (leith) MV_GO(n, true, true); else MV_GO(n, false, true); } \
+                           else if (leith) MV_GO(n, true, false); else MV_GO(n, false, false); return true;
         CASE_NL(1) CASE_NL(2) CASE_NL(3) CASE_NL(4) CASE_NL(5) CASE_NL(6) CASE_NL(7) CASE_NL(8)
 #undef CASE_NL
+#undef MV_GO
         default: return false;
     }
 }
 template <int Q>
-static void raw_uv_fused(beom_engine *E, bool first_x, bool prod, bool zv, bool hm, double gene, double ramp, double ctim) {
+static void raw_uv_fused(beom_engine *E, bool first_x, bool prod, bool zv, bool hm, bool plain, double gene, double ramp, double ctim) {
     const dim3 g = uv_fused_grid<Q>(E->d), b(TileGeom<Q>::BLOCK);
     DevView &d = E->d;
 #define UV_GO(kern, fx, pr, z) hipLaunchKernelGGL((kern<Q, fx, pr, z>), g, b, 0, E->stream, d, gene, ramp, ctim)
+#define UV_PLAIN(fx, z, h) hipLaunchKernelGGL((k_uv_fused<Q, fx, true, z, h, true>), g, b, 0, E->stream, d, gene, ramp, ctim)
 #define UV_PICK(fx) do { \
-        if (hm) { if (zv) hipLaunchKernelGGL((k_uv_fused<Q, fx, true, true, true>), g, b, 0, E->stream, d, gene, ramp, ctim); \
-                  else hipLaunchKernelGGL((k_uv_fused<Q, fx, true, false, true>), g, b, 0, E->stream, d, gene, ramp, ctim); } \
+        if (plain) { if (hm) { if (zv) UV_PLAIN(fx, true, true); else UV_PLAIN(fx, false, true); } \
+                     else { if (zv) UV_PLAIN(fx, true, false); else UV_PLAIN(fx, false, false); } } \
+        else if (hm) { if (zv) hipLaunchKernelGGL((k_uv_fused<Q, fx, true, true, true>), g, b, 0, E->stream, d, gene, ramp, ctim); \
+                       else hipLaunchKernelGGL((k_uv_fused<Q, fx, true, false, true>), g, b, 0, E->stream, d, gene, ramp, ctim); } \
         else if (d.stress_fold) { if (zv) UV_GO(k_uv_fused_sf, fx, true, true); else if (prod) UV_GO(k_uv_fused_sf, fx, true, false); else UV_GO(k_uv_fused_sf, fx, false, false); } \
         else { if (zv) UV_GO(k_uv_fused, fx, true, true); else if (prod) UV_GO(k_uv_fused, fx, true, false); else UV_GO(k_uv_fused, fx, false, false); } \
     } while (0)
     // (stress_fold: distribute_stress formed inside the sweep — its own instantiations, so that the unforced ones stay lean;
-    // hm: the history-from-Montgomery form, instantiated for the staged k_uv_fused only — mont_hist_step is its gate)
+    // hm: the history-from-Montgomery form, instantiated for the staged k_uv_fused only — mont_hist_step is its gate;
+    // plain: the staged forms with the optional forcing compiled out — launch_uv_fused is its gate)
     if (first_x) UV_PICK(true); else UV_PICK(false);
 #undef UV_PICK
+#undef UV_PLAIN
 #undef UV_GO
 }
 // fused Montgomery + Leith sweep (dense frames); false if no instantiation for this nlay
@@ -767,7 +779,11 @@ static bool launch_mont_visc(beom_engine *E, bool uv_fused_follows, bool leith, 
     E->d.keep_visc = keep_visc;
     E->d.zero_visc = !leith && uv_fused_follows && E->lean_visc && E->visc_all_zero && E->P.dvis == 0.0 && E->P.bvis == 0.0 &&
                      !E->d.keep_diag;
-    return E->tile4 ? raw_mont_visc<1>(E, leith) : raw_mont_visc<2>(E, leith);
+    // plain: nothing of what PLAIN compiles out of body_mont_visc is asked for by this launch
+    const bool plain = E->plain_sweeps && E->d.ocrp == 0.0 && !(E->d.rgld >= 0.5) && !E->d.has_hto && !E->d.keep_diag && !E->d.keep_visc;
+    const bool ok = E->tile4 ? raw_mont_visc<1>(E, leith, plain) : raw_mont_visc<2>(E, leith, plain);
+    if (ok && plain) E->last_plain |= 2;
+    return ok;
 }
 // fused U+V sweep (dense frames): first_x = update_u first (even tstp)
 static void uv_fused_swap(beom_engine *E, bool first_x, bool hm = false) {
@@ -782,8 +798,13 @@ static void uv_fused_swap(beom_engine *E, bool first_x, bool hm = false) {
 static void launch_uv_fused(beom_engine *E, bool first_x, bool prod, double gene, double ramp, double ctim,
                             bool swap = true, bool hm = false) {
     const bool zv = prod && E->d.zero_visc;       // set by launch_mont_visc of this step
-    if (E->tile4) raw_uv_fused<1>(E, first_x, prod, zv, hm, gene, ramp, ctim);
-    else raw_uv_fused<2>(E, first_x, prod, zv, hm, gene, ramp, ctim);
+    // plain: a staged sweep (not the _sf kernel) of a handle with nothing of what PLAIN compiles out of uv_core
+    const DevView &d = E->d;
+    const bool plain = E->plain_sweeps && prod && !d.stress_fold && !d.has_nudg && !d.has_tide && !d.has_stress && !d.has_bodf &&
+                       !(d.rgld >= 0.5) && d.svis == 0.0;
+    if (plain) E->last_plain |= 1;
+    if (E->tile4) raw_uv_fused<1>(E, first_x, prod, zv, hm, plain, gene, ramp, ctim);
+    else raw_uv_fused<2>(E, first_x, prod, zv, hm, plain, gene, ramp, ctim);
     if (swap) uv_fused_swap(E, first_x, hm);
 }
 static bool can_fuse(const beom_engine *E, int n_3d, bool first3) {
@@ -959,6 +980,7 @@ static void one_step(beom_engine *E, int tstp, const StepScalars &s) {
     if (!hm) (void)hist_sync(E);                                   // a step on the arrays: bring them up to date first
     rotate_mont(E);                                                // the one place d.mont moves to its next buffer
     StepTimer *T = begin_step(E, tstp, s);
+    E->last_plain = 0;
     const bool prod = step_front(E, s, T);
     const bool u_first = tstp % 2 == 0;                            // :2193-2199,2276-2282
     E->last_uv_fused = s.fused_uv;
@@ -1089,6 +1111,7 @@ int beom_step_phase(beom_handle E, int tstp, double tres, double dtd8, double dt
     E->last_uv_fused = true;
     E->last_mont_hist = false;
     if (phase == 1) {
+        E->last_plain = 0;
         E->split_prod = step_front(E, s, T);      // (s.fused_uv holds: parts 2 and 3 are the fused u+v sweep it prepares)
     } else if (phase == 2) {
         // a side without a neighbour has no strip (its rows belong to part 3)
@@ -1385,6 +1408,7 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "biharm_tiled")) return biharm_tiled(E) ? 1 : 0;
     if (!strcmp(what, "uv_fused")) return E->last_uv_fused ? 1 : 0;
     if (!strcmp(what, "mont_history")) return E->last_mont_hist ? 1 : 0;
+    if (!strcmp(what, "plain_sweeps")) return E->last_plain;
     if (!strcmp(what, "tracers")) return E->ntrc;
     if (!strcmp(what, "lid_sweeps")) return (int)std::min<long long>(E->lid_sweeps, 2000000000ll);        // Gauss-Seidel sweeps kept, all steps so far
     if (!strcmp(what, "lid_solves")) return (int)std::min<long long>(E->lid_solves, 2000000000ll);
@@ -1406,6 +1430,7 @@ int beom_set_option(beom_handle E, const char *name, int value) {
     else if (!strcmp(name, "lean_d2h")) E->lean_d2h = value != 0;
     else if (!strcmp(name, "lean_visc")) E->lean_visc = value != 0;
     else if (!strcmp(name, "mont_history")) E->mont_history = value != 0;
+    else if (!strcmp(name, "plain_sweeps")) E->plain_sweeps = value != 0;
     else return -3;
     return 0;
 }

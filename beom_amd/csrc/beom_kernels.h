@@ -316,7 +316,9 @@ __device__ __forceinline__ bool halo_target(const DevView &d, int &a, int &b) {
 // LEITH = false: configurations whose viscosity is never refreshed after the first three steps
 // (dvis <= 1e-3, svis = 0): v_cc, v_ll keep whatever update_viscosity left there (:2188) and only
 // the products with this step's dive, rvor are formed — no ring of rvor/dive is needed.
-template <int Q, int NL, bool INT, bool LEITH>
+// PLAIN: no outcropping (ocrp = 0), no lid, no h_to, neither keep_diag nor keep_visc — compile-time facts (the engine picks
+// the form per launch, launch_mont_visc); every surviving statement is the one of the general form
+template <int Q, int NL, bool INT, bool LEITH, bool PLAIN>
 __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0, bool wr_d2h, bool wr_prod,
                                                double (*s_rv)[TileGeom<Q>::MV_LDY][TileGeom<Q>::MV_LDX],
                                                double (*s_dv)[TileGeom<Q>::MV_LDY][TileGeom<Q>::MV_LDX],
@@ -345,7 +347,7 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
         n1[q] = c[q].template nb<1>(); n3[q] = c[q].template nb<3>(); n5[q] = c[q].template nb<5>();
         n6[q] = c[q].template nb<6>(); n7[q] = c[q].template nb<7>();
         fcor[q] = d.fcor[c[q].ipnt]; h_th[q] = d.h_th[c[q].ipnt];
-        h_to[q] = d.has_hto ? d.h_to[c[q].ipnt] : 0.0;
+        h_to[q] = (!PLAIN && d.has_hto) ? d.h_to[c[q].ipnt] : 0.0;
         hcol[q] = 0.0;
 #pragma unroll
         for (int l = 0; l < NL; ++l) { hown[l][q] = LL(d.hlay, c[q].ipnt, l + 1); hcol[q] = hcol[q] + hown[l][q]; }
@@ -438,7 +440,7 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
             const double u_le = w[q][0], u_ri = w[q][1], v_bo = w[q][2], v_to = w[q][3];
             const double h0 = hown[l][q];
             double mpot = -0.0;
-            if (d.ocrp != 0.0) {
+            if (!PLAIN && d.ocrp != 0.0) {
                 mpot = h0 + d.hmin * (1.0 - mkn);
                 mpot = powi_dev(d.hsal / mpot, d.nsal - 1);
                 mpot = mpot * (-d.ocrp * i_ns * d.hsal * mkn);
@@ -447,7 +449,7 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
             const double i_rn = d.i_rn[l];
 #pragma unroll
             for (int m = 0; m < l; ++m) mpot = mpot - (d.rhon[l] - d.rhon[m]) * i_rn * hown[m][q];
-            if (d.rgld < 0.5) mpot = hcol[q] - h_th[q] + mpot;
+            if (PLAIN || d.rgld < 0.5) mpot = hcol[q] - h_th[q] + mpot;
             LL(d.mont, ipnt, ilay) = mpot + 0.25 * d.uadv * i_gr
                                           * (u_ri * u_ri + u_le * u_le + v_to * v_to + v_bo * v_bo);
             // thickness of the neighbours from the stage (what the lookups n1, n5, n3, n7, n6 return)
@@ -456,7 +458,7 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
             if (wr_d2h) {
                 double d2x = (hE + hW - h0 * 2.0) * mk1 * mk5 * mkn;
                 double d2y = (hN + hS - h0 * 2.0) * mk3 * mk7 * mkn;
-                if (d.ocrp > 0.5) {
+                if (!PLAIN && d.ocrp > 0.5) {
                     if (hE < 2.0 * hs_8 || hW < 2.0 * hs_8 || h0 < 2.0 * hs_8) d2x = 0.0;
                     if (hN < 2.0 * hs_8 || hS < 2.0 * hs_8 || h0 < 2.0 * hs_8) d2y = 0.0;
                 }
@@ -489,10 +491,10 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
                 LL(d.pcd, ipnt, ilay) = vcc * d_cc;
                 LL(d.qlr, ipnt, ilay) = vll * r_bl;
             }
-            if (d.keep_diag) {
+            if (!PLAIN && d.keep_diag) {
                 LL(d.rvor, ipnt, ilay) = r_bl; LL(d.dive, ipnt, ilay) = d_cc;
                 if (LEITH) { LL(d.v_cc, ipnt, ilay) = vcc; LL(d.v_ll, ipnt, ilay) = vll; }
-            } else if (LEITH && d.keep_visc) {       // refreshed every n_3d > 1 steps: must stand until the next refresh
+            } else if (!PLAIN && LEITH && d.keep_visc) {       // refreshed every n_3d > 1 steps: must stand until the next refresh
                 LL(d.v_cc, ipnt, ilay) = vcc; LL(d.v_ll, ipnt, ilay) = vll;
             }
         }
@@ -503,7 +505,7 @@ __device__ __forceinline__ void body_mont_visc(const DevView &d, int x0, int y0,
 // would take 172 and run two).  Measured on one box, alternating builds (tools/ab_variants.sh): mont+visc 1000 -> 905 us at
 // 4096^2 x 4, 180 -> 157 us on the sill frame (Leith + outcropping), 822 -> 706 us at 8192 x 1024 x 8 despite 84-328 B of
 // scratch per lane there; a cap for four waves (128 VGPRs) spills more than it hides.
-template <int Q, int NL, bool LEITH = true>
+template <int Q, int NL, bool LEITH = true, bool PLAIN = false>
 __global__ __launch_bounds__(BEOM_BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void k_mont_visc(DevView d) {
     using G = TileGeom<Q>;
     __shared__ double s_rv[LEITH ? 2 : 1][LEITH ? G::MV_LDY : 1][LEITH ? G::MV_LDX : 1];
@@ -526,8 +528,8 @@ __global__ __launch_bounds__(BEOM_BLOCK) __attribute__((amdgpu_waves_per_eu(3)))
             for (int dx = -1; dx <= 1; ++dx) deep = deep && tile_regular(d, x0 + dx * G::TX, uy0 + dy * G::TY, G::TY);
     const bool wr_d2h = !(d.lean_d2h && deep);
     const bool wr_prod = !(d.zero_visc && deep);   // zero viscosity: interior workgroups of k_uv_fused skip the term
-    if (interior) body_mont_visc<Q, NL, true, LEITH>(d, x0, y0, wr_d2h, wr_prod, (double (*)[G::MV_LDY][G::MV_LDX])s_rv, (double (*)[G::MV_LDY][G::MV_LDX])s_dv, s_hh);
-    else body_mont_visc<Q, NL, false, LEITH>(d, x0, y0, wr_d2h, wr_prod, (double (*)[G::MV_LDY][G::MV_LDX])s_rv, (double (*)[G::MV_LDY][G::MV_LDX])s_dv, s_hh);
+    if (interior) body_mont_visc<Q, NL, true, LEITH, PLAIN>(d, x0, y0, wr_d2h, wr_prod, (double (*)[G::MV_LDY][G::MV_LDX])s_rv, (double (*)[G::MV_LDY][G::MV_LDX])s_dv, s_hh);
+    else body_mont_visc<Q, NL, false, LEITH, PLAIN>(d, x0, y0, wr_d2h, wr_prod, (double (*)[G::MV_LDY][G::MV_LDX])s_rv, (double (*)[G::MV_LDY][G::MV_LDX])s_dv, s_hh);
 }
 template <int Q>
 static inline dim3 mont_visc_grid(const DevView &d) { return dim3(TileMap(d, TileGeom<Q>::TX, TileGeom<Q>::TY).blocks(), 1, 1); }
@@ -659,11 +661,15 @@ __device__ __forceinline__ double hist_from_mont(const DevView &d, double m_b, d
 // SF (stress fold): distribute_stress formed here (a template switch: the unforced sweeps must not carry its registers)
 // HM (history from Montgomery): the three history levels are re-formed from the kept Montgomery levels d.mo0..2 (pre[5..7]
 // hold them already formed, or the cell and cb are read here); the history arrays are neither read nor written
-template <bool XDIR, bool PROD, bool STORE, bool SF, bool HM, class C, class SH>
+// PLAIN (with PROD, without SF): no nudging rate, no tide, no stress arrays, no body force, no lid — compile-time facts (the
+// engine picks the form per launch, launch_uv_fused; svis = 0 comes with PROD); the rare-lane paths and every surviving
+// statement are those of the general form
+template <bool XDIR, bool PROD, bool STORE, bool SF, bool HM, bool PLAIN = false, class C, class SH>
 __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay, double gene, double ramp,
                                           double ctim, int copy_hist, const UVio &io,
                                           double q0, double qb, double qa, double qd, const SH &sh,
                                           bool do_store = true, const double *pre = nullptr, bool zv = false) {
+    static_assert(!PLAIN || (PROD && !SF), "the plain form exists for the staged (PROD) bodies without the stress fold");
     const int ipnt = c.ipnt;
     // u: cb = W(5), ca = N(3);   v: cb = S(7), ca = E(1)
     const int cb = XDIR ? c.template nb<5>() : c.template nb<7>();
@@ -682,7 +688,7 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
     // nudging rate of this point; the target velocity is fetched only where the rate is not zero (sponges cover a
     // few rows or columns of a frame) or where the sign of an exact zero is at stake
     double f_ng = 0.0;
-    if (d.has_nudg) f_ng = NUDG_(ipnt, IV);       // (the tile table of update_h costs this sweep more registers than it saves bytes)
+    if (!PLAIN && d.has_nudg) f_ng = NUDG_(ipnt, IV);       // (the tile table of update_h costs this sweep more registers than it saves bytes)
     const double dmd4 = (sh.mont_b() - m_self) * i_dl * d.grav * mask;
     const double pva = sh.pvor_a();
     double rhsi = dmd4 * (1.0 - gene);
@@ -703,14 +709,14 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
             if (lay_b && d.has_bot) rhsi = rhsi - fold_drag<XDIR, false>(c, d, ilay, vold) * i_r0 * i__h;
             if (lay_t && d.has_top) rhsi = rhsi - fold_drag<XDIR, true>(c, d, ilay, vold) * i_r0 * i__h;
         }
-    } else if (d.has_stress) {
+    } else if (!PLAIN && d.has_stress) {
         const double i__h = 1.0 / (hcen + 1.0 - mask);
         const double tauw = 0.5 * (T3_(d.tt3d, cb, ID, ilay) + T3_(d.tt3d, ipnt, ID, ilay)) * ramp;
         rhsi = rhsi + tauw * i_r0 * i__h;
         rhsi = rhsi - T3_(d.tb3d, ipnt, ID, ilay) * i_r0 * i__h;
         rhsi = rhsi - T3_(d.tu3d, ipnt, ID, ilay) * i_r0 * i__h;
     }
-    rhsi = rhsi + (d.has_bodf ? d.bodf[(ilay - 1) + d.nlay * (ID - 1)] : 0.0);   // + (+0) is not a no-op for -0
+    rhsi = rhsi + ((!PLAIN && d.has_bodf) ? d.bodf[(ilay - 1) + d.nlay * (ID - 1)] : 0.0);   // + (+0) is not a no-op for -0
     // gene = 0 (steps 1-3, g_fb = 0): the term is (finite)*0 = +-0 and only matters for the sign of
     // an exactly-zero rhsi; fetch the history on those (rare) lanes only.
     if (HM) {
@@ -770,7 +776,7 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
     vold = vold + rhsi * mask * d.dt;
     // Rate zero (or no nudging at all): the reference still evaluates vfor*0 + vold*(1-0) = (+-0) + vold, i.e. vold
     // unless vold is an exact zero, so only those (rare) lanes go through the full expression.
-    if (f_ng != 0.0 || vold == 0.0) {
+    if ((!PLAIN && f_ng != 0.0) || vold == 0.0) {
         const double i__hh = 1.0 / (hcen + 1.0 - mask);
         double vfor = FNUD_(ipnt, ilay, IV);
         if (SF) {                              // tt3d = taus * fraction (1 in the top layer, 0 below), formed here (see above)
@@ -778,14 +784,14 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
             const double t0 = d.has_wind ? d.taus_cells[ipnt + d.n1 * (IO - 1)] * lt : 0.0, tb_ = d.has_wind ? d.taus_cells[cb + d.n1 * (IO - 1)] * lt : 0.0;
             const double ek = 0.5 * (t0 + tb_) * i_r1 * d.invf * i__hh * ramp;
             vfor = XDIR ? vfor + ek : vfor - ek;
-        } else if (d.has_stress) {
+        } else if (!PLAIN && d.has_stress) {
             const double ek = 0.5 * (T3_(d.tt3d, ipnt, IO, ilay) + T3_(d.tt3d, cb, IO, ilay))
                               * i_r1 * d.invf * i__hh * ramp;
             vfor = XDIR ? vfor + ek : vfor - ek;
         } else {
             vfor = XDIR ? vfor + 0.0 : vfor - 0.0;                      // the Ekman term is +0 then
         }
-        if (d.has_tide) vfor = vfor + ramp * TIDE_(1, ipnt, IV) * cos(TIDE_(2, ipnt, IV) - d.w_ti * ctim);
+        if (!PLAIN && d.has_tide) vfor = vfor + ramp * TIDE_(1, ipnt, IV) * cos(TIDE_(2, ipnt, IV) - d.w_ti * ctim);
         else vfor = vfor + 0.0;                                         // ramp*0*cos(0)
         vold = vfor * f_ng + vold * (1.0 - f_ng);
     }
@@ -793,7 +799,7 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
                       + 0.5 * (vold - fabs(vold)) * (hcen - 0.16667 * sh.template d2h_s<XDIR>());   // rgld = 0 (:1491,1577)
     if (STORE && do_store) {
         LL(io.vel_out, ipnt, ilay) = vold;
-        if (d.rgld < 0.5) LL(io.hp_out, ipnt, ilay) = hnew;          // (:1491, :1577: with a lid the transports are rebuilt after the sweeps)
+        if (PLAIN || d.rgld < 0.5) LL(io.hp_out, ipnt, ilay) = hnew;          // (:1491, :1577: with a lid the transports are rebuilt after the sweeps)
         if (HM) {                              // the kept Montgomery levels stand for the history
         } else if (copy_hist) {                // single-layer entry points: shift like the reference
             const double m2 = LL(io.dm1, ipnt, ilay), m3 = LL(io.dm2, ipnt, ilay);
@@ -844,7 +850,7 @@ __global__ __launch_bounds__(BEOM_BLOCK) void k_update_uv(DevView d, int ilay_on
 //      place as well (the first update of other workgroups still reads the old one).
 //      Algorithmic traffic: 22 words per cell-layer instead of 14 + 14.
 // first update at one cell; SH = where its shared fields come from
-template <bool FIRST_X, bool PROD, bool STORE, bool INT, bool SF, bool HM = false, class SH>
+template <bool FIRST_X, bool PROD, bool STORE, bool INT, bool SF, bool HM = false, bool PLAIN = false, class SH>
 __device__ __forceinline__ double uv_first_eval(const DevView &d, const CellDenseT<INT> &c, int ilay, double gene,
                                                 double ramp, double ctim, const SH &sh, bool do_store = true,
                                                 const double *pre = nullptr, bool zv = false) {
@@ -856,15 +862,15 @@ __device__ __forceinline__ double uv_first_eval(const DevView &d, const CellDens
     double *const *dm = FIRST_X ? d.dmx : d.dmy;
     const UVio io{FIRST_X ? d.u : d.v, FIRST_X ? d.u_alt : d.v_alt, FIRST_X ? d.h_u : d.h_v,
                   HM ? nullptr : dm[0], HM ? nullptr : dm[1], HM ? nullptr : dm[2], HM ? nullptr : dm[3]};
-    if (pre) return uv_core<FIRST_X, PROD, STORE, SF, HM>(c, d, ilay, gene, ramp, ctim, 0, io, pre[1], pre[2], pre[3], pre[4],
+    if (pre) return uv_core<FIRST_X, PROD, STORE, SF, HM, PLAIN>(c, d, ilay, gene, ramp, ctim, 0, io, pre[1], pre[2], pre[3], pre[4],
                                                       sh, do_store, pre, zv);
-    return uv_core<FIRST_X, PROD, STORE, SF, HM>(c, d, ilay, gene, ramp, ctim, 0, io, LL(hq, ipnt, ilay),
+    return uv_core<FIRST_X, PROD, STORE, SF, HM, PLAIN>(c, d, ilay, gene, ramp, ctim, 0, io, LL(hq, ipnt, ilay),
                                              LL(hq, cb, ilay), LL(hq, ca, ilay), LL(hq, cd, ilay), sh, do_store);
 }
 
 // boundary workgroups: new first-component transport seen by a NEIGHBOUR lookup of the local
 // target (a, b) — wraps / sentinel applied, everything from global memory
-template <bool FIRST_X, bool PROD, bool SF, bool HM = false>
+template <bool FIRST_X, bool PROD, bool SF, bool HM = false, bool PLAIN = false>
 __device__ __forceinline__ double uv_first_halo(const DevView &d, int a, int b, int ilay, double gene,
                                                 double ramp, double ctim) {
     if (d.xper) { if (a == 0) a = d.L - 1; else if (a == d.L) a = 1; }
@@ -876,7 +882,7 @@ __device__ __forceinline__ double uv_first_halo(const DevView &d, int a, int b, 
     const int cb = FIRST_X ? h.template nb<5>() : h.template nb<7>();
     const int ca = FIRST_X ? h.template nb<3>() : h.template nb<1>();
     const ShGlobal sh{d, h.ipnt, cb, ca, ilay};
-    return uv_first_eval<FIRST_X, PROD, false, false, SF, HM>(d, h, ilay, gene, ramp, ctim, sh);
+    return uv_first_eval<FIRST_X, PROD, false, false, SF, HM, PLAIN>(d, h, ilay, gene, ramp, ctim, sh);
 }
 
 // Interior workgroups of the production pair (PROD, tile and ring strictly inside the wet interior):
@@ -928,7 +934,7 @@ __device__ __forceinline__ double (*hm_side_table())[TY] {
     return s_w;
 }
 
-template <int Q, bool FIRST_X, bool ZV, bool SF, bool HM>
+template <int Q, bool FIRST_X, bool ZV, bool SF, bool HM, bool PLAIN>
 __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, int y0, int ilay, double gene,
                                                      double ramp, double ctim, double (*s_h)[TileGeom<Q>::LDX], UVstage<Q> *s_f,
                                                      double (*s_hl)[TileGeom<Q>::HLDX]) {
@@ -1031,7 +1037,7 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
         if (rr1 >= 0) {
             const ShLds<Q, FIRST_X> sh{s_f, s_hl, rb - (y0 - 1), ra - (x0 - 1), d.ocrp, hs2};
             if (HM) hm_form(d, msR, mbR, preR);
-            s_h[rr1][cc1] = uv_first_eval<FIRST_X, true, false, true, SF, HM>(d, hc, ilay, gene, ramp, ctim, sh, true, preR, ZV);
+            s_h[rr1][cc1] = uv_first_eval<FIRST_X, true, false, true, SF, HM, PLAIN>(d, hc, ilay, gene, ramp, ctim, sh, true, preR, ZV);
         }
     };
     if (HM) ring_cell();
@@ -1043,7 +1049,7 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
             if (FIRST_X) hm_form_w<G::TY>(d, ms[q], s_w, r, lx, pre[q]);
             else hm_form(d, ms[q], mb[q], pre[q]);
         }
-        s_h[r + ROFF][lx + COFF] = uv_first_eval<FIRST_X, true, true, true, SF, HM>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q], pre[q], ZV);
+        s_h[r + ROFF][lx + COFF] = uv_first_eval<FIRST_X, true, true, true, SF, HM, PLAIN>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q], pre[q], ZV);
     }
     if (!HM) ring_cell();
     __syncthreads();
@@ -1066,7 +1072,7 @@ __device__ __forceinline__ void body_uv_fused_staged(const DevView &d, int x0, i
             q0 = s_h[r][lx + 1]; qb = s_h[r][lx]; qa = s_h[r + 1][lx + 1]; qd = s_h[r + 1][lx];
         }
         const ShLds<Q, !FIRST_X> sh{s_f, s_hl, r + 1, lx + 1, d.ocrp, hs2};
-        uv_core<!FIRST_X, true, true, SF, HM>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh, true, pre2[q], ZV);
+        uv_core<!FIRST_X, true, true, SF, HM, PLAIN>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh, true, pre2[q], ZV);
     }
 }
 
@@ -1169,7 +1175,7 @@ struct ShLdsEdge {                                   // field order in the stage
     template <bool X> __device__ __forceinline__ double d2h_b() const { return LL(X ? d.d2hx : d.d2hy, cb, ilay); }
 };
 
-template <int Q, bool FIRST_X, bool SF, bool HM>
+template <int Q, bool FIRST_X, bool SF, bool HM, bool PLAIN>
 __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int y0, int ilay, double gene, double ramp,
                                                    double ctim, double (*s_h)[TileGeom<Q>::LDX], UVstage<Q> *s_f,
                                                    double (*s_hl)[TileGeom<Q>::HLDX]) {
@@ -1228,11 +1234,11 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
                 // so the cell's own update reads global memory; and what it stages is what a lookup of it returns
                 const int ca = FIRST_X ? c[q].template nb<3>() : c[q].template nb<1>();
                 const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
-                (void)uv_first_eval<FIRST_X, true, true, false, SF, HM>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
-                hnew = uv_first_halo<FIRST_X, true, SF, HM>(d, i, j, ilay, gene, ramp, ctim);
+                (void)uv_first_eval<FIRST_X, true, true, false, SF, HM, PLAIN>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
+                hnew = uv_first_halo<FIRST_X, true, SF, HM, PLAIN>(d, i, j, ilay, gene, ramp, ctim);
             } else {
                 const ShLdsEdge<Q, FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
-                hnew = uv_first_eval<FIRST_X, true, true, false, SF, HM>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
+                hnew = uv_first_eval<FIRST_X, true, true, false, SF, HM, PLAIN>(d, c[q], ilay, gene, ramp, ctim, sh, wr[q]);
             }
         }
         s_h[r + ROFF][lx + COFF] = hnew;
@@ -1249,13 +1255,13 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
                 if (a != ga || b != gb) {
                     // a ring position beyond the periodic seam: the image around it is not the neighbourhood of the
                     // cell it stands for (the wraps act on every lookup anew) — the rare global path
-                    val = uv_first_halo<FIRST_X, true, SF, HM>(d, ga, gb, ilay, gene, ramp, ctim);
+                    val = uv_first_halo<FIRST_X, true, SF, HM, PLAIN>(d, ga, gb, ilay, gene, ramp, ctim);
                 } else {
                     CellDenseT<false> h;
                     h.set_cell(d, a, b);
                     const int cb = FIRST_X ? h.template nb<5>() : h.template nb<7>();
                     const ShLdsEdge<Q, FIRST_X> sh{s_f, s_hs, gb - (y0 - 1), ga - (x0 - 1), d, h.ipnt, cb, ilay};
-                    val = uv_first_eval<FIRST_X, true, false, false, SF, HM>(d, h, ilay, gene, ramp, ctim, sh);
+                    val = uv_first_eval<FIRST_X, true, false, false, SF, HM, PLAIN>(d, h, ilay, gene, ramp, ctim, sh);
                 }
             }
             s_h[rr][cc] = val;
@@ -1277,19 +1283,21 @@ __device__ __forceinline__ void body_uv_fused_edge(const DevView &d, int x0, int
         if ((d.xper && i == d.L) || (d.yper && !d.slab && y0 + r == d.M)) {      // orphan column / row: see above
             const int ca = !FIRST_X ? c[q].template nb<3>() : c[q].template nb<1>();
             const ShGlobal sh{d, c[q].ipnt, cb, ca, ilay};
-            uv_core<!FIRST_X, true, true, SF, HM>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
+            uv_core<!FIRST_X, true, true, SF, HM, PLAIN>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
         } else {
             const ShLdsEdge<Q, !FIRST_X> sh{s_f, s_hs, r + 1, lx + 1, d, c[q].ipnt, cb, ilay};
-            uv_core<!FIRST_X, true, true, SF, HM>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
+            uv_core<!FIRST_X, true, true, SF, HM, PLAIN>(c[q], d, ilay, gene, ramp, ctim, 0, io, q0, qb, qa, qd, sh);
         }
     }
 }
 
 // ZV (with PROD): v_cc = v_ll = +0 everywhere — interior workgroups drop the viscous products
 // HM (with PROD): the history-from-Montgomery form — dmx, dmy are not touched (uv_core)
-template <int Q, bool FIRST_X, bool PROD, bool ZV, bool SF, bool HM = false>
+// PLAIN (with PROD, without SF): the unforced form (uv_core)
+template <int Q, bool FIRST_X, bool PROD, bool ZV, bool SF, bool HM = false, bool PLAIN = false>
 __device__ __forceinline__ void uv_fused_workgroup(const DevView &d, double gene, double ramp, double ctim) {
     static_assert(PROD || !HM, "the history-from-Montgomery form exists for the staged (PROD) bodies only");
+    static_assert(!PLAIN || (PROD && !SF), "the plain form exists for the staged (PROD) bodies without the stress fold");
     using G = TileGeom<Q>;
     __shared__ double s_h[G::TY + 1][G::LDX];
     __shared__ UVstage<Q> s_f[PROD ? 4 : 1];                    // (ZV: the interior workgroups use two of them, the edge ones all four)
@@ -1301,14 +1309,16 @@ __device__ __forceinline__ void uv_fused_workgroup(const DevView &d, double gene
     const int ilay = blockIdx.y + 1;
     const bool interior = x0 - 1 >= 2 && x0 + G::TX <= d.L - 2 && y0 - 1 >= 2 && y0 + G::TY <= d.M - 2
                           && y0 - 1 + d.joff >= 2 && y0 + G::TY + d.joff <= d.Mg - 2 && tile_regular(d, x0, y0, G::TY);
-    if (interior && PROD) body_uv_fused_staged<Q, FIRST_X, ZV, SF, HM>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
+    if (interior && PROD) body_uv_fused_staged<Q, FIRST_X, ZV, SF, HM, PLAIN>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
     else if (interior) body_uv_fused<Q, FIRST_X, true, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
-    else if (PROD) body_uv_fused_edge<Q, FIRST_X, SF, HM>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
+    else if (PROD) body_uv_fused_edge<Q, FIRST_X, SF, HM, PLAIN>(d, x0, y0, ilay, gene, ramp, ctim, s_h, s_f, s_hl);
     else body_uv_fused<Q, FIRST_X, false, SF>(d, x0, y0, ilay, gene, ramp, ctim, s_h);
 }
-template <int Q, bool FIRST_X, bool PROD, bool ZV = false, bool HM = false>
+// (PLAIN: its own instantiations for the same reason as the _sf kernels below — the unforced frames must not carry the
+// registers of the forcing they do not have)
+template <int Q, bool FIRST_X, bool PROD, bool ZV = false, bool HM = false, bool PLAIN = false>
 __global__ __launch_bounds__(TileGeom<Q>::BLOCK) void k_uv_fused(DevView d, double gene, double ramp, double ctim) {
-    uv_fused_workgroup<Q, FIRST_X, PROD, ZV, false, HM>(d, gene, ramp, ctim);
+    uv_fused_workgroup<Q, FIRST_X, PROD, ZV, false, HM, PLAIN>(d, gene, ramp, ctim);
 }
 // ... with distribute_stress formed inside (SF): its own kernels, so that the unforced ones do not carry its registers.  Their
 // 64 x 8 u-first zero-viscosity form takes 128 VGPRs and runs four waves per SIMD: wind-driven 4096x2048x2, same box, u+v

@@ -216,6 +216,9 @@ int beom_unpack_rows2(beom_handle h, int nrows, int jlo_a, const void *buffer_a,
  *  "fold_stress" (default 1): with constant layer fractions (ocrp = 0) and a stress refresh on every step (n_3d = 1), steps
  *      after the third form distribute_stress (private_mod.f95:1921-2149) inside the fused update_u/update_v sweep: no
  *      launch of its own, tt3d/tb3d/tu3d neither written nor read (they keep their values of step 1 unless "keep_diag" = 1).
+ *  "plain_sweeps" (default 1): a launch of the fused update_u/update_v sweep whose handle has no nudging, tide, stress, body
+ *      force, lid or svis, and a launch of the fused Montgomery sweep with ocrp = 0, no lid, no h_to and "keep_diag" = 0, take
+ *      the instantiations with those branches compiled out (same statements, same results).  0 = the general ones.
  * Returns -3 for an unknown name. */
 int beom_set_option(beom_handle h, const char *name, int value);
 /* Introspection (>= 0, or -3 for an unknown name): "stress_folded" = the last step formed its stress inside the momentum
@@ -223,7 +226,8 @@ int beom_set_option(beom_handle h, const char *name, int value);
  * sweeps (8 | 4; 0 on the table path); "biharm_tiled" = the biharmonic part of this handle's update_viscosity (svis > 0,
  * private_mod.f95:2508-2599) runs as the tiled sweep k_biharm_tiled (1: every dense or embedded handle with svis > 0) or
  * not (0: the table kernels of a packed handle, and every handle with svis = 0); "uv_fused" = the last step's update_u and
- * update_v ran as the fused sweep (1) or as two sweeps (0; 0 before the first step). */
+ * update_v ran as the fused sweep (1) or as two sweeps (0; 0 before the first step); "plain_sweeps" = which sweeps of the
+ * last step ran their plain form: bit 0 (1) the fused update_u/update_v sweep, bit 1 (2) the fused Montgomery sweep. */
 int beom_info(beom_handle h, const char *what);
 
 /* Run all launches of this handle on the caller's HIP stream (e.g. the stream a

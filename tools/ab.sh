@@ -1,7 +1,7 @@
 #!/bin/bash
-# A/B of two engine builds on the SAME box: ab/prev.so against the in-tree library, alternating
+# A/B of two engine builds on the SAME box: ab/prev.so against the in-tree library, alternating REPS times (default 3)
 R=${GRAFT_REPO_ROOT:-$PWD}; cd /tmp; export TMPDIR=/tmp
-for rep in 1 2 3; do
+for rep in $(seq ${REPS:-3}); do
   for which in prev new; do
     if [ $which = prev ]; then export BEOM_HIP_LIB=$R/ab/prev.so; else unset BEOM_HIP_LIB; fi
     python3 $R/bench.py --steps 40 --warmup 10 --no-cpu-baseline > $R/gpurun_out/ab_$which.log 2>&1

@@ -49,7 +49,11 @@ e = capi.Engine(f, dense_hint=0 if case == "headline_gather" else 1)
 e.step(1, 10)
 t = time.perf_counter(); e.step(11, K); dt = time.perf_counter() - t
 ms, nl = e.profile_steps(11 + K, 50)
+try:
+    plain = e.info("plain_sweeps")      # bit 0: the u+v sweep of the last step ran its plain form, bit 1: the Montgomery sweep
+except capi.BeomError:                  # (an older library named by BEOM_HIP_LIB)
+    plain = None
 names = ("h", "mont", "visc", "u", "v", "mont+visc", "u+v", "mont+visc+u+v")
-print(json.dumps({"case": case, "per_kernel_us": {names[k]: round(ms[k] / 50 * 1e3, 1) for k in range(len(nl)) if nl[k]}, "lm": p.lm, "mm": p.mm, "nlay": p.nlay, "steps": K, "us_per_step": dt / K * 1e6,
+print(json.dumps({"case": case, "plain_sweeps": plain, "per_kernel_us": {names[k]: round(ms[k] / 50 * 1e3, 1) for k in range(len(nl)) if nl[k]}, "lm": p.lm, "mm": p.mm, "nlay": p.nlay, "steps": K, "us_per_step": dt / K * 1e6,
                   "cell_layer_updates_per_s": p.ndeg * p.nlay * K / dt, "dense": e.is_dense,
                   "kernel_us_per_step": round(sum(ms) / 50 * 1e3, 1)}))

@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_floats.h", "beom_dense_host.h",
                os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -217,6 +217,15 @@ def load(path: Optional[str] = None) -> C.CDLL:
         for name in ("beom_set_tracers", "beom_upload_tracers", "beom_download_tracers", "beom_update_tracers",
                      "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers"):
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_floats"):          # (likewise: an older build has no floats)
+        lib.beom_set_floats.argtypes = [H, C.c_int64, ci, ci, cp, ci]
+        lib.beom_upload_floats.argtypes = [H, dpp, dpp, ipp, cp, ci]
+        lib.beom_download_floats.argtypes = [H, dpp, dpp, ipp, ipp, cp, ci]
+        lib.beom_download_float_track.argtypes = [H, dpp, C.POINTER(ci), C.POINTER(ci), cp, ci]
+        lib.beom_update_floats.argtypes = [H, ci]
+        for name in ("beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track",
+                     "beom_update_floats"):
+            getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
                  "beom_multi_stats", "beom_multi_create_ex", "beom_multi_describe", "beom_multi_engine",
@@ -257,7 +266,8 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_integral_count", "beom_integral_rows", "beom_integral_combine", "beom_integrals",
            "beom_multi_integrals", "beom_multi_integral_rows_local",
            "beom_set_tracers", "beom_upload_tracers", "beom_download_tracers", "beom_update_tracers",
-           "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers")
+           "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
+           "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats")
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -341,7 +351,57 @@ class _Tracers:
         return q
 
 
-class Engine(_Tracers):
+class _Floats:
+    """Lagrangian floats of a handle (beom_set_floats, include/beom_hip.h): positions x, y in grid units (cell (i, j) spans
+    [i-1, i] x [j-1, j]), a fixed 1-based layer per float, moved by every step with Heun's method on the layer velocities.
+    Single handles only: a band refuses them."""
+
+    nfloats = 0
+    float_records = 0
+
+    def set_floats(self, x, y, layer, records: int = 0, stride: int = 1):
+        """Replaces the handle's floats by these (arrays of one length; an empty x frees them) and zeroes their `rejected`
+        counters.  records > 0: a recorder of that many records (x, y, h) per float, one behind every step with
+        tstp % stride == 0 (download_float_track).  Between steps only."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        layer = np.ascontiguousarray(np.broadcast_to(np.asarray(layer, dtype=np.int32), x.shape), dtype=np.int32)
+        if y.shape != x.shape:
+            raise BeomError("set_floats: x of %d positions, y of %d" % (x.size, y.size))
+        self._check(self.lib.beom_set_floats(self.h, x.size, int(records), int(stride), self._err, ERRLEN))
+        self.nfloats, self.float_records = 0, 0
+        if x.size:
+            try:
+                self._check(self.lib.beom_upload_floats(self.h, _dp(x), _dp(y), _ip(layer), self._err, ERRLEN))
+            except BeomError:
+                self.lib.beom_set_floats(self.h, 0, 0, 1, None, 0)       # (refused positions: the handle carries no floats)
+                raise
+            self.nfloats, self.float_records = int(x.size), int(records)
+
+    def download_floats(self) -> dict:
+        n = self.nfloats
+        out = {"x": np.zeros(n), "y": np.zeros(n), "layer": np.zeros(n, dtype=np.int32), "rejected": np.zeros(n, dtype=np.int32)}
+        self._check(self.lib.beom_download_floats(self.h, _dp(out["x"]), _dp(out["y"]), _ip(out["layer"]), _ip(out["rejected"]),
+                                                  self._err, ERRLEN))
+        return out
+
+    def download_float_track(self) -> dict:
+        """The records held, oldest first, and empties the recorder: x, y, h [count, nfloats], tstp [count]."""
+        rec = np.zeros((max(self.float_records, 1), 3, self.nfloats))
+        tstp = (C.c_int * max(self.float_records, 1))()
+        count = C.c_int(0)
+        self._check(self.lib.beom_download_float_track(self.h, _dp(rec), C.byref(count), tstp, self._err, ERRLEN))
+        k = count.value
+        return {"x": rec[:k, 0].copy(), "y": rec[:k, 1].copy(), "h": rec[:k, 2].copy(), "tstp": np.array(list(tstp)[:k], dtype=np.int64)}
+
+    def update_floats(self, stage: int):
+        """Per-sweep entry: stage 1 or stage 2 of the scheme on the velocities as they stand (no record)."""
+        rc = self.lib.beom_update_floats(self.h, int(stage))
+        if rc != 0:
+            raise BeomError("beom_update_floats(stage %d) = %d (floats set and uploaded? stage 1 or 2?)" % (stage, rc))
+
+
+class Engine(_Tracers, _Floats):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
@@ -503,7 +563,8 @@ class Engine(_Tracers):
         """beom_info: "stress_folded" (the last step formed its stress inside the momentum sweep: tt3d, tb3d, tu3d are
         then not kept current), "tile_rows", "biharm_tiled" (1: the handle's biharmonic viscosity, svis > 0, runs as the tiled
         sweep; 0 on the table path and with svis = 0), "uv_fused" (1: the last step's momentum ran as the fused u+v sweep),
-        "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did)."""
+        "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did), "tracers", "floats",
+        "float_records" (records the track recorder holds), "float_launches" (float launches so far)."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))

@@ -18,6 +18,7 @@
 #include "beom_kernels.h"
 #include "beom_integrals.h"
 #include "beom_tracers.h"
+#include "beom_floats.h"
 #include "beom_dense_host.h"
 
 namespace {
@@ -132,6 +133,19 @@ struct beom_engine {
     int ntrc = 0;
     double *trc_q = nullptr, *trc_q_alt = nullptr, *trc_rq[2] = {nullptr, nullptr}, *trc_ctrg = nullptr;
     std::vector<void *> trc_allocs;
+    // Lagrangian floats (beom_set_floats; beom_floats.h): positions, layers, rejected steps, stage 1's increment and
+    // provisional position; the track recorder [record][3][float] with the step of every held record
+    long long nflt = 0;
+    bool flt_ready = false;            // positions have been uploaded
+    double *flt_x = nullptr, *flt_y = nullptr, *flt_k1x = nullptr, *flt_k1y = nullptr, *flt_xs = nullptr, *flt_ys = nullptr;
+    int32_t *flt_layer = nullptr, *flt_rej = nullptr;
+    unsigned long long *flt_first_dry = nullptr;
+    double *flt_rec = nullptr;
+    int flt_nrec = 0, flt_stride = 1;
+    std::vector<int> flt_rec_tstp;     // (its size = the records held)
+    long long flt_launches = 0;        // beom_info "float_launches"
+    bool cellmap_known = false;        // integ_cellmap (table path) and integ_xper / integ_yper are set
+    std::vector<void *> flt_allocs;
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -447,6 +461,7 @@ int beom_destroy(beom_handle E) {
     if (E->stream) (void)hipStreamSynchronize(E->stream);
     for (void *p : E->allocs) (void)hipFree(p);
     for (void *p : E->trc_allocs) (void)hipFree(p);
+    for (void *p : E->flt_allocs) (void)hipFree(p);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -695,6 +710,31 @@ static void launch_tracers(beom_engine *E, double gene, double ramp, double ctim
     else LAUNCH_CTX((k_tracers<CellGather, 0>), (k_tracers<CellDense, 0>), nz, E->d, tv, gene, ramp, ctim);
     swp(E->trc_q, E->trc_q_alt);
     rot2(E->trc_rq);
+}
+// a float launch (beom_floats.h): mode 1 = stage 1, 2 = stage 2, 3 = stage 2 then stage 1; rec: the record stage 2 writes
+static FloatView float_view(const beom_engine *E, double *rec) {
+    const DevView &d = E->d;
+    return FloatView{E->nflt, E->flt_x, E->flt_y, E->flt_layer, E->flt_rej, E->flt_k1x, E->flt_k1y, E->flt_xs, E->flt_ys,
+                     E->integ_cellmap, d.dt * d.i_dl, (double)d.lm, (double)d.mm, E->integ_xper, E->integ_yper, rec};
+}
+static void launch_floats(beom_engine *E, int mode, double *rec) {
+    const DevView &d = E->d;
+    const FloatView f = float_view(E, rec);
+    const dim3 g((unsigned)((E->nflt + BEOM_BLOCK - 1) / BEOM_BLOCK)), b(BEOM_BLOCK);
+#define FLT_GO(m) do { if (E->dense) hipLaunchKernelGGL((k_floats<CellDense, m>), g, b, 0, E->stream, d, f); \
+                       else hipLaunchKernelGGL((k_floats<CellGather, m>), g, b, 0, E->stream, d, f); } while (0)
+    if (mode == 1) FLT_GO(1); else if (mode == 2) FLT_GO(2); else FLT_GO(3);
+#undef FLT_GO
+    ++E->flt_launches;
+}
+// stage 2 of step tstp (then stage 1 of the next step if `then_stage1`), with the step's record if it is due
+static void launch_floats_after(beom_engine *E, int tstp, bool then_stage1) {
+    double *rec = nullptr;
+    if (E->flt_nrec > 0 && tstp % E->flt_stride == 0 && (int)E->flt_rec_tstp.size() < E->flt_nrec) {
+        rec = E->flt_rec + 3 * (size_t)E->nflt * E->flt_rec_tstp.size();
+        E->flt_rec_tstp.push_back(tstp);
+    }
+    launch_floats(E, then_stage1 ? 3 : 2, rec);
 }
 template <class CTX>
 static bool launch_mont_all(beom_engine *E) {
@@ -975,7 +1015,11 @@ static bool mont_hist_step(const beom_engine *E, const StepScalars &s) {
            E->mont_levels_valid >= 3;
 }
 
-static void one_step(beom_engine *E, int tstp, const StepScalars &s) {
+// flt: -1 = the handle carries no floats; else bit 0 = the first step of its beom_step call, bit 1 = the last.  The float
+// launches sit at the top and at the very end: stage 1 alone in front of the call's first step, stage 2 (+ the next step's
+// stage 1, on the same velocities) behind every step.
+static void one_step(beom_engine *E, int tstp, const StepScalars &s, int flt = -1) {
+    if (flt >= 0 && (flt & 1)) launch_floats(E, 1, nullptr);
     const bool hm = mont_hist_step(E, s);
     if (!hm) (void)hist_sync(E);                                   // a step on the arrays: bring them up to date first
     rotate_mont(E);                                                // the one place d.mont moves to its next buffer
@@ -1000,6 +1044,7 @@ static void one_step(beom_engine *E, int tstp, const StepScalars &s) {
     }
     if (E->lid) { launch_lid_fluxes(E, s.first3); launch_lid_pressure(E); }       // :2206-2222, 2290-2316
     E->d.stress_fold = 0;
+    if (flt >= 0) launch_floats_after(E, tstp, !(flt & 2));
 }
 
 // rows [jlo, jlo+nrows) of hlay,u,v,h_u,h_v  ->  dbuf (device memory, 5*nlay*nrows*(lm+1) doubles); the *2 forms move a second
@@ -1027,9 +1072,23 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
     if (tstp_first < 1 || nsteps < 0 || n_3d < 1) { set_err(errm, errm_len, "beom_step: bad arguments"); return -3; }
     if (E->P.flag_nudging && E->P.mcbc < 0.5 && !E->obc && !E->obc_set) { set_err(errm, errm_len, "beom_step: mcbc = 0 with nudging needs beom_set_open_boundaries (no_gradient_obc, private_mod.f95:2613-2679)"); return -6; }
     if (E->lid && !E->lid_ready) { set_err(errm, errm_len, "beom_step: rgld = 1 needs beom_set_rigid_lid (the Poisson operators Ow, Os, Osum_ and the lid pressure, private_mod.f95:505-563)"); return -6; }
+    const bool flt = E->nflt > 0;
+    if (flt && !E->flt_ready) { set_err(errm, errm_len, "beom_step: the handle's %lld floats have no positions yet (beom_upload_floats)", E->nflt); return -3; }
+    if (flt && E->flt_nrec > 0) {          // the recorder must hold every record of the call: refused before anything is launched
+        long long due = 0;
+        for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp) due += tstp % E->flt_stride == 0;
+        const long long held = (long long)E->flt_rec_tstp.size();
+        if (held + due > E->flt_nrec) {
+            set_err(errm, errm_len, "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
+                    "empty it with beom_download_float_track, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
+                    E->flt_stride, held, E->flt_nrec);
+            return -3;
+        }
+    }
     HIP_TRY(hipSetDevice(E->device));
     for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp)
-        one_step(E, tstp, step_scalars(E, tstp, tres, dtd8, dt_r, rsta, n_3d));
+        one_step(E, tstp, step_scalars(E, tstp, tres, dtd8, dt_r, rsta, n_3d),
+                 flt ? (tstp == tstp_first ? 1 : 0) | (tstp == tstp_first + nsteps - 1 ? 2 : 0) : -1);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1217,6 +1276,29 @@ static int pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 int beom_integral_count(int nlay) { return 4 * nlay + 1; }
 
+// Whether the frame wraps (integ_xper, integ_yper) and, on the table path, the packed cell of every (i, j) (integ_cellmap):
+// built on the first use by the integrals or by the floats.
+static int ensure_cellmap(beom_engine *E, char *errm, int errm_len) {
+    if (E->cellmap_known) return 0;
+    DevView &d = E->d;
+    E->integ_xper = d.xper; E->integ_yper = d.yper;
+    if (!E->dense) {
+        int32_t *flags = nullptr;
+        HIP_TRY(hipMalloc((void **)&E->integ_cellmap, ((size_t)d.L * d.M + 2) * sizeof(int32_t)));
+        E->allocs.push_back(E->integ_cellmap);
+        HIP_TRY(hipMemsetAsync(E->integ_cellmap, 0, ((size_t)d.L * d.M + 2) * sizeof(int32_t), E->stream));
+        flags = E->integ_cellmap + (size_t)d.L * d.M;
+        hipLaunchKernelGGL(k_integral_cellmap, dim3((unsigned)((d.ndeg + BEOM_BLOCK - 1) / BEOM_BLOCK)), dim3(BEOM_BLOCK), 0, E->stream,
+                           d, E->integ_cellmap, flags);
+        int32_t fl[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, E->stream));
+        HIP_TRY(hipStreamSynchronize(E->stream));
+        E->integ_xper = fl[0]; E->integ_yper = fl[1];
+    }
+    E->cellmap_known = true;
+    return 0;
+}
+
 int beom_integral_rows(beom_handle E, int jlo, int nrows, double *rows, char *errm, int errm_len) {
     if (!E || !rows) { set_err(errm, errm_len, "beom_integral_rows: null argument"); return -1; }
     DevView &d = E->d;
@@ -1230,21 +1312,8 @@ int beom_integral_rows(beom_handle E, int jlo, int nrows, double *rows, char *er
         E->allocs.push_back(E->integ_part);
         HIP_TRY(hipMalloc((void **)&E->integ_rows, (size_t)d.M * count * sizeof(double)));
         E->allocs.push_back(E->integ_rows);
-        E->integ_xper = d.xper; E->integ_yper = d.yper;
-        if (!E->dense) {
-            int32_t *flags = nullptr;
-            HIP_TRY(hipMalloc((void **)&E->integ_cellmap, ((size_t)d.L * d.M + 2) * sizeof(int32_t)));
-            E->allocs.push_back(E->integ_cellmap);
-            HIP_TRY(hipMemsetAsync(E->integ_cellmap, 0, ((size_t)d.L * d.M + 2) * sizeof(int32_t), E->stream));
-            flags = E->integ_cellmap + (size_t)d.L * d.M;
-            hipLaunchKernelGGL(k_integral_cellmap, dim3((unsigned)((d.ndeg + BEOM_BLOCK - 1) / BEOM_BLOCK)), dim3(BEOM_BLOCK), 0, E->stream,
-                               d, E->integ_cellmap, flags);
-            int32_t fl[2] = {0, 0};
-            HIP_TRY(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, E->stream));
-            HIP_TRY(hipStreamSynchronize(E->stream));
-            E->integ_xper = fl[0]; E->integ_yper = fl[1];
-        }
     }
+    if (const int rc = ensure_cellmap(E, errm, errm_len)) return rc;
     const dim3 g((unsigned)nch, (unsigned)((nrows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
     if (E->dense) hipLaunchKernelGGL(k_integral_rows<true>, g, b, 0, E->stream, d, jlo, nrows, width, E->integ_xper, E->integ_yper,
                                      (const int32_t *)nullptr, E->integ_part);
@@ -1345,6 +1414,137 @@ int beom_download_tracers(beom_handle E, double *q, double *rq, char *errm, int 
     return 0;
 }
 
+// ---- Lagrangian floats (beom_floats.h) -------------------------------------------------------------------------------------
+static void free_floats(beom_engine *E) {
+    for (void *p : E->flt_allocs) (void)hipFree(p);
+    E->flt_allocs.clear();
+    E->nflt = 0; E->flt_ready = false; E->flt_nrec = 0; E->flt_stride = 1;
+    E->flt_rec_tstp.clear();
+    E->flt_x = E->flt_y = E->flt_k1x = E->flt_k1y = E->flt_xs = E->flt_ys = E->flt_rec = nullptr;
+    E->flt_layer = E->flt_rej = nullptr;
+    E->flt_first_dry = nullptr;
+}
+// a zeroed device array of n elements of `size` bytes
+static int alloc_float_array(beom_engine *E, void *p, size_t n, size_t size, char *errm, int errm_len) {
+    void *q = nullptr;
+    HIP_TRY(hipMalloc(&q, n * size));
+    E->flt_allocs.push_back(q);
+    HIP_TRY(hipMemsetAsync(q, 0, n * size, E->stream));
+    *(void **)p = q;
+    return 0;
+}
+
+int beom_set_floats(beom_handle E, int64_t n, int nrec, int stride, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (n < 0 || nrec < 0 || stride < 1) { set_err(errm, errm_len, "beom_set_floats: %lld floats, %d records, stride %d (n >= 0, nrec >= 0, stride >= 1)", (long long)n, nrec, stride); return -3; }
+    if (n > 0 && (double)n * 3.0 * (double)std::max(nrec, 1) >= 9.0e15) { set_err(errm, errm_len, "beom_set_floats: %lld floats x %d records is too much", (long long)n, nrec); return -3; }
+    if (n > 0 && E->d.slab) {
+        set_err(errm, errm_len, "beom_set_floats: this handle holds one band of rows (slab_mm = %d): a float leaves its band, and floats do not "
+                "migrate between devices yet; carry them on a single handle of the whole frame", E->P.slab_mm);
+        return -6;
+    }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    free_floats(E);
+    if (n == 0) return 0;
+    int rc = ensure_cellmap(E, errm, errm_len);
+    if (rc) return rc;
+    E->nflt = (long long)n;
+    const size_t m = (size_t)n;
+    for (double **a : {&E->flt_x, &E->flt_y, &E->flt_k1x, &E->flt_k1y, &E->flt_xs, &E->flt_ys})
+        if ((rc = alloc_float_array(E, a, m, sizeof(double), errm, errm_len))) { free_floats(E); return rc; }
+    for (int32_t **a : {&E->flt_layer, &E->flt_rej})
+        if ((rc = alloc_float_array(E, a, m, sizeof(int32_t), errm, errm_len))) { free_floats(E); return rc; }
+    if ((rc = alloc_float_array(E, &E->flt_first_dry, 1, sizeof(unsigned long long), errm, errm_len))) { free_floats(E); return rc; }
+    if (nrec > 0 && (rc = alloc_float_array(E, &E->flt_rec, 3 * m * (size_t)nrec, sizeof(double), errm, errm_len))) { free_floats(E); return rc; }
+    E->flt_nrec = nrec; E->flt_stride = stride;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int beom_upload_floats(beom_handle E, const double *x, const double *y, const int32_t *layer, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->nflt < 1) { set_err(errm, errm_len, "beom_upload_floats: the handle carries no float (beom_set_floats)"); return -3; }
+    if (!x || !y || !layer) { set_err(errm, errm_len, "beom_upload_floats: null array"); return -1; }
+    HIP_TRY(hipSetDevice(E->device));
+    const DevView &d = E->d;
+    const size_t n = (size_t)E->nflt;
+    long long bad_layer = -1;
+    for (size_t t = 0; t < n && bad_layer < 0; ++t)
+        if (layer[t] < 1 || layer[t] > d.nlay) bad_layer = (long long)t;
+    // the candidates go to the scratch of stage 1; the floats the handle holds are replaced only if every one is accepted
+    const unsigned long long none = ~0ull;
+    unsigned long long first_dry = none;
+    HIP_TRY(hipMemcpyAsync(E->flt_xs, x, n * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_ys, y, n * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_first_dry, &none, sizeof(none), hipMemcpyHostToDevice, E->stream));
+    const FloatView f = float_view(E, nullptr);
+    const dim3 g((unsigned)((E->nflt + BEOM_BLOCK - 1) / BEOM_BLOCK)), b(BEOM_BLOCK);
+    if (E->dense) hipLaunchKernelGGL(k_floats_check<CellDense>, g, b, 0, E->stream, d, f, E->flt_first_dry);
+    else hipLaunchKernelGGL(k_floats_check<CellGather>, g, b, 0, E->stream, d, f, E->flt_first_dry);
+    HIP_TRY(hipMemcpyAsync(&first_dry, E->flt_first_dry, sizeof(first_dry), hipMemcpyDeviceToHost, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    if (bad_layer >= 0 && (first_dry == none || (unsigned long long)bad_layer <= first_dry)) {
+        set_err(errm, errm_len, "beom_upload_floats: float %lld has layer %d, outside 1..%d (nothing uploaded)", bad_layer, (int)layer[bad_layer], d.nlay);
+        return -3;
+    }
+    if (first_dry != none) {
+        const double px = x[first_dry], py = y[first_dry];
+        set_err(errm, errm_len, "beom_upload_floats: float %llu at (%.17g, %.17g) does not start in a wet cell: cell (%.0f, %.0f) of the "
+                "%d x %d frame is dry, land or outside (nothing uploaded)", first_dry, px, py, std::floor(px) + 1.0, std::floor(py) + 1.0, d.lm, d.mm);
+        return -3;
+    }
+    HIP_TRY(hipMemcpyAsync(E->flt_x, E->flt_xs, n * sizeof(double), hipMemcpyDeviceToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_y, E->flt_ys, n * sizeof(double), hipMemcpyDeviceToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_layer, layer, n * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipMemsetAsync(E->flt_rej, 0, n * sizeof(int32_t), E->stream));
+    HIP_TRY(hipMemsetAsync(E->flt_k1x, 0, n * sizeof(double), E->stream));
+    HIP_TRY(hipMemsetAsync(E->flt_k1y, 0, n * sizeof(double), E->stream));
+    E->flt_rec_tstp.clear();
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    E->flt_ready = true;
+    return 0;
+}
+
+int beom_download_floats(beom_handle E, double *x, double *y, int32_t *layer, int32_t *rejected, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->nflt < 1) { set_err(errm, errm_len, "beom_download_floats: the handle carries no float (beom_set_floats)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t n = (size_t)E->nflt;
+    if (x) HIP_TRY(hipMemcpyAsync(x, E->flt_x, n * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    if (y) HIP_TRY(hipMemcpyAsync(y, E->flt_y, n * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    if (layer) HIP_TRY(hipMemcpyAsync(layer, E->flt_layer, n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    if (rejected) HIP_TRY(hipMemcpyAsync(rejected, E->flt_rej, n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int beom_download_float_track(beom_handle E, double *rec, int *count, int *tstp_of_record, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->nflt < 1 || E->flt_nrec < 1) { set_err(errm, errm_len, "beom_download_float_track: the handle has no track recorder (beom_set_floats with nrec > 0)"); return -3; }
+    if (!count) { set_err(errm, errm_len, "beom_download_float_track: null count"); return -1; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t held = E->flt_rec_tstp.size();
+    if (held && !rec) { set_err(errm, errm_len, "beom_download_float_track: %d records held and no array to put them in", (int)held); return -1; }
+    if (held) HIP_TRY(hipMemcpyAsync(rec, E->flt_rec, held * 3 * (size_t)E->nflt * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    *count = (int)held;
+    if (tstp_of_record) for (size_t k = 0; k < held; ++k) tstp_of_record[k] = E->flt_rec_tstp[k];
+    E->flt_rec_tstp.clear();
+    return 0;
+}
+
+int beom_update_floats(beom_handle E, int stage) {
+    if (!E) return -1;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    if (E->nflt < 1 || !E->flt_ready || (stage != 1 && stage != 2)) return -3;
+    launch_floats(E, stage, nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)
 // of nudged open-boundary segments, Fortran storage.  Activates no_gradient_obc after the
 // momentum sweeps of every step when flag_nudging and mcbc < 0.5 (:2201-2204, 2285-2288).
@@ -1410,6 +1610,9 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "mont_history")) return E->last_mont_hist ? 1 : 0;
     if (!strcmp(what, "plain_sweeps")) return E->last_plain;
     if (!strcmp(what, "tracers")) return E->ntrc;
+    if (!strcmp(what, "floats")) return (int)std::min<long long>(E->nflt, 2000000000ll);
+    if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
+    if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far
     if (!strcmp(what, "lid_sweeps")) return (int)std::min<long long>(E->lid_sweeps, 2000000000ll);        // Gauss-Seidel sweeps kept, all steps so far
     if (!strcmp(what, "lid_solves")) return (int)std::min<long long>(E->lid_solves, 2000000000ll);
     if (!strcmp(what, "lid_launches")) return (int)std::min<long long>(E->lid_launches, 2000000000ll);

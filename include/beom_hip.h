@@ -295,6 +295,46 @@ int beom_upload_tracers(beom_handle h, const double *q, const double *rq, const 
 int beom_download_tracers(beom_handle h, double *q, double *rq, char *errm, int errm_len);
 int beom_update_tracers(beom_handle h, double gene, double ramp, double ctim);
 
+/* ---- Lagrangian (isopycnal) floats carried by the layer velocities (no reference routine; DESIGN.md f-N7).  A float has a
+ * position (x, y) in FP64 grid units and a fixed layer l.  Cell (i, j) spans [i-1, i] x [j-1, j]; u(p) sits on the cell's west
+ * face and v(p) on its south face; E = neig(1, p), N = neig(3, p).  cell(x, y) is the packed cell of i = floor(x)+1,
+ * j = floor(y)+1, or 0 if (i, j) lies outside 1..lm+1 x 1..mm+1 or holds no packed cell; wet(x, y) means
+ * mk_n(cell(x, y)) > 0.5.  xper (yper): the frame wraps in x (y) — some cell of column (row) 1 has a W (S) neighbour.
+ * The velocity at a position is linear between the two faces of the home cell, each component along its own axis only (the
+ * usual C-grid float interpolation: the wall-normal velocity is exactly the stored masked zero on a coast face).  All
+ * arithmetic FP64, in this order, no contraction:
+ *   fx = floor(x); a = x - fx;   fy = floor(y); b = y - fy;   p = cell(x, y)
+ *   U(x,y) = (1.0 - a)*u(p,l) + a*u(E,l)        V(x,y) = (1.0 - b)*v(p,l) + b*v(N,l)
+ *   cdt = dt * i_dl     (formed once on the host; i_dl is the engine's own 1.0/dl)
+ *   wrapx(z): if xper { if (z < 0.0) z = z + lm; if (z >= lm) z = z - lm }     (wrapy alike with mm, yper)
+ * A step is Heun's method on the velocities before and after that step's momentum update:
+ *   stage 1 (u, v as they stand when the step begins):
+ *     k1 = (U, V)(x, y)*cdt;  (xs, ys) = (wrapx(x + k1x), wrapy(y + k1y));  if !wet(xs, ys) then (xs, ys) = (x, y)
+ *   stage 2 (u, v as the step leaves them: after the open-boundary pass and, with a lid, after the pressure correction):
+ *     k2 = (U, V)(xs, ys)*cdt;  xn = wrapx(x + 0.5*(k1x + k2x)), yn alike
+ *   landing rule: the float takes the first wet candidate of (xn, yn), (xn, y), (x, yn), (x, y); the per-float counter
+ *     `rejected` counts the steps whose first candidate was not taken.
+ * So a float that starts in a wet cell is in a wet cell after every step, by construction.  Neighbours come from the handle's
+ * own connectivity, so periodic seams behave as for every other sweep; a position is wrapped, so the duplicated column lm+1 /
+ * row mm+1 of a periodic frame is never a home cell.
+ *
+ * beom_set_floats allocates n floats (n = 0 frees them; between steps only) and a track recorder of nrec records (0 = none):
+ * behind stage 2 of every step with tstp % stride == 0, beom_step keeps (x, y, h) of every float on the device, h = hlay of
+ * the home cell as the step leaves it.  It refuses (-6) handles that hold one band of rows (slab_mm != 0): a float leaves
+ * its band.  beom_upload_floats sets positions and layers (1-based), zeroes `rejected` and empties the recorder; it refuses
+ * (-3, naming the first offender, the handle's floats untouched) a layer outside 1..nlay and a position whose cell is not
+ * wet.  beom_step then moves the floats: K steps of one call cost K + 1 float launches (stage 2 of a step and stage 1 of
+ * the next read the same velocities); it refuses (-3), before launching anything, a call whose steps would write more
+ * records than the recorder has free.  beom_download_floats: any pointer may be NULL.  beom_download_float_track copies
+ * the held records, rec[(k*3 + c)*n + f] (record k; c = 0, 1, 2: x, y, h; float f), their number and steps, and empties
+ * the recorder; rec needs room for nrec records.  beom_update_floats is the per-sweep entry (stage = 1 | 2, on the state as it
+ * stands; writes no record).  beom_info: "floats" (the count), "float_records" (held), "float_launches" (so far). */
+int beom_set_floats(beom_handle h, int64_t n, int nrec, int stride, char *errm, int errm_len);
+int beom_upload_floats(beom_handle h, const double *x, const double *y, const int32_t *layer, char *errm, int errm_len);
+int beom_download_floats(beom_handle h, double *x, double *y, int32_t *layer, int32_t *rejected, char *errm, int errm_len);
+int beom_download_float_track(beom_handle h, double *rec, int *count, int *tstp_of_record, char *errm, int errm_len);
+int beom_update_floats(beom_handle h, int stage);
+
 /* ---- Conservation integrals of the state as it stands between two steps (no reference routine: the reference's test
  * case 3 forms them from the output files, testcases/conservation.m:116-211).  All FP64, raw sums over the frame:
  *   out[(l-1)*4 + 0]  vol   sum of mk_n*h                                    layer volume / dl^2

@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_floats.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_floats.h", "beom_moments.h", "beom_dense_host.h",
                os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -226,6 +226,18 @@ def load(path: Optional[str] = None) -> C.CDLL:
         for name in ("beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track",
                      "beom_update_floats"):
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_moments"):         # (likewise: an older build has no moments)
+        llp = C.POINTER(C.c_longlong)
+        lib.beom_set_moments.argtypes = [H, ci, ci, cp, ci]
+        lib.beom_reset_moments.argtypes = [H]
+        lib.beom_sample_moments.argtypes = [H]
+        lib.beom_download_moments.argtypes = [H, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
+        lib.beom_multi_set_moments.argtypes = [MH, ci, ci, cp, ci]
+        lib.beom_multi_reset_moments.argtypes = [MH, cp, ci]
+        lib.beom_multi_download_moments.argtypes = [MH, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
+        for name in ("beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
+                     "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments"):
+            getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
                  "beom_multi_stats", "beom_multi_create_ex", "beom_multi_describe", "beom_multi_engine",
@@ -267,7 +279,9 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_integrals", "beom_multi_integral_rows_local",
            "beom_set_tracers", "beom_upload_tracers", "beom_download_tracers", "beom_update_tracers",
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
-           "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats")
+           "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
+           "beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
+           "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments")
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -401,7 +415,54 @@ class _Floats:
             raise BeomError("beom_update_floats(stage %d) = %d (floats set and uploaded? stage 1 or 2?)" % (stage, rc))
 
 
-class Engine(_Tracers, _Floats):
+MOMENT_FIELDS = ("hlay", "u", "v", "h_u", "h_v")
+MOMENT_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 3), (2, 4))      # the five second moments: (h,h) (u,u) (v,v) (u,h_u) (v,h_v)
+
+
+class _Moments:
+    """Time means and second moments of the layer fields (beom_set_moments, include/beom_hip.h): sums shifted by the first
+    sample, kept on the device and fed behind every step with tstp % stride == 0.  Shared by Engine and MultiEngine."""
+
+    _mom_multi = False
+    moment_level = 0
+
+    def set_moments(self, level: int, stride: int = 1):
+        """level 1: ref, sum of hlay, u, v; 2: and of h_u, h_v; 3: and the five second moments; 0 frees.  Between steps only."""
+        fn = self.lib.beom_multi_set_moments if self._mom_multi else self.lib.beom_set_moments
+        self._check(fn(self.h, int(level), int(stride), self._err, ERRLEN))
+        self.moment_level = int(level)
+
+    def reset_moments(self):
+        """count = 0: the next sample is a first sample (no memory moves)."""
+        if self._mom_multi:
+            self._check(self.lib.beom_multi_reset_moments(self.h, self._err, ERRLEN))
+        else:
+            rc = self.lib.beom_reset_moments(self.h)
+            if rc != 0:
+                raise BeomError("beom_hip error %d: beom_reset_moments (moments set?)" % rc)
+
+    def download_moments(self) -> dict:
+        """count, tstp_first, tstp_last; the raw ref, sum [fields, nlay, ndeg+1] and, at level 3, sq [5, nlay, ndeg+1]; the
+        derived mean = ref + sum/count and, at level 3, var = sq/count - (sum_a/count)*(sum_b/count) (var[0..2] the variances
+        of hlay, u, v; var[3..4] the covariances of (u, h_u), (v, h_v))."""
+        lv = self.moment_level
+        nf = 5 if lv >= 2 else 3
+        shape = (self.p.nlay, self.p.ndeg + 1)
+        ref, sm = np.zeros((nf,) + shape), np.zeros((nf,) + shape)
+        sq = np.zeros((5,) + shape) if lv >= 3 else None
+        count, t0, t1 = C.c_longlong(0), C.c_int(0), C.c_int(0)
+        fn = self.lib.beom_multi_download_moments if self._mom_multi else self.lib.beom_download_moments
+        self._check(fn(self.h, _dp(ref), _dp(sm), _dp(sq), C.byref(count), C.byref(t0), C.byref(t1), self._err, ERRLEN))
+        out = {"count": int(count.value), "tstp_first": int(t0.value), "tstp_last": int(t1.value), "ref": ref, "sum": sm}
+        n = float(max(out["count"], 1))
+        out["mean"] = ref + sm / n
+        if sq is not None:
+            out["sq"] = sq
+            out["var"] = np.stack([sq[m] / n - (sm[a] / n) * (sm[b] / n) for m, (a, b) in enumerate(MOMENT_PAIRS)])
+        return out
+
+
+class Engine(_Tracers, _Floats, _Moments):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
@@ -564,7 +625,8 @@ class Engine(_Tracers, _Floats):
         then not kept current), "tile_rows", "biharm_tiled" (1: the handle's biharmonic viscosity, svis > 0, runs as the tiled
         sweep; 0 on the table path and with svis = 0), "uv_fused" (1: the last step's momentum ran as the fused u+v sweep),
         "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did), "tracers", "floats",
-        "float_records" (records the track recorder holds), "float_launches" (float launches so far)."""
+        "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
+        "moment_samples", "moment_launches"."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))
@@ -619,11 +681,17 @@ class Engine(_Tracers, _Floats):
     def update_viscosity(self, ilay=0): self._check(self.lib.beom_update_viscosity(self.h, ilay))
     def update_u(self, ilay, gene, ramp, ctim): self._check(self.lib.beom_update_u(self.h, ilay, gene, ramp, ctim))
     def update_v(self, ilay, gene, ramp, ctim): self._check(self.lib.beom_update_v(self.h, ilay, gene, ramp, ctim))
+    def sample_moments(self):
+        """Per-sweep entry: one sample of the state as it stands, whatever the stride."""
+        rc = self.lib.beom_sample_moments(self.h)
+        if rc != 0:
+            raise BeomError("beom_hip error %d: beom_sample_moments (moments set?)" % rc)
+
     def rebuild_fluxes(self): self._check(self.lib.beom_rebuild_fluxes(self.h))
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers):
+class MultiEngine(_Tracers, _Moments):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""
@@ -652,6 +720,7 @@ class MultiEngine(_Tracers):
 
     _check = Engine._check
     _trc_prefix = "beom_multi_"
+    _mom_multi = True
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:

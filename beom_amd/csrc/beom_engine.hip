@@ -19,6 +19,7 @@
 #include "beom_integrals.h"
 #include "beom_tracers.h"
 #include "beom_floats.h"
+#include "beom_moments.h"
 #include "beom_dense_host.h"
 
 namespace {
@@ -146,6 +147,16 @@ struct beom_engine {
     long long flt_launches = 0;        // beom_info "float_launches"
     bool cellmap_known = false;        // integ_cellmap (table path) and integ_xper / integ_yper are set
     std::vector<void *> flt_allocs;
+    // moments (beom_set_moments; beom_moments.h): per field the reference, the shifted sum and, at level 3, the shifted
+    // second moment, in arrays of the state's shape; the steps of the first and the latest sample
+    int mom_level = 0, mom_stride = 1;
+    bool mom_by_caller = false;        // option "moments_by_caller": beom_step takes no sample by itself
+    long long mom_count = 0, mom_launches = 0;
+    int mom_first = 0, mom_last = 0;
+    int last_tstp = 0;                 // the last step taken (beom_step, beom_step_phase)
+    double *mom_ref[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *mom_sum[5] = {nullptr, nullptr, nullptr, nullptr, nullptr},
+           *mom_sq[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<void *> mom_allocs;
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -462,6 +473,7 @@ int beom_destroy(beom_handle E) {
     for (void *p : E->allocs) (void)hipFree(p);
     for (void *p : E->trc_allocs) (void)hipFree(p);
     for (void *p : E->flt_allocs) (void)hipFree(p);
+    for (void *p : E->mom_allocs) (void)hipFree(p);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -735,6 +747,24 @@ static void launch_floats_after(beom_engine *E, int tstp, bool then_stage1) {
         E->flt_rec_tstp.push_back(tstp);
     }
     launch_floats(E, then_stage1 ? 3 : 2, rec);
+}
+// one sample of the moments (beom_moments.h) of the fields as they stand, recorded under step tstp
+static void launch_moments(beom_engine *E, int tstp) {
+    const DevView &d = E->d;
+    double *const *r = E->mom_ref, *const *s = E->mom_sum, *const *q = E->mom_sq;
+    const MomentView m{(long long)d.nlay * d.n1, d.hlay, d.u, d.v, d.h_u, d.h_v, r[0], r[1], r[2], r[3], r[4],
+                       s[0], s[1], s[2], s[3], s[4], q[0], q[1], q[2], q[3], q[4]};
+    const long long pairs = (m.n - 1) / 2;
+    const dim3 g((unsigned)std::max<long long>(1, std::min<long long>((pairs + BEOM_BLOCK - 1) / BEOM_BLOCK, 2048))), b(BEOM_BLOCK);
+    const bool first = E->mom_count == 0;
+#define MOM_GO(lv) do { if (first) hipLaunchKernelGGL((k_moments<lv, true>), g, b, 0, E->stream, m); \
+                        else hipLaunchKernelGGL((k_moments<lv, false>), g, b, 0, E->stream, m); } while (0)
+    if (E->mom_level == 1) MOM_GO(1); else if (E->mom_level == 2) MOM_GO(2); else MOM_GO(3);
+#undef MOM_GO
+    if (first) E->mom_first = tstp;
+    E->mom_last = tstp;
+    ++E->mom_count;
+    ++E->mom_launches;
 }
 template <class CTX>
 static bool launch_mont_all(beom_engine *E) {
@@ -1045,6 +1075,8 @@ static void one_step(beom_engine *E, int tstp, const StepScalars &s, int flt = -
     if (E->lid) { launch_lid_fluxes(E, s.first3); launch_lid_pressure(E); }       // :2206-2222, 2290-2316
     E->d.stress_fold = 0;
     if (flt >= 0) launch_floats_after(E, tstp, !(flt & 2));
+    E->last_tstp = tstp;
+    if (E->mom_level > 0 && !E->mom_by_caller && tstp % E->mom_stride == 0) launch_moments(E, tstp);
 }
 
 // rows [jlo, jlo+nrows) of hlay,u,v,h_u,h_v  ->  dbuf (device memory, 5*nlay*nrows*(lm+1) doubles); the *2 forms move a second
@@ -1184,6 +1216,7 @@ int beom_step_phase(beom_handle E, int tstp, double tres, double dtd8, double dt
     }
     set_rows(d, 1, 1, M);
     d.stress_fold = 0;
+    E->last_tstp = tstp;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1545,6 +1578,88 @@ int beom_update_floats(beom_handle E, int stage) {
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
+// ---- moments (beom_moments.h) ----------------------------------------------------------------------------------------------
+static void free_moments(beom_engine *E) {
+    for (void *p : E->mom_allocs) (void)hipFree(p);
+    E->mom_allocs.clear();
+    E->mom_level = 0; E->mom_stride = 1; E->mom_count = 0; E->mom_first = E->mom_last = 0;
+    for (int f = 0; f < 5; ++f) E->mom_ref[f] = E->mom_sum[f] = E->mom_sq[f] = nullptr;
+}
+// a zeroed array of the state's shape [nlay][n1], element 1 aligned as dev_alloc's
+static int alloc_moment_array(beom_engine *E, double **p, char *errm, int errm_len) {
+    void *q = nullptr;
+    const size_t n = (size_t)E->d.nlay * (size_t)E->d.n1 + 16;
+    HIP_TRY(hipMalloc(&q, n * sizeof(double)));
+    E->mom_allocs.push_back(q);
+    HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(double), E->stream));
+    *p = (double *)q + 15;
+    return 0;
+}
+
+int beom_set_moments(beom_handle E, int level, int stride, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (level < 0 || level > 3 || stride < 1) { set_err(errm, errm_len, "beom_set_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    free_moments(E);
+    if (level == 0) return 0;
+    int rc = 0;
+    const int nf = level >= 2 ? 5 : 3;
+    for (int f = 0; f < nf && !rc; ++f) {
+        rc = alloc_moment_array(E, &E->mom_ref[f], errm, errm_len);
+        if (!rc) rc = alloc_moment_array(E, &E->mom_sum[f], errm, errm_len);
+    }
+    for (int m = 0; m < 5 && !rc && level >= 3; ++m) rc = alloc_moment_array(E, &E->mom_sq[m], errm, errm_len);
+    if (rc) { free_moments(E); return rc; }
+    E->mom_level = level; E->mom_stride = stride;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int beom_reset_moments(beom_handle E) {
+    if (!E) return -1;
+    if (E->mom_level < 1) return -3;
+    E->mom_count = 0; E->mom_first = E->mom_last = 0;
+    return 0;
+}
+
+int beom_sample_moments(beom_handle E) {
+    if (!E) return -1;
+    if (E->mom_level < 1) return -3;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    launch_moments(E, E->last_tstp);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int beom_download_moments(beom_handle E, double *ref, double *sum, double *sq, long long *count, int *tstp_first, int *tstp_last,
+                          char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->mom_level < 1) { set_err(errm, errm_len, "beom_download_moments: the handle keeps no moments (beom_set_moments)"); return -3; }
+    if (sq && E->mom_level < 3) { set_err(errm, errm_len, "beom_download_moments: the second moments are kept at level 3, this handle has level %d", E->mom_level); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t nl = (size_t)E->d.nlay, slab = ((size_t)E->d.ndeg + 1) * nl;
+    const int nf = E->mom_level >= 2 ? 5 : 3;
+    if (count) *count = E->mom_count;
+    if (tstp_first) *tstp_first = E->mom_first;
+    if (tstp_last) *tstp_last = E->mom_last;
+    if (E->mom_count == 0) {           // nothing sampled yet: the arrays hold whatever an earlier average left
+        if (ref) std::fill(ref, ref + nf * slab, 0.0);
+        if (sum) std::fill(sum, sum + nf * slab, 0.0);
+        if (sq) std::fill(sq, sq + 5 * slab, 0.0);
+        return 0;
+    }
+    int rc;
+    for (int f = 0; f < nf; ++f) {
+        if (ref && (rc = copy_out(E, ref + f * slab, E->mom_ref[f], nl, errm, errm_len))) return rc;
+        if (sum && (rc = copy_out(E, sum + f * slab, E->mom_sum[f], nl, errm, errm_len))) return rc;
+    }
+    for (int m = 0; m < 5 && sq; ++m)
+        if ((rc = copy_out(E, sq + m * slab, E->mom_sq[m], nl, errm, errm_len))) return rc;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)
 // of nudged open-boundary segments, Fortran storage.  Activates no_gradient_obc after the
 // momentum sweeps of every step when flag_nudging and mcbc < 0.5 (:2201-2204, 2285-2288).
@@ -1613,6 +1728,9 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "floats")) return (int)std::min<long long>(E->nflt, 2000000000ll);
     if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
     if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far
+    if (!strcmp(what, "moments")) return E->mom_level;
+    if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom_count, 2000000000ll);
+    if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom_launches, 2000000000ll);     // all calls so far
     if (!strcmp(what, "lid_sweeps")) return (int)std::min<long long>(E->lid_sweeps, 2000000000ll);        // Gauss-Seidel sweeps kept, all steps so far
     if (!strcmp(what, "lid_solves")) return (int)std::min<long long>(E->lid_solves, 2000000000ll);
     if (!strcmp(what, "lid_launches")) return (int)std::min<long long>(E->lid_launches, 2000000000ll);
@@ -1634,6 +1752,7 @@ int beom_set_option(beom_handle E, const char *name, int value) {
     else if (!strcmp(name, "lean_visc")) E->lean_visc = value != 0;
     else if (!strcmp(name, "mont_history")) E->mont_history = value != 0;
     else if (!strcmp(name, "plain_sweeps")) E->plain_sweeps = value != 0;
+    else if (!strcmp(name, "moments_by_caller")) E->mom_by_caller = value != 0;
     else return -3;
     return 0;
 }

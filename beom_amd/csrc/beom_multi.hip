@@ -347,6 +347,9 @@ struct beom_multi {
     size_t xbytes = 0;
     long long n_split = 0, n_plain = 0;   // band-steps taken in two phases / in one piece
     int ntrc = 0;                  // passive tracers carried by every band (beom_multi_set_tracers): q joins the exchange
+    // moments kept by every band (beom_multi_set_moments): the bands sample on request ("moments_by_caller"), the step whose
+    // sample is still owed (0 = none) is taken where the main streams next join the exchange
+    int mom_level = 0, mom_stride = 1, mom_due = 0;
     // companion frame of a y-periodic ring (lives with band 0): rows 1..kMiniLo, Mr-3..Mr, Mr+1
     beom_handle mini = nullptr;
     int mini_k = -1;               // local index of band 0, or -1 if band 0 is not here
@@ -870,6 +873,7 @@ int beom_multi_set_option(beom_multi_handle M, const char *name, int value) {
     if (!M || !name) return -1;
     if (!strcmp(name, "overlap")) { M->overlap = value != 0; return 0; }
     if (!strcmp(name, "edge_stream")) return 0;       // (an option of the earlier split form; accepted, without effect)
+    if (!strcmp(name, "moments_by_caller")) return -3;   // (the bands' samples are placed by beom_multi_step)
     int rc = 0;
     for (int k = 0; k < M->n && !rc; ++k) rc = beom_set_option(M->eng[k], name, value);
     if (!rc && M->mini) rc = beom_set_option(M->mini, name, value);
@@ -1027,6 +1031,68 @@ int beom_multi_download_tracers(beom_multi_handle M, double *q, double *rq, char
         for (int f = 0; f < 2; ++f) {
             if (M->land) paste_v(dst[f], a[f], outer, inner[f], n1g, n1l, s.lst, M->gst, s.gs + 1, s.nown(), rows, k == 0);
             else paste(dst[f], a[f], outer, inner[f], n1g, n1l, L, s.gs + 1, s.nown(), rows, k == 0);
+        }
+    }
+    return 0;
+}
+
+// ---- moments (beom_set_moments) on the bands: every band accumulates over all its rows, ghosts included, and the global
+//      arrays take the owned rows; a ring's row mm+1 comes from the companion frame, which samples behind its own steps ----
+int beom_multi_set_moments(beom_multi_handle M, int level, int stride, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_moments: an earlier step failed half way; destroy the handle"); return -30; }
+    if (level < 0 || level > 3 || stride < 1) { m_err(errm, errm_len, "beom_multi_set_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_set_moments: a handle that holds one band's window does not keep moments yet (its global arrays are nowhere assembled); use a handle created from the global arrays"); return -6; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    const bool single = M->nb == 1 && !M->ring;       // steps through beom_step: the handle samples by itself
+    for (int k = 0; k < M->n; ++k) {
+        M_RC(beom_set_moments(M->eng[k], level, stride, errm, errm_len));
+        if (beom_set_option(M->eng[k], "moments_by_caller", single ? 0 : 1)) { m_err(errm, errm_len, "beom_multi_set_moments: option refused"); return -3; }
+    }
+    if (M->mini) M_RC(beom_set_moments(M->mini, level, stride, errm, errm_len));
+    M->mom_level = level; M->mom_stride = stride; M->mom_due = 0;
+    return 0;
+}
+
+int beom_multi_reset_moments(beom_multi_handle M, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->mom_level < 1) { m_err(errm, errm_len, "beom_multi_reset_moments: the handle keeps no moments (beom_multi_set_moments)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    for (int k = 0; k < M->n; ++k) M_RC(beom_reset_moments(M->eng[k]));
+    if (M->mini) M_RC(beom_reset_moments(M->mini));
+    M->mom_due = 0;
+    return 0;
+}
+
+int beom_multi_download_moments(beom_multi_handle M, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
+                                int *tstp_last, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_moments: this handle holds a window and keeps no moments"); return -6; }
+    if (M->mom_level < 1) { m_err(errm, errm_len, "beom_multi_download_moments: the handle keeps no moments (beom_multi_set_moments)"); return -3; }
+    if (sq && M->mom_level < 3) { m_err(errm, errm_len, "beom_multi_download_moments: the second moments are kept at level 3, this handle has level %d", M->mom_level); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (M->nb == 1 && !M->ring) return beom_download_moments(M->eng[0], ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
+    const int nl = M->P.nlay, L = M->P.lm + 1;
+    const size_t n1g = M->n1g;
+    const int nf = M->mom_level >= 2 ? 5 : 3;
+    double *dst[3] = {ref, sum, sq};
+    const size_t outer[3] = {(size_t)nf * nl, (size_t)nf * nl, (size_t)5 * nl};
+    for (int k = -1; k < M->n; ++k) {
+        if (k < 0 && !M->mini) continue;
+        const size_t n1l = k < 0 ? (size_t)M->mini_rows.size() * L + 1 : (size_t)M->band[k].n_loc() + 1;
+        std::vector<double> a[3];
+        for (int f = 0; f < 3; ++f) if (dst[f]) a[f].assign(outer[f] * n1l, 0.0);
+        long long cnt = 0;
+        int t0 = 0, t1 = 0;
+        M_RC(beom_download_moments(k < 0 ? M->mini : M->eng[k], ptr(a[0]), ptr(a[1]), ptr(a[2]), &cnt, &t0, &t1, errm, errm_len));
+        if (k == 0) { if (count) *count = cnt; if (tstp_first) *tstp_first = t0; if (tstp_last) *tstp_last = t1; }
+        int j0, n;
+        std::vector<int> rows;
+        if (k < 0) { j0 = (int)M->mini_rows.size(); n = 1; rows.push_back(M->P.mm + 1); }      // the orphan row
+        else { const Band &s = M->band[k]; j0 = s.gs + 1; n = s.nown(); for (int j = 0; j < n; ++j) rows.push_back(s.own0 + j); }
+        for (int f = 0; f < 3; ++f) {
+            if (M->land) paste_v(dst[f], a[f], outer[f], 1, n1g, n1l, M->band[k < 0 ? 0 : k].lst, M->gst, j0, n, rows, k == 0);
+            else paste(dst[f], a[f], outer[f], 1, n1g, n1l, L, j0, n, rows, k == 0);
         }
     }
     return 0;
@@ -1340,6 +1406,15 @@ int beom_multi_profile_stop(beom_multi_handle M, double *ms, int *launches, char
 // looks at the second one exactly once per step — "have my ghost rows landed?" before the next step starts — and by then
 // the exchange has had the whole interior sweep to finish.  Steps that cannot be cut that way (open-boundary passes, the
 // separate u and v sweeps, option "overlap" = 0) run whole, the exchange after them.
+// the moments' sample a step left owing, on every band's main stream (which has joined the exchange of that step)
+static int multi_sample_due(beom_multi *M, char *errm, int errm_len) {
+    if (!M->mom_due) return 0;
+    for (int k = 0; k < M->n; ++k)
+        if (beom_sample_moments(M->eng[k])) { m_err(errm, errm_len, "beom_sample_moments failed on band %d (step %d)", M->band[k].index, M->mom_due); return -3; }
+    M->mom_due = 0;
+    return 0;
+}
+
 static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double dt_r, double rsta, int n_3d,
                           char *errm, int errm_len) {
     const int n = M->n;
@@ -1351,6 +1426,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
         M_HIP(hipSetDevice(M->dev[k]));
         M_HIP(hipStreamWaitEvent(M->main_s[k], M->landed[k], 0));
     }
+    M_RC(multi_sample_due(M, errm, errm_len));          // the sample of the step before: its strips and ghost rows are in place
     // companion frame of a ring: rows 1..6 of band 0 and its south ghosts (= rows mm-3..mm) as they stand before this
     // step, then the companion's own step on its own stream
     if (M->mini) {
@@ -1478,6 +1554,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
             M->pending[k] = 1;
         }
     }
+    if (M->mom_level > 0 && t % M->mom_stride == 0) M->mom_due = t;
     return 0;
 }
 
@@ -1496,6 +1573,14 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
             for (int k = 0; k < M->n; ++k) { (void)beom_set_stream(M->eng[k], (void *)M->main_s[k], 0); M->pending[k] = 0; }
             return rc;
         }
+    }
+    if (M->mom_due) {            // the last step's sample: behind the same wait the next step would begin with
+        for (int k = 0; k < M->n; ++k) {
+            if (!M->pending[k]) continue;
+            M_HIP(hipSetDevice(M->dev[k]));
+            M_HIP(hipStreamWaitEvent(M->main_s[k], M->landed[k], 0));
+        }
+        M_RC(multi_sample_due(M, errm, errm_len));
     }
     return 0;
 }

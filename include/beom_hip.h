@@ -335,6 +335,40 @@ int beom_download_floats(beom_handle h, double *x, double *y, int32_t *layer, in
 int beom_download_float_track(beom_handle h, double *rec, int *count, int *tstp_of_record, char *errm, int errm_len);
 int beom_update_floats(beom_handle h, int stage);
 
+/* ---- Moments: time means and second moments of the layer fields, accumulated on the device (no reference routine;
+ * DESIGN.md f-N8).  The five fields are f = 0..4: hlay, u, v, h_u, h_v.  A SAMPLE is taken behind step tstp of beom_step when
+ * tstp % stride == 0: after the open-boundary pass, the lid's pressure correction and its transport rebuild, so it reads the
+ * fields exactly as beom_download_state would return them after that step.  K steps of one call take their samples without
+ * returning to the host; the bits do not depend on how the steps are divided into calls.
+ * The sums are shifted by a reference that the first sample sets.  All arithmetic FP64, in this order, no contraction, at
+ * every element of the packed (0:ndeg, nlay) storage, the sentinel included (it holds constants: its sums are +0.0):
+ *   first sample after beom_set_moments / beom_reset_moments:   ref_f = x_f;  S_f = +0.0;  Q_m = +0.0;  count = 1
+ *   every later sample:   d_f = x_f - ref_f;  S_f = S_f + d_f;  Q_m = Q_m + d_a*d_b  (the product rounded, then added);  count += 1
+ *   the five second moments m = 0..4 are (a, b) = (h,h) (u,u) (v,v) (u,h_u) (v,h_v)
+ * Derived by the caller: mean = ref + S/count; (co)variance = Q/count - (S_a/count)*(S_b/count).  Why shifted: a plain
+ * sum of x and x*x loses the signal of a deep layer.  On h = 4000 + 0.01*sin(0.0137*t + phi) + 0.003*noise, 16 cells,
+ * 100 000 samples, the shifted variance is within 5.8e-14 relative of the long-double two-pass value; the plain form is
+ * off by 7.2e-3 (tests/test_moments_cpu.py repeats both).
+ * `level` chooses what is kept; nothing else is read or written:
+ *   1: ref, S of hlay, u, v        2: level 1 plus ref, S of h_u, h_v        3: level 2 plus the five Q
+ * (6 / 10 / 15 more arrays of the state's size; 12 / 20 / 30 words of traffic per cell-layer and sample).
+ * beom_set_moments: level = 0 frees, stride >= 1; allocates, count = 0; between steps only; every handle kind (bands of
+ * rows, variant = 1 and the rigid lid included); -3 for a level outside 0..3 or stride < 1.  beom_reset_moments sets
+ * count = 0 and moves no memory: the next sample is a first sample.  beom_upload_state does NOT reset: a restart continues
+ * an average.  beom_sample_moments is the per-sweep entry: one sample of the state as it stands, whatever the stride,
+ * recorded under the step number of the handle's last step (0 before any).  beom_download_moments: any array pointer may be
+ * NULL; the layout is that of the state arrays with the field index slowest, sum[ipnt + (ndeg+1)*((ilay-1) + nlay*f)] (ref
+ * alike; sq with m for f); levels 1 and 2 fill only the fields they keep; -3 if sq is asked for below level 3 or the handle
+ * has no moments; with count = 0 it returns zeros (tstp_first = tstp_last = 0) and no error.  tstp_first / tstp_last: the
+ * steps of the first and the latest sample.  beom_info: "moments" (the level), "moment_samples" (the count, capped at
+ * 2e9), "moment_launches" (so far).  beom_set_option(h, "moments_by_caller", 1): beom_step takes no sample by itself and the
+ * caller places every sample with beom_sample_moments (what the bands of beom_multi_* do). */
+int beom_set_moments(beom_handle h, int level, int stride, char *errm, int errm_len);
+int beom_reset_moments(beom_handle h);
+int beom_sample_moments(beom_handle h);
+int beom_download_moments(beom_handle h, double *ref, double *sum, double *sq, long long *count, int *tstp_first, int *tstp_last,
+                          char *errm, int errm_len);
+
 /* ---- Conservation integrals of the state as it stands between two steps (no reference routine: the reference's test
  * case 3 forms them from the output files, testcases/conservation.m:116-211).  All FP64, raw sums over the frame:
  *   out[(l-1)*4 + 0]  vol   sum of mk_n*h                                    layer volume / dl^2
@@ -499,6 +533,17 @@ int beom_multi_download_local(beom_multi_handle h, beom_state *window, beom_stat
 int beom_multi_set_tracers(beom_multi_handle m, int ntrc, char *errm, int errm_len);
 int beom_multi_upload_tracers(beom_multi_handle m, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len);
 int beom_multi_download_tracers(beom_multi_handle m, double *q, double *rq, char *errm, int errm_len);
+
+/* Moments on a frame cut into bands (see beom_set_moments): GLOBAL arrays assembled from every band's OWNED rows, handles
+ * created from the global arrays (beom_multi_create[_ex]), chains and rings; the bits are a single handle's.  A band's sample
+ * of step t is placed where its main stream has joined the exchange of that step (in front of step t + 1, and once more
+ * behind the last step of a beom_multi_step call), so cut steps stay cut and no stream hop is added.  A ring's row mm+1 comes
+ * from the companion frame, which accumulates its own moments.  Refused with -6: handles that hold one band's window
+ * (beom_multi_create_local*). */
+int beom_multi_set_moments(beom_multi_handle m, int level, int stride, char *errm, int errm_len);
+int beom_multi_reset_moments(beom_multi_handle m, char *errm, int errm_len);
+int beom_multi_download_moments(beom_multi_handle m, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
+                                int *tstp_last, char *errm, int errm_len);
 
 /* Conservation integrals (see beom_integrals).  Global-array handles: every band forms the row sums of its OWNED rows; a
  * ring's row mm+1 duplicates row 1 and is all +0, so the companion frame is not asked; combined in global row order. */

@@ -37,13 +37,14 @@
 #include <vector>
 
 #include "../../include/beom_hip.h"
+#include "beom_bands_host.h"
 #include "beom_dense_host.h"
+
+using namespace beom_bands;
 
 namespace {
 
-constexpr int kGhost = 4;          // rows per neighbour; see DESIGN.md §5 for why 4 is enough
 constexpr int kFields = 5;         // hlay, u, v, h_u, h_v
-constexpr int kMiniLo = 6;         // rows 1..6 of a y-periodic frame that the companion frame carries
 constexpr int kFakePad = 8;        // a ring band is presented as rows 9.. of a frame 16 rows taller
 
 void m_err(char *errm, int len, const char *fmt, ...) {
@@ -215,100 +216,29 @@ static int shm_open_all(ShmXchg **out, const char *name, int nb, int band, size_
     return 0;
 }
 
-// ---- geometry ---------------------------------------------------------------------------------------
-struct Band {
-    int index = 0;                 // position in the chain / ring of nb bands
-    int own0 = 0, own1 = 0;        // owned global rows (1-based, inclusive)
-    int gs = 0, gn = 0;            // ghost rows on the south / north side
-    int L = 0;                     // columns = lm + 1
-    int Mr = 0;                    // rows of the ring (frames periodic in y), else 0
-    std::vector<long long> lst;    // frames with land: first local packed cell of local row j = 1..rows()+1 (rows differ in length)
-    int nown() const { return own1 - own0 + 1; }
-    int rows() const { return gs + nown() + gn; }
-    long long n_loc() const { return lst.empty() ? (long long)rows() * L : lst[(size_t)rows() + 1] - 1; }
-    int grow(int j) const {        // global row of local row j (ghosts of a ring wrap)
-        int g = own0 - gs + (j - 1);
-        if (Mr) { while (g < 1) g += Mr; while (g > Mr) g -= Mr; }
-        return g;
-    }
-    std::vector<int> row_list() const { std::vector<int> r; for (int j = 1; j <= rows(); ++j) r.push_back(grow(j)); return r; }
-};
-
-// shapes of the caller's arrays around the packed index: x[outer][0:n][inner]
-struct Shape { int outer_nl, outer_c, inner; size_t outer(int nl) const { return (size_t)outer_nl * nl + outer_c; } };
-//                         fcor     h_th     h_to     nudg     fnud     hdot     tide     taus
-const Shape kStatic[8] = {{0,1,1}, {0,1,1}, {0,1,1}, {0,3,1}, {3,0,1}, {1,0,1}, {0,3,2}, {0,2,1}};
-//                        hlay     u        v        h_u      h_v      rs_h     dmdx     dmdy     v_cc     v_ll     tt3d     tb3d     tu3d
-const Shape kState[13] = {{1,0,1}, {1,0,1}, {1,0,1}, {1,0,1}, {1,0,1}, {1,0,2}, {1,0,3}, {1,0,3}, {1,0,1}, {1,0,1}, {2,0,1}, {2,0,1}, {2,0,1}};
-
-// [outer][0:n1src][inner] -> [outer][0:rows*L][inner]: sentinel first, then the listed rows of the source
-template <class T>
-std::vector<T> cut(const T *x, size_t outer, size_t inner, size_t n1src, const std::vector<int> &rows, int L) {
-    std::vector<T> z;
-    if (!x) return z;
-    const size_t n1l = rows.size() * (size_t)L + 1;
-    z.resize(outer * n1l * inner);
-    for (size_t o = 0; o < outer; ++o) {
-        std::memcpy(&z[o * n1l * inner], &x[o * n1src * inner], inner * sizeof(T));
-        for (size_t r = 0; r < rows.size(); ++r)
-            std::memcpy(&z[(o * n1l + 1 + r * L) * inner], &x[(o * n1src + 1 + (size_t)(rows[r] - 1) * L) * inner],
-                        (size_t)L * inner * sizeof(T));
-    }
-    return z;
-}
-// local rows [j0, j0+n) of a local [outer][0:n1l][inner] array -> rows g(j) of a [outer][0:n1dst][inner] array
-template <class T>
-void paste(T *dst, const std::vector<T> &loc, size_t outer, size_t inner, size_t n1dst, size_t n1l, int L,
-           int j0, int n, const std::vector<int> &dst_rows, bool sentinel) {
-    if (!dst || loc.empty()) return;
-    for (size_t o = 0; o < outer; ++o) {
-        if (sentinel) std::memcpy(&dst[o * n1dst * inner], &loc[o * n1l * inner], inner * sizeof(T));
-        for (int r = 0; r < n; ++r)
-            std::memcpy(&dst[(o * n1dst + 1 + (size_t)(dst_rows[r] - 1) * L) * inner],
-                        &loc[(o * n1l + 1 + (size_t)(j0 - 1 + r) * L) * inner], (size_t)L * inner * sizeof(T));
-    }
-}
+// ---- the caller's arrays cut into windows: geometry and the copy are beom_bands_host.h's ---------------------------------
 template <class T> const T *ptr(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
 template <class T> T *ptr(std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
-
-// ---- the same for frames WITH land: a row is the packed range [gst[j], gst[j+1]) of the caller's arrays (packing is
-//      j-major), rows differ in length; lst = the starts of a band's rows in its own packed order ----
-template <class T>
-std::vector<T> cut_v(const T *x, size_t outer, size_t inner, size_t n1src, const std::vector<int> &rows, const std::vector<long long> &gst) {
-    std::vector<T> z;
-    if (!x) return z;
-    size_t n1l = 1;
-    for (int g : rows) n1l += (size_t)(gst[(size_t)g + 1] - gst[(size_t)g]);
-    z.resize(outer * n1l * inner);
-    for (size_t o = 0; o < outer; ++o) {
-        std::memcpy(&z[o * n1l * inner], &x[o * n1src * inner], inner * sizeof(T));
-        size_t at = 1;
-        for (int g : rows) {
-            const size_t len = (size_t)(gst[(size_t)g + 1] - gst[(size_t)g]);
-            if (len) std::memcpy(&z[(o * n1l + at) * inner], &x[(o * n1src + (size_t)gst[(size_t)g]) * inner], len * inner * sizeof(T));
-            at += len;
-        }
-    }
-    return z;
-}
-template <class T>
-void paste_v(T *dst, const std::vector<T> &loc, size_t outer, size_t inner, size_t n1dst, size_t n1l, const std::vector<long long> &lst,
-             const std::vector<long long> &gst, int j0, int n, const std::vector<int> &dst_rows, bool sentinel) {
-    if (!dst || loc.empty()) return;
-    for (size_t o = 0; o < outer; ++o) {
-        if (sentinel) std::memcpy(&dst[o * n1dst * inner], &loc[o * n1l * inner], inner * sizeof(T));
-        for (int r = 0; r < n; ++r) {
-            const size_t g = (size_t)dst_rows[(size_t)r], len = (size_t)(gst[g + 1] - gst[g]);
-            if (len) std::memcpy(&dst[(o * n1dst + (size_t)gst[g]) * inner], &loc[(o * n1l + (size_t)lst[(size_t)(j0 + r)]) * inner], len * inner * sizeof(T));
-        }
-    }
-}
 
 struct StaticsV {                  // one band's (or the companion frame's) static arrays in window layout
     std::vector<double> a[8];
     const double *bodf = nullptr;
 };
 struct StateV { std::vector<double> a[13]; };
+int upload_state_v(beom_handle h, const StateV &a, char *errm, int errm_len) {
+    return beom_upload_state(h, ptr(a.a[0]), ptr(a.a[1]), ptr(a.a[2]), ptr(a.a[3]), ptr(a.a[4]), ptr(a.a[5]), ptr(a.a[6]), ptr(a.a[7]),
+                             ptr(a.a[8]), ptr(a.a[9]), ptr(a.a[10]), ptr(a.a[11]), ptr(a.a[12]), errm, errm_len);
+}
+int download_state_v(beom_handle h, StateV &a, char *errm, int errm_len) {
+    return beom_download_state(h, ptr(a.a[0]), ptr(a.a[1]), ptr(a.a[2]), ptr(a.a[3]), ptr(a.a[4]), ptr(a.a[5]), ptr(a.a[6]), ptr(a.a[7]),
+                               ptr(a.a[8]), ptr(a.a[9]), ptr(a.a[10]), ptr(a.a[11]), ptr(a.a[12]), errm, errm_len);
+}
+// an engine from tables and masks (mk_u, mk_v, mk_n, mkpe, mkpi) and a window's statics
+int create_engine(const beom_params &lp, int dev, const int32_t *neig, const int32_t *subc, const double *const (&mk)[5], const StaticsV &st,
+                  beom_handle *out, char *errm, int errm_len) {
+    return beom_create(&lp, dev, neig, subc, mk[0], mk[1], mk[2], mk[3], mk[4], ptr(st.a[0]), ptr(st.a[1]), ptr(st.a[2]), ptr(st.a[3]),
+                       ptr(st.a[4]), ptr(st.a[5]), ptr(st.a[6]), st.bodf, ptr(st.a[7]), out, errm, errm_len);
+}
 
 const double *const *statics_ptrs(const beom_statics *s, const double *(&p)[8]) {
     p[0] = s->fcor; p[1] = s->h_th; p[2] = s->h_to; p[3] = s->nudg; p[4] = s->fnud; p[5] = s->hdot; p[6] = s->tide; p[7] = s->taus;
@@ -333,7 +263,7 @@ struct beom_multi {
     bool overlap = true;           // steps cut boundary first, the exchange inside the interior sweep (beom_multi_set_option "overlap")
     size_t n1g = 0;
     bool land = false;             // a frame with land: bands are packed row ranges of unequal length, on the rectangle ("embedded") form
-    std::vector<long long> gst;    // land: first packed cell of every global row j = 1..mm+2
+    std::vector<long long> gst;    // first packed cell of every global row j = 1..mm+2 (handles from global arrays; land or not)
     std::vector<int> dev;
     std::vector<Band> band;
     std::vector<beom_handle> eng;
@@ -369,6 +299,30 @@ struct beom_multi {
 
 namespace {
 
+// A part of the frame: band k of this process, or (k = -1) the companion frame of a ring.  "in" cuts the caller's arrays to
+// the part's window (all its rows), "out" pastes what the part owns back: a band's owned rows, the companion's orphan row.
+// A handle that holds one band's window has that window in the caller's place (and the orphan row in a one-row array).
+struct Part {
+    int k;
+    beom_handle eng;               // (null while the handle is being created)
+    Spans in, out;
+    size_t n1() const { return in.n1dst; }      // slots of the part's own arrays
+};
+std::vector<Part> parts(const beom_multi *M) {
+    std::vector<Part> v;
+    const int L = M->P.lm + 1;
+    for (int k = 0; k < M->n; ++k) {
+        const Band &b = M->band[k];
+        if (M->local_mode) v.push_back({k, M->eng[k], spans_whole(b), spans_whole(b)});
+        else v.push_back({k, M->eng[k], spans_in(b.row_list(), M->gst, M->n1g), spans_out(b, M->gst, M->n1g)});
+    }
+    if (M->mini_k >= 0) {
+        if (M->local_mode) v.push_back({-1, M->mini, spans_window_to_mini(M->band[M->mini_k]), spans_mini_to_orphan(L)});
+        else v.push_back({-1, M->mini, spans_in(M->mini_rows, M->gst, M->n1g), spans_orphan_out(M->P.mm, L, M->gst, M->n1g)});
+    }
+    return v;
+}
+
 void destroy_all(beom_multi *M) {
     if (!M) return;
     for (int k = 0; k < M->n; ++k) {
@@ -401,17 +355,6 @@ void destroy_all(beom_multi *M) {
     delete M;
 }
 
-// rows of the chain / ring dealt to nb bands: equal counts, remainders to the first bands
-void deal_rows(int nrows_total, int nb, int idx, int *own0, int *own1) {
-    const int base = nrows_total / nb, rem = nrows_total % nb;
-    int j = 1;
-    for (int k = 0; k < nb; ++k) {
-        const int cnt = base + (k < rem ? 1 : 0);
-        if (k == idx) { *own0 = j; *own1 = j + cnt - 1; }
-        j += cnt;
-    }
-}
-
 int check_frame(const beom_params *prm, int nb, int yper, bool global_arrays, bool land, char *errm, int errm_len) {
     const int L = prm->lm + 1, Mg = prm->mm + 1;
     if (prm->abi_version != BEOM_ABI_VERSION) { m_err(errm, errm_len, "beom_multi: ABI version mismatch"); return -2; }
@@ -433,16 +376,6 @@ int check_frame(const beom_params *prm, int nb, int yper, bool global_arrays, bo
     return 0;
 }
 
-// geometry of band idx; a single band of a non-periodic frame is the whole frame (no slab at all)
-Band make_band(const beom_params *prm, int nb, int idx, bool ring) {
-    Band s;
-    s.index = idx; s.L = prm->lm + 1; s.Mr = ring ? prm->mm : 0;
-    deal_rows(ring ? prm->mm : prm->mm + 1, nb, idx, &s.own0, &s.own1);
-    s.gs = (ring || idx > 0) ? kGhost : 0;
-    s.gn = (ring || idx < nb - 1) ? kGhost : 0;
-    return s;
-}
-
 int finish_band(beom_multi *M, int k, char *errm, int errm_len);
 
 // one band's engine from its window statics (tables come from the closed form)
@@ -456,10 +389,8 @@ int create_band(beom_multi *M, int k, const StaticsV &st, char *errm, int errm_l
     else if (M->nb > 1) { joff = s.own0 - s.gs - 1; Mg = M->P.mm + 1; slab = 1; }
     lp.slab_row0 = slab ? joff : 0; lp.slab_mm = slab ? Mg - 1 : 0;
     const beom_dense::Tables t = beom_dense::generate(s.L, s.rows(), joff, Mg, slab, M->xper, 0);
-    int rc = beom_create(&lp, M->dev[k], t.neig.data(), t.subc.data(), t.mk_u.data(), t.mk_v.data(), t.mk_n.data(),
-                         t.mkpe.data(), t.mkpi.data(), ptr(st.a[0]), ptr(st.a[1]), ptr(st.a[2]), ptr(st.a[3]), ptr(st.a[4]),
-                         ptr(st.a[5]), ptr(st.a[6]), st.bodf, ptr(st.a[7]), &M->eng[k], errm, errm_len);
-    if (rc) return rc;
+    M_RC(create_engine(lp, M->dev[k], t.neig.data(), t.subc.data(), {t.mk_u.data(), t.mk_v.data(), t.mk_n.data(), t.mkpe.data(), t.mkpi.data()},
+                       st, &M->eng[k], errm, errm_len));
     if (!beom_is_dense(M->eng[k])) { m_err(errm, errm_len, "beom_multi: band %d did not qualify for the dense path", s.index); return -4; }
     return finish_band(M, k, errm, errm_len);
 }
@@ -467,8 +398,8 @@ int create_band(beom_multi *M, int k, const StaticsV &st, char *errm, int errm_l
 // Band k of a frame WITH land: the rows' packed cells with the caller's own tables, re-indexed to the window (links that
 // leave the window become the sentinel: they start in the outermost ghost row, whose values nobody uses).  The engine
 // lays such a band out on its rectangle ("embedded", beom_engine.hip) — that is what the ghost-row copies rely on.
-int create_band_land(beom_multi *M, int k, const int32_t *neig, const int32_t *subc, const double *const *masks, const StaticsV &st,
-                     char *errm, int errm_len) {
+int create_band_land(beom_multi *M, int k, const Spans &in, const int32_t *neig, const int32_t *subc, const double *const (&masks)[5],
+                     const StaticsV &st, char *errm, int errm_len) {
     const Band &s = M->band[k];
     const size_t n1g = M->n1g, nloc = (size_t)s.n_loc(), n1l = nloc + 1;
     const int row0 = s.own0 - s.gs;                               // global row of local row 1
@@ -488,14 +419,12 @@ int create_band_land(beom_multi *M, int k, const int32_t *neig, const int32_t *s
             lsub[q + n1l] = subc[(size_t)p + n1g] - row0 + 1;
         }
     std::vector<double> lm[5];
-    for (int f = 0; f < 5; ++f) lm[f] = cut_v(masks[f], 1, 1, n1g, rows, M->gst);
+    for (int f = 0; f < 5; ++f) lm[f] = cut_rows(masks[f], 1, 1, in);
     beom_params lp = M->P;
     lp.mm = s.rows() - 1; lp.ndeg = (int32_t)nloc; lp.dense_hint = 1;
     lp.slab_row0 = row0 - 1; lp.slab_mm = M->P.mm;              // a window of the global frame: the engine splits its steps around the exchange
-    int rc = beom_create(&lp, M->dev[k], ln.data(), lsub.data(), lm[0].data(), lm[1].data(), lm[2].data(), lm[3].data(), lm[4].data(),
-                         ptr(st.a[0]), ptr(st.a[1]), ptr(st.a[2]), ptr(st.a[3]), ptr(st.a[4]), ptr(st.a[5]), ptr(st.a[6]), st.bodf,
-                         ptr(st.a[7]), &M->eng[k], errm, errm_len);
-    if (rc) return rc;
+    M_RC(create_engine(lp, M->dev[k], ln.data(), lsub.data(), {lm[0].data(), lm[1].data(), lm[2].data(), lm[3].data(), lm[4].data()},
+                       st, &M->eng[k], errm, errm_len));
     if (beom_is_dense(M->eng[k]) < 1) {           // (2: the rectangle form with land; 1: no land at all in this window)
         m_err(errm, errm_len, "beom_multi: band %d (rows %d..%d) does not fit the rectangle form (fewer than 30 %% of its cells wet, or a coast on a periodic seam)",
               s.index, s.own0, s.own1);
@@ -525,13 +454,12 @@ int finish_band(beom_multi *M, int k, char *errm, int errm_len) {
 
 // the companion frame of a ring: a y-periodic frame of kMiniLo + kGhost + 1 rows on band 0's device
 int create_mini(beom_multi *M, const StaticsV &st, char *errm, int errm_len) {
-    const int k = M->mini_k, L = M->P.lm + 1, Mm = kMiniLo + kGhost + 1;
+    const int k = M->mini_k, L = M->P.lm + 1, Mm = kMiniRows;
     beom_params lp = M->P;
     lp.mm = Mm - 1; lp.ndeg = Mm * L; lp.dense_hint = 1; lp.slab_row0 = 0; lp.slab_mm = 0;
     const beom_dense::Tables t = beom_dense::generate(L, Mm, 0, Mm, 0, M->xper, 1);
-    M_RC(beom_create(&lp, M->dev[k], t.neig.data(), t.subc.data(), t.mk_u.data(), t.mk_v.data(), t.mk_n.data(),
-                     t.mkpe.data(), t.mkpi.data(), ptr(st.a[0]), ptr(st.a[1]), ptr(st.a[2]), ptr(st.a[3]), ptr(st.a[4]),
-                     ptr(st.a[5]), ptr(st.a[6]), st.bodf, ptr(st.a[7]), &M->mini, errm, errm_len));
+    M_RC(create_engine(lp, M->dev[k], t.neig.data(), t.subc.data(), {t.mk_u.data(), t.mk_v.data(), t.mk_n.data(), t.mkpe.data(), t.mkpi.data()},
+                       st, &M->mini, errm, errm_len));
     if (!beom_is_dense(M->mini)) { m_err(errm, errm_len, "beom_multi: the companion frame did not qualify for the dense path"); return -4; }
     M_HIP(hipSetDevice(M->dev[k]));
     M_HIP(hipStreamCreateWithFlags(&M->mini_s, hipStreamNonBlocking));
@@ -596,33 +524,6 @@ void size_vectors(beom_multi *M) {
     M->xbytes = (size_t)kFields * M->P.nlay * kGhost * (M->P.lm + 1) * sizeof(double);
 }
 
-std::vector<int> mini_row_list(int Mr) {
-    std::vector<int> r;
-    for (int j = 1; j <= kMiniLo; ++j) r.push_back(j);
-    for (int j = Mr - kGhost + 1; j <= Mr; ++j) r.push_back(j);
-    r.push_back(Mr + 1);
-    return r;
-}
-
-// window layout of band 0 of a ring + the orphan row -> the companion frame's layout
-// win: [outer][0:(rows*L)][inner] with local rows 1..gs = ring rows Mr-gs+1..Mr, then rows 1..; orph: [outer][0:L][inner]
-std::vector<double> mini_from_window(const double *win, const double *orph, size_t outer, size_t inner, const Band &b0) {
-    std::vector<double> z;
-    if (!win) return z;
-    const int L = b0.L, Mm = kMiniLo + kGhost + 1;
-    const size_t n1w = (size_t)b0.n_loc() + 1, n1m = (size_t)Mm * L + 1, n1o = (size_t)L + 1;
-    z.assign(outer * n1m * inner, 0.0);
-    for (size_t o = 0; o < outer; ++o) {
-        std::memcpy(&z[o * n1m * inner], &win[o * n1w * inner], inner * sizeof(double));
-        // rows 1..kMiniLo = band 0's first owned rows (local rows gs+1..)
-        std::memcpy(&z[(o * n1m + 1) * inner], &win[(o * n1w + 1 + (size_t)b0.gs * L) * inner], (size_t)kMiniLo * L * inner * sizeof(double));
-        // rows Mr-3..Mr = band 0's south ghosts (local rows 1..gs)
-        std::memcpy(&z[(o * n1m + 1 + (size_t)kMiniLo * L) * inner], &win[(o * n1w + 1) * inner], (size_t)kGhost * L * inner * sizeof(double));
-        if (orph) std::memcpy(&z[(o * n1m + 1 + (size_t)(kMiniLo + kGhost) * L) * inner], &orph[(o * n1o + 1) * inner], (size_t)L * inner * sizeof(double));
-    }
-    return z;
-}
-
 }  // namespace
 
 extern "C" {
@@ -682,7 +583,7 @@ int beom_multi_create_ex(const beom_params *prm, int ndev, const int *devices, i
     const size_t n1g = M->n1g;
     int rc = 0;
     if (whole) {                                  // the caller's own tables, any coastline
-        Band s; s.index = 0; s.own0 = 1; s.own1 = Mg; s.L = L;
+        Band s; s.index = 0; s.own0 = 1; s.own1 = Mg; s.L = L;      // (no window: nothing is cut, lst stays empty)
         M->band.push_back(s);
         rc = beom_create(prm, M->dev[0], neig, subc, mk_u, mk_v, mk_n, mkpe, mkpi, fcor, h_th, h_to, nudg, fnud, hdot, tide, bodf, taus,
                          &M->eng[0], errm, errm_len);
@@ -693,6 +594,7 @@ int beom_multi_create_ex(const beom_params *prm, int ndev, const int *devices, i
         return 0;
     }
     const double *src[8] = {fcor, h_th, h_to, nudg, fnud, hdot, tide, taus};
+    const double *const masks[5] = {mk_u, mk_v, mk_n, mkpe, mkpi};
     if (land) {
         // rows as packed ranges (packing is j-major: subc's row number never decreases along the packed index)
         M->land = true;
@@ -719,43 +621,24 @@ int beom_multi_create_ex(const beom_params *prm, int ndev, const int *devices, i
             if (e > last_allowed || e < j) { m_err(errm, errm_len, "beom_multi_create: %d rows are too few for %d bands", Mg, ndev); rc = -3; break; }
             b.own1 = e; j = e + 1;
             b.gs = k > 0 ? kGhost : 0; b.gn = k < ndev - 1 ? kGhost : 0;
-            b.lst.assign((size_t)b.rows() + 2, 0);
-            b.lst[1] = 1;
-            for (int jl = 1; jl <= b.rows(); ++jl) {
-                const size_t g = (size_t)(b.own0 - b.gs + jl - 1);
-                b.lst[(size_t)jl + 1] = b.lst[(size_t)jl] + (M->gst[g + 1] - M->gst[g]);
-            }
+            b.lst = local_starts(b.row_list(), M->gst);
             M->band.push_back(b);
         }
-        const double *masks[5] = {mk_u, mk_v, mk_n, mkpe, mkpi};
-        for (int k = 0; k < ndev && !rc; ++k) {
-            const std::vector<int> rows = M->band[k].row_list();
+    } else {                                      // the same geometry in closed form: every row L cells long
+        M->gst = dense_starts(Mg, L);
+        for (int k = 0; k < ndev; ++k) M->band.push_back(make_band(prm->lm, prm->mm, ndev, k, M->ring));
+        if (M->ring) { M->mini_k = 0; M->mini_rows = mini_row_list(prm->mm); }
+    }
+    if (!rc)
+        for (const Part &p : parts(M)) {
             StaticsV st;
-            for (int f = 0; f < 8; ++f) st.a[f] = cut_v(src[f], kStatic[f].outer(nl), kStatic[f].inner, n1g, rows, M->gst);
+            for (int f = 0; f < 8; ++f) st.a[f] = cut_rows(src[f], kStatic[f].outer(nl), kStatic[f].inner, p.in);
             st.bodf = bodf;
-            rc = create_band_land(M, k, neig, subc, masks, st, errm, errm_len);
+            rc = p.k < 0 ? create_mini(M, st, errm, errm_len)
+                 : land  ? create_band_land(M, p.k, p.in, neig, subc, masks, st, errm, errm_len)
+                         : create_band(M, p.k, st, errm, errm_len);
+            if (rc) break;
         }
-        if (!rc) rc = init_transport(M, nullptr, errm, errm_len);
-        if (rc) { destroy_all(M); return rc; }
-        *out = M;
-        return 0;
-    }
-    for (int k = 0; k < ndev && !rc; ++k) {
-        M->band.push_back(make_band(prm, ndev, k, M->ring));
-        const std::vector<int> rows = M->band[k].row_list();
-        StaticsV st;
-        for (int f = 0; f < 8; ++f) st.a[f] = cut(src[f], kStatic[f].outer(nl), kStatic[f].inner, n1g, rows, L);
-        st.bodf = bodf;
-        rc = create_band(M, k, st, errm, errm_len);
-    }
-    if (!rc && M->ring) {
-        M->mini_k = 0;
-        M->mini_rows = mini_row_list(prm->mm);
-        StaticsV st;
-        for (int f = 0; f < 8; ++f) st.a[f] = cut(src[f], kStatic[f].outer(nl), kStatic[f].inner, n1g, M->mini_rows, L);
-        st.bodf = bodf;
-        rc = create_mini(M, st, errm, errm_len);
-    }
     if (!rc) rc = init_transport(M, nullptr, errm, errm_len);
     if (rc) { destroy_all(M); return rc; }
     *out = M;
@@ -778,7 +661,7 @@ int beom_multi_create(const beom_params *prm, int ndev, const int *devices,
 
 int beom_multi_window(const beom_params *prm, int nb, int band, int yper, int *own0, int *own1, int *ghost_s, int *ghost_n) {
     if (!prm || nb < 1 || band < 0 || band >= nb) return -3;
-    const Band s = make_band(prm, nb, band, yper != 0);
+    const Band s = make_band(prm->lm, prm->mm, nb, band, yper != 0);
     if (own0) *own0 = s.own0;
     if (own1) *own1 = s.own1;
     if (ghost_s) *ghost_s = s.gs;
@@ -813,25 +696,22 @@ int beom_multi_create_local_ex(const beom_params *prm, int nb, int band, int dev
     M->loopback = (transport_and_flags & BEOM_XCHG_LOOPBACK) != 0;
     M->dev.assign(1, device);
     size_vectors(M);
-    M->band.push_back(make_band(prm, nb, band, ring));
-    const Band &s = M->band[0];
+    M->band.push_back(make_band(prm->lm, prm->mm, nb, band, ring));
+    if (ring && band == 0) { M->mini_k = 0; M->mini_rows = mini_row_list(prm->mm); }
     const int nl = prm->nlay;
-    const size_t n1w = (size_t)s.n_loc() + 1;
-    const double *wp[8], *op[8];
+    const double *wp[8], *op[8] = {};
     statics_ptrs(win, wp);
-    StaticsV st;
-    for (int f = 0; f < 8; ++f)
-        if (wp[f]) st.a[f].assign(wp[f], wp[f] + kStatic[f].outer(nl) * n1w * kStatic[f].inner);
-    st.bodf = win->bodf;
-    int rc = create_band(M, 0, st, errm, errm_len);
-    if (!rc && ring && band == 0) {
-        M->mini_k = 0;
-        M->mini_rows = mini_row_list(prm->mm);
-        statics_ptrs(orphan, op);
-        StaticsV sm;
-        for (int f = 0; f < 8; ++f) sm.a[f] = mini_from_window(wp[f], op[f], kStatic[f].outer(nl), kStatic[f].inner, s);
-        sm.bodf = win->bodf;
-        rc = create_mini(M, sm, errm, errm_len);
+    if (M->mini_k >= 0) statics_ptrs(orphan, op);
+    int rc = 0;
+    for (const Part &p : parts(M)) {              // the band from its window as it stands, the companion frame from window and orphan row
+        StaticsV st;
+        for (int f = 0; f < 8; ++f) {
+            st.a[f] = cut_rows(wp[f], kStatic[f].outer(nl), kStatic[f].inner, p.in);
+            if (p.k < 0) copy_rows(ptr(st.a[f]), op[f], kStatic[f].outer(nl), kStatic[f].inner, spans_orphan_to_mini(prm->lm + 1));
+        }
+        st.bodf = win->bodf;
+        rc = p.k < 0 ? create_mini(M, st, errm, errm_len) : create_band(M, p.k, st, errm, errm_len);
+        if (rc) break;
     }
     if (!rc && (nb > 1 || ring)) rc = init_transport(M, rccl_id, errm, errm_len);
     if (rc) { destroy_all(M); return rc; }
@@ -911,20 +791,14 @@ int beom_multi_upload_state(beom_multi_handle M, const double *hlay, const doubl
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
     if (M->local_mode) { m_err(errm, errm_len, "beom_multi_upload_state: this handle holds a window (use beom_multi_upload_local)"); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
-    const int nl = M->P.nlay, L = M->P.lm + 1;
-    const size_t n1g = M->n1g;
+    const int nl = M->P.nlay;
     const double *src[13] = {hlay, u, v, h_u, h_v, rs_h, dmdx, dmdy, v_cc, v_ll, tt3d, tb3d, tu3d};
     if (M->nb == 1 && !M->ring)
         return beom_upload_state(M->eng[0], hlay, u, v, h_u, h_v, rs_h, dmdx, dmdy, v_cc, v_ll, tt3d, tb3d, tu3d, errm, errm_len);
-    for (int k = -1; k < M->n; ++k) {
-        if (k < 0 && !M->mini) continue;
-        const std::vector<int> rows = k < 0 ? M->mini_rows : M->band[k].row_list();
+    for (const Part &p : parts(M)) {
         StateV a;
-        for (int f = 0; f < 13; ++f)
-            a.a[f] = M->land ? cut_v(src[f], kState[f].outer(nl), kState[f].inner, n1g, rows, M->gst)
-                             : cut(src[f], kState[f].outer(nl), kState[f].inner, n1g, rows, L);
-        M_RC(beom_upload_state(k < 0 ? M->mini : M->eng[k], ptr(a.a[0]), ptr(a.a[1]), ptr(a.a[2]), ptr(a.a[3]), ptr(a.a[4]), ptr(a.a[5]),
-                               ptr(a.a[6]), ptr(a.a[7]), ptr(a.a[8]), ptr(a.a[9]), ptr(a.a[10]), ptr(a.a[11]), ptr(a.a[12]), errm, errm_len));
+        for (int f = 0; f < 13; ++f) a.a[f] = cut_rows(src[f], kState[f].outer(nl), kState[f].inner, p.in);
+        M_RC(upload_state_v(p.eng, a, errm, errm_len));
     }
     return 0;
 }
@@ -935,26 +809,15 @@ int beom_multi_download_state(beom_multi_handle M, double *hlay, double *u, doub
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
     if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_state: this handle holds a window (use beom_multi_download_local)"); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
-    const int nl = M->P.nlay, L = M->P.lm + 1;
-    const size_t n1g = M->n1g;
+    const int nl = M->P.nlay;
     double *dst[13] = {hlay, u, v, h_u, h_v, rs_h, dmdx, dmdy, v_cc, v_ll, tt3d, tb3d, tu3d};
     if (M->nb == 1 && !M->ring)
         return beom_download_state(M->eng[0], hlay, u, v, h_u, h_v, rs_h, dmdx, dmdy, v_cc, v_ll, tt3d, tb3d, tu3d, errm, errm_len);
-    for (int k = -1; k < M->n; ++k) {
-        if (k < 0 && !M->mini) continue;
-        const size_t n1l = k < 0 ? (size_t)M->mini_rows.size() * L + 1 : (size_t)M->band[k].n_loc() + 1;
+    for (const Part &p : parts(M)) {
         StateV a;
-        for (int f = 0; f < 13; ++f) if (dst[f]) a.a[f].assign(kState[f].outer(nl) * n1l * kState[f].inner, 0.0);
-        M_RC(beom_download_state(k < 0 ? M->mini : M->eng[k], ptr(a.a[0]), ptr(a.a[1]), ptr(a.a[2]), ptr(a.a[3]), ptr(a.a[4]), ptr(a.a[5]),
-                                 ptr(a.a[6]), ptr(a.a[7]), ptr(a.a[8]), ptr(a.a[9]), ptr(a.a[10]), ptr(a.a[11]), ptr(a.a[12]), errm, errm_len));
-        int j0, n;
-        std::vector<int> rows;
-        if (k < 0) { j0 = (int)M->mini_rows.size(); n = 1; rows.push_back(M->P.mm + 1); }      // the orphan row
-        else { const Band &s = M->band[k]; j0 = s.gs + 1; n = s.nown(); for (int j = 0; j < n; ++j) rows.push_back(s.own0 + j); }
-        for (int f = 0; f < 13; ++f) {
-            if (M->land) paste_v(dst[f], a.a[f], kState[f].outer(nl), kState[f].inner, n1g, n1l, M->band[k].lst, M->gst, j0, n, rows, k == 0);
-            else paste(dst[f], a.a[f], kState[f].outer(nl), kState[f].inner, n1g, n1l, L, j0, n, rows, k == 0);
-        }
+        for (int f = 0; f < 13; ++f) if (dst[f]) a.a[f].assign(kState[f].outer(nl) * p.n1() * kState[f].inner, 0.0);
+        M_RC(download_state_v(p.eng, a, errm, errm_len));
+        for (int f = 0; f < 13; ++f) copy_rows(dst[f], ptr(a.a[f]), kState[f].outer(nl), kState[f].inner, p.out);
     }
     return 0;
 }
@@ -996,16 +859,13 @@ int beom_multi_upload_tracers(beom_multi_handle M, const double *q, const double
     if (M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_upload_tracers: the handle carries no tracer (beom_multi_set_tracers)"); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
     if (M->nb == 1) return beom_upload_tracers(M->eng[0], q, rq, ctrg, errm, errm_len);
-    const size_t outer = (size_t)M->ntrc * M->P.nlay, n1g = M->n1g;
-    const int L = M->P.lm + 1;
+    const size_t outer = (size_t)M->ntrc * M->P.nlay;
     const double *src[3] = {q, rq, ctrg};
     const size_t inner[3] = {1, 2, 1};
-    for (int k = 0; k < M->n; ++k) {
-        const std::vector<int> rows = M->band[k].row_list();
+    for (const Part &p : parts(M)) {
         std::vector<double> a[3];
-        for (int f = 0; f < 3; ++f)
-            a[f] = M->land ? cut_v(src[f], outer, inner[f], n1g, rows, M->gst) : cut(src[f], outer, inner[f], n1g, rows, L);
-        M_RC(beom_upload_tracers(M->eng[k], ptr(a[0]), ptr(a[1]), ptr(a[2]), errm, errm_len));
+        for (int f = 0; f < 3; ++f) a[f] = cut_rows(src[f], outer, inner[f], p.in);
+        M_RC(beom_upload_tracers(p.eng, ptr(a[0]), ptr(a[1]), ptr(a[2]), errm, errm_len));
     }
     return 0;
 }
@@ -1016,22 +876,14 @@ int beom_multi_download_tracers(beom_multi_handle M, double *q, double *rq, char
     if (M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_download_tracers: the handle carries no tracer (beom_multi_set_tracers)"); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
     if (M->nb == 1) return beom_download_tracers(M->eng[0], q, rq, errm, errm_len);
-    const size_t outer = (size_t)M->ntrc * M->P.nlay, n1g = M->n1g;
-    const int L = M->P.lm + 1;
+    const size_t outer = (size_t)M->ntrc * M->P.nlay;
     double *dst[2] = {q, rq};
     const size_t inner[2] = {1, 2};
-    for (int k = 0; k < M->n; ++k) {
-        const Band &s = M->band[k];
-        const size_t n1l = (size_t)s.n_loc() + 1;
+    for (const Part &p : parts(M)) {
         std::vector<double> a[2];
-        for (int f = 0; f < 2; ++f) if (dst[f]) a[f].assign(outer * n1l * inner[f], 0.0);
-        M_RC(beom_download_tracers(M->eng[k], ptr(a[0]), ptr(a[1]), errm, errm_len));
-        std::vector<int> rows;
-        for (int j = 0; j < s.nown(); ++j) rows.push_back(s.own0 + j);
-        for (int f = 0; f < 2; ++f) {
-            if (M->land) paste_v(dst[f], a[f], outer, inner[f], n1g, n1l, s.lst, M->gst, s.gs + 1, s.nown(), rows, k == 0);
-            else paste(dst[f], a[f], outer, inner[f], n1g, n1l, L, s.gs + 1, s.nown(), rows, k == 0);
-        }
+        for (int f = 0; f < 2; ++f) if (dst[f]) a[f].assign(outer * p.n1() * inner[f], 0.0);
+        M_RC(beom_download_tracers(p.eng, ptr(a[0]), ptr(a[1]), errm, errm_len));
+        for (int f = 0; f < 2; ++f) copy_rows(dst[f], ptr(a[f]), outer, inner[f], p.out);
     }
     return 0;
 }
@@ -1072,81 +924,23 @@ int beom_multi_download_moments(beom_multi_handle M, double *ref, double *sum, d
     if (sq && M->mom_level < 3) { m_err(errm, errm_len, "beom_multi_download_moments: the second moments are kept at level 3, this handle has level %d", M->mom_level); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
     if (M->nb == 1 && !M->ring) return beom_download_moments(M->eng[0], ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
-    const int nl = M->P.nlay, L = M->P.lm + 1;
-    const size_t n1g = M->n1g;
-    const int nf = M->mom_level >= 2 ? 5 : 3;
+    const int nl = M->P.nlay, nf = M->mom_level >= 2 ? 5 : 3;
     double *dst[3] = {ref, sum, sq};
     const size_t outer[3] = {(size_t)nf * nl, (size_t)nf * nl, (size_t)5 * nl};
-    for (int k = -1; k < M->n; ++k) {
-        if (k < 0 && !M->mini) continue;
-        const size_t n1l = k < 0 ? (size_t)M->mini_rows.size() * L + 1 : (size_t)M->band[k].n_loc() + 1;
+    for (const Part &p : parts(M)) {
         std::vector<double> a[3];
-        for (int f = 0; f < 3; ++f) if (dst[f]) a[f].assign(outer[f] * n1l, 0.0);
+        for (int f = 0; f < 3; ++f) if (dst[f]) a[f].assign(outer[f] * p.n1(), 0.0);
         long long cnt = 0;
         int t0 = 0, t1 = 0;
-        M_RC(beom_download_moments(k < 0 ? M->mini : M->eng[k], ptr(a[0]), ptr(a[1]), ptr(a[2]), &cnt, &t0, &t1, errm, errm_len));
-        if (k == 0) { if (count) *count = cnt; if (tstp_first) *tstp_first = t0; if (tstp_last) *tstp_last = t1; }
-        int j0, n;
-        std::vector<int> rows;
-        if (k < 0) { j0 = (int)M->mini_rows.size(); n = 1; rows.push_back(M->P.mm + 1); }      // the orphan row
-        else { const Band &s = M->band[k]; j0 = s.gs + 1; n = s.nown(); for (int j = 0; j < n; ++j) rows.push_back(s.own0 + j); }
-        for (int f = 0; f < 3; ++f) {
-            if (M->land) paste_v(dst[f], a[f], outer[f], 1, n1g, n1l, M->band[k < 0 ? 0 : k].lst, M->gst, j0, n, rows, k == 0);
-            else paste(dst[f], a[f], outer[f], 1, n1g, n1l, L, j0, n, rows, k == 0);
-        }
+        M_RC(beom_download_moments(p.eng, ptr(a[0]), ptr(a[1]), ptr(a[2]), &cnt, &t0, &t1, errm, errm_len));
+        if (p.k == 0) { if (count) *count = cnt; if (tstp_first) *tstp_first = t0; if (tstp_last) *tstp_last = t1; }
+        for (int f = 0; f < 3; ++f) copy_rows(dst[f], ptr(a[f]), outer[f], 1, p.out);
     }
     return 0;
 }
 
 // ---- output records of all bands (SURVEY §8f N2 for the multi-device handle): as beom_download_outputs /
 //      beom_download_diag with GLOBAL (ndeg, nlay) real*4 records; every band forms its rows on its device.
-namespace {
-// (ndeg, nlay) records have no sentinel: cell (row r, column i) of layer k at (i-1) + (r-1)*L + ndeg*(k-1)
-static std::vector<float> cut_rec(const float *x, int nl, size_t ndeg_g, const std::vector<int> &rows, int L) {
-    std::vector<float> z;
-    if (!x) return z;
-    const size_t nloc = rows.size() * (size_t)L;
-    z.resize(nloc * nl);
-    for (int k = 0; k < nl; ++k)
-        for (size_t r = 0; r < rows.size(); ++r)
-            std::memcpy(&z[k * nloc + r * L], &x[k * ndeg_g + (size_t)(rows[r] - 1) * L], (size_t)L * sizeof(float));
-    return z;
-}
-// (frames with land: rows as packed ranges; records have no sentinel, so cell p sits at p - 1)
-static std::vector<float> cut_rec_v(const float *x, int nl, size_t ndeg_g, const std::vector<int> &rows, const std::vector<long long> &gst) {
-    std::vector<float> z;
-    if (!x) return z;
-    size_t nloc = 0;
-    for (int g : rows) nloc += (size_t)(gst[(size_t)g + 1] - gst[(size_t)g]);
-    z.resize(nloc * nl);
-    for (int k = 0; k < nl; ++k) {
-        size_t at = 0;
-        for (int g : rows) {
-            const size_t len = (size_t)(gst[(size_t)g + 1] - gst[(size_t)g]);
-            if (len) std::memcpy(&z[k * nloc + at], &x[k * ndeg_g + (size_t)gst[(size_t)g] - 1], len * sizeof(float));
-            at += len;
-        }
-    }
-    return z;
-}
-void paste_rec_v(float *dst, const std::vector<float> &loc, int nl, size_t ndeg_g, size_t nloc, const std::vector<long long> &lst,
-                 const std::vector<long long> &gst, int j0, int n, const std::vector<int> &dst_rows) {
-    if (!dst || loc.empty()) return;
-    for (int k = 0; k < nl; ++k)
-        for (int r = 0; r < n; ++r) {
-            const size_t g = (size_t)dst_rows[(size_t)r], len = (size_t)(gst[g + 1] - gst[g]);
-            if (len) std::memcpy(&dst[k * ndeg_g + (size_t)gst[g] - 1], &loc[k * nloc + (size_t)lst[(size_t)(j0 + r)] - 1], len * sizeof(float));
-        }
-}
-void paste_rec(float *dst, const std::vector<float> &loc, int nl, size_t ndeg_g, size_t nloc, int L, int j0, int n,
-               const std::vector<int> &dst_rows) {
-    if (!dst || loc.empty()) return;
-    for (int k = 0; k < nl; ++k)
-        for (int r = 0; r < n; ++r)
-            std::memcpy(&dst[k * ndeg_g + (size_t)(dst_rows[r] - 1) * L], &loc[k * nloc + (size_t)(j0 - 1 + r) * L], (size_t)L * sizeof(float));
-}
-}  // namespace
-
 int beom_multi_download_outputs(beom_multi_handle M, const float *h0r4, float *eta, float *u4, float *v4,
                                 double *minmax, int *thin_layer, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
@@ -1154,36 +948,24 @@ int beom_multi_download_outputs(beom_multi_handle M, const float *h0r4, float *e
     if (!h0r4) { m_err(errm, errm_len, "beom_multi_download_outputs: h_0 (real*4) is needed"); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
     if (M->nb == 1 && !M->ring) return beom_download_outputs(M->eng[0], h0r4, eta, u4, v4, minmax, thin_layer, errm, errm_len);
-    const int nl = M->P.nlay, L = M->P.lm + 1;
-    const size_t ndeg_g = (size_t)M->P.ndeg;
+    const int nl = M->P.nlay;
     if (thin_layer) *thin_layer = 0;
-    for (int k = -1; k < M->n; ++k) {
-        if (k < 0 && !M->mini) continue;
-        const std::vector<int> rows = k < 0 ? M->mini_rows : M->band[k].row_list();
-        const size_t nloc = M->land ? (size_t)M->band[k].n_loc() : rows.size() * (size_t)L;
-        std::vector<float> h0 = M->land ? cut_rec_v(h0r4, nl, ndeg_g, rows, M->gst) : cut_rec(h0r4, nl, ndeg_g, rows, L);
+    for (const Part &p : parts(M)) {
+        const Spans in = p.in.records(), out = p.out.records();
+        const size_t nloc = in.n1dst;
+        const std::vector<float> h0 = cut_rows(h0r4, nl, 1, in);
         std::vector<float> e(eta ? nloc * nl : 0), a(u4 ? nloc * nl : 0), b(v4 ? nloc * nl : 0);
         std::vector<double> mm((size_t)nl * 6);
         int thin = 0;
-        M_RC(beom_download_outputs(k < 0 ? M->mini : M->eng[k], h0.data(), ptr(e), ptr(a), ptr(b), mm.data(), &thin, errm, errm_len));
-        int j0, n;
-        std::vector<int> dst_rows;
-        if (k < 0) { j0 = (int)rows.size(); n = 1; dst_rows.push_back(M->P.mm + 1); }       // the orphan row; its scans are not merged
-        else { const Band &s = M->band[k]; j0 = s.gs + 1; n = s.nown(); for (int j = 0; j < n; ++j) dst_rows.push_back(s.own0 + j); }
-        if (M->land) {
-            paste_rec_v(eta, e, nl, ndeg_g, nloc, M->band[k].lst, M->gst, j0, n, dst_rows);
-            paste_rec_v(u4, a, nl, ndeg_g, nloc, M->band[k].lst, M->gst, j0, n, dst_rows);
-            paste_rec_v(v4, b, nl, ndeg_g, nloc, M->band[k].lst, M->gst, j0, n, dst_rows);
-        } else {
-            paste_rec(eta, e, nl, ndeg_g, nloc, L, j0, n, dst_rows);
-            paste_rec(u4, a, nl, ndeg_g, nloc, L, j0, n, dst_rows);
-            paste_rec(v4, b, nl, ndeg_g, nloc, L, j0, n, dst_rows);
-        }
-        if (k < 0) continue;
+        M_RC(beom_download_outputs(p.eng, h0.data(), ptr(e), ptr(a), ptr(b), mm.data(), &thin, errm, errm_len));
+        copy_rows(eta, ptr(e), nl, 1, out);
+        copy_rows(u4, ptr(a), nl, 1, out);
+        copy_rows(v4, ptr(b), nl, 1, out);
+        if (p.k < 0) continue;                     // the orphan row's scans are not merged
         // a band's scans cover its ghost rows too: they hold the neighbours' owned values (the exchange has landed)
         if (minmax)
             for (int q = 0; q < nl * 6; ++q)
-                minmax[q] = (k == 0) ? mm[q] : ((q % 2 == 0) ? std::fmin(minmax[q], mm[q]) : std::fmax(minmax[q], mm[q]));
+                minmax[q] = (p.k == 0) ? mm[q] : ((q % 2 == 0) ? std::fmin(minmax[q], mm[q]) : std::fmax(minmax[q], mm[q]));
         if (thin_layer && thin > 0 && (*thin_layer == 0 || thin < *thin_layer)) *thin_layer = thin;
     }
     return 0;
@@ -1198,42 +980,11 @@ int beom_multi_set_open_boundaries(beom_multi_handle M, int nseg, const int32_t 
     if (M->local_mode) { m_err(errm, errm_len, "beom_multi_set_open_boundaries: needs a handle created from the global arrays"); return -3; }
     if (M->land) { m_err(errm, errm_len, "beom_multi_set_open_boundaries: not for bands of a frame with land"); return -3; }
     if (M->nb == 1 && !M->ring) return beom_set_open_boundaries(M->eng[0], nseg, segm, errm, errm_len);
-    const int L = M->P.lm + 1;
-    auto S = [&](int is, int col) { return segm[(size_t)is + (size_t)nseg * (col - 1)]; };
-    // k = -1: the companion frame of a ring (rows 1..6, mm-3..mm, mm+1 — it holds the orphan row's end of every segment)
-    for (int k = M->mini ? -1 : 0; k < M->n; ++k) {
-        const std::vector<int> wrows = k < 0 ? M->mini_rows : M->band[k].row_list();   // global row of every local row (a ring's ghosts wrap)
-        // A pass of a segment (its updated cell: column 10 for the first pass, 1 for the second; its source cell: 16 / 13) goes
-        // to EVERY local row that holds the updated cell's global row — in a ring a row can be there twice, owned and as a
-        // wrapped ghost — with the source cell taken from the local row next to it (or itself) that holds the source's row.
-        std::vector<std::array<int32_t, 18>> rowsv;
-        auto row_of = [&](int32_t q) { return (q - 1) / L + 1; };
-        auto col_of = [&](int32_t q) { return (q - 1) % L + 1; };
-        for (int is = 0; is < nseg; ++is)
-            for (int pass = 0; pass < 2; ++pass) {
-                const int cu = pass == 0 ? 10 : 1, cs = pass == 0 ? 16 : 13;
-                const int32_t qu = S(is, cu), qs = S(is, cs);
-                if (qu < 1) continue;
-                for (size_t jl = 0; jl < wrows.size(); ++jl) {
-                    if (wrows[jl] != row_of(qu)) continue;
-                    int32_t src = qs == 0 ? 0 : -1;
-                    if (qs > 0)
-                        for (long long js = (long long)jl - 1; js <= (long long)jl + 1; ++js)
-                            if (js >= 0 && js < (long long)wrows.size() && wrows[(size_t)js] == row_of(qs)) { src = (int32_t)(col_of(qs) + js * L); break; }
-                    if (src < 0) continue;                                   // the source's row is not next to this copy of the row: another band's
-                    std::array<int32_t, 18> r;
-                    for (int c = 1; c <= 18; ++c) r[(size_t)c - 1] = S(is, c);
-                    r[0] = r[9] = -1; r[12] = r[15] = r[6] = 0;              // both passes off, then this one on
-                    r[(size_t)cu - 1] = (int32_t)(col_of(qu) + (long long)jl * L);
-                    r[(size_t)cs - 1] = src;
-                    rowsv.push_back(r);
-                }
-            }
-        const int nloc = (int)rowsv.size();
-        std::vector<int32_t> tab((size_t)nloc * 18);
-        for (int is = 0; is < nloc; ++is)
-            for (int c = 0; c < 18; ++c) tab[(size_t)is + (size_t)nloc * c] = rowsv[(size_t)is][(size_t)c];
-        M_RC(beom_set_open_boundaries(k < 0 ? M->mini : M->eng[k], nloc, nloc ? tab.data() : nullptr, errm, errm_len));
+    // (the companion frame of a ring — rows 1..6, mm-3..mm, mm+1 — holds the orphan row's end of every segment)
+    for (const Part &p : parts(M)) {
+        const std::vector<int32_t> tab = obc_table(obc_window_rows(nseg, segm, p.k < 0 ? M->mini_rows : M->band[p.k].row_list(), M->P.lm + 1));
+        const int nloc = (int)tab.size() / 18;
+        M_RC(beom_set_open_boundaries(p.eng, nloc, nloc ? tab.data() : nullptr, errm, errm_len));
     }
     return 0;
 }
@@ -1250,33 +1001,27 @@ int beom_multi_set_open_boundaries_local(beom_multi_handle M, int nseg, const in
     M_RC(beom_set_open_boundaries(M->eng[0], nseg, nseg ? segm : nullptr, errm, errm_len));
     if (!M->mini) return 0;
     const int L = M->P.lm + 1, gs = M->band[0].gs;
-    std::vector<std::array<int32_t, 18>> rowsv;
+    std::vector<ObcRow> rowsv;
     // window row jl (1-based) -> row of the companion frame, 0 = not there
     auto from_window = [&](int jl) { return (jl >= 1 && jl <= gs) ? kMiniLo + jl : (jl > gs && jl <= gs + kMiniLo) ? jl - gs : 0; };
-    auto from_orphan = [&](int jl) { return jl == 1 ? kMiniLo + kGhost + 1 : 0; };
+    auto from_orphan = [&](int jl) { return jl == 1 ? kMiniRows : 0; };
     for (int src = 0; src < 2; ++src) {
         const int n = src ? nseg_orphan : nseg;
         const int32_t *tab = src ? segm_orphan : segm;
         for (int is = 0; is < n; ++is)
             for (int pass = 0; pass < 2; ++pass) {
-                const int cu = pass == 0 ? 10 : 1, cs = pass == 0 ? 16 : 13;
-                const int32_t qu = tab[(size_t)is + (size_t)n * (cu - 1)], qs = tab[(size_t)is + (size_t)n * (cs - 1)];
+                const ObcRow c = obc_columns(tab, n, is);
+                const int32_t qu = c[pass == 0 ? 9 : 0], qs = c[pass == 0 ? 15 : 12];
                 if (qu < 1) continue;
                 const int mu = src ? from_orphan((qu - 1) / L + 1) : from_window((qu - 1) / L + 1);
                 const int ms = qs > 0 ? (src ? from_orphan((qs - 1) / L + 1) : from_window((qs - 1) / L + 1)) : 0;
                 if (!mu || (qs > 0 && !ms)) continue;
-                std::array<int32_t, 18> r;
-                for (int c = 1; c <= 18; ++c) r[(size_t)c - 1] = tab[(size_t)is + (size_t)n * (c - 1)];
-                r[0] = r[9] = -1; r[12] = r[15] = r[6] = 0;
-                r[(size_t)cu - 1] = (int32_t)((qu - 1) % L + 1 + (long long)(mu - 1) * L);
-                r[(size_t)cs - 1] = qs > 0 ? (int32_t)((qs - 1) % L + 1 + (long long)(ms - 1) * L) : 0;
-                rowsv.push_back(r);
+                rowsv.push_back(obc_pass_row(c, pass, (int32_t)((qu - 1) % L + 1 + (long long)(mu - 1) * L),
+                                             qs > 0 ? (int32_t)((qs - 1) % L + 1 + (long long)(ms - 1) * L) : 0));
             }
     }
+    const std::vector<int32_t> t2 = obc_table(rowsv);
     const int nloc = (int)rowsv.size();
-    std::vector<int32_t> t2((size_t)nloc * 18);
-    for (int is = 0; is < nloc; ++is)
-        for (int c = 0; c < 18; ++c) t2[(size_t)is + (size_t)nloc * c] = rowsv[(size_t)is][(size_t)c];
     return beom_set_open_boundaries(M->mini, nloc, nloc ? t2.data() : nullptr, errm, errm_len);
 }
 
@@ -1285,27 +1030,15 @@ int beom_multi_download_diag(beom_multi_handle M, float *pvor4, float *mont4, fl
     if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_diag: this handle holds a window"); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
     if (M->nb == 1 && !M->ring) return beom_download_diag(M->eng[0], pvor4, mont4, vcc4, errm, errm_len);
-    const int nl = M->P.nlay, L = M->P.lm + 1;
-    const size_t ndeg_g = (size_t)M->P.ndeg;
-    for (int k = -1; k < M->n; ++k) {
-        if (k < 0 && !M->mini) continue;
-        const std::vector<int> rows = k < 0 ? M->mini_rows : M->band[k].row_list();
-        const size_t nloc = M->land ? (size_t)M->band[k].n_loc() : rows.size() * (size_t)L;
+    const int nl = M->P.nlay;
+    for (const Part &p : parts(M)) {
+        const Spans out = p.out.records();
+        const size_t nloc = out.n1src;
         std::vector<float> a(pvor4 ? nloc * nl : 0), b(mont4 ? nloc * nl : 0), c(vcc4 ? nloc * nl : 0);
-        M_RC(beom_download_diag(k < 0 ? M->mini : M->eng[k], ptr(a), ptr(b), ptr(c), errm, errm_len));
-        int j0, n;
-        std::vector<int> dst_rows;
-        if (k < 0) { j0 = (int)rows.size(); n = 1; dst_rows.push_back(M->P.mm + 1); }
-        else { const Band &s = M->band[k]; j0 = s.gs + 1; n = s.nown(); for (int j = 0; j < n; ++j) dst_rows.push_back(s.own0 + j); }
-        if (M->land) {
-            paste_rec_v(pvor4, a, nl, ndeg_g, nloc, M->band[k].lst, M->gst, j0, n, dst_rows);
-            paste_rec_v(mont4, b, nl, ndeg_g, nloc, M->band[k].lst, M->gst, j0, n, dst_rows);
-            paste_rec_v(vcc4, c, nl, ndeg_g, nloc, M->band[k].lst, M->gst, j0, n, dst_rows);
-        } else {
-            paste_rec(pvor4, a, nl, ndeg_g, nloc, L, j0, n, dst_rows);
-            paste_rec(mont4, b, nl, ndeg_g, nloc, L, j0, n, dst_rows);
-            paste_rec(vcc4, c, nl, ndeg_g, nloc, L, j0, n, dst_rows);
-        }
+        M_RC(beom_download_diag(p.eng, ptr(a), ptr(b), ptr(c), errm, errm_len));
+        copy_rows(pvor4, ptr(a), nl, 1, out);
+        copy_rows(mont4, ptr(b), nl, 1, out);
+        copy_rows(vcc4, ptr(c), nl, 1, out);
     }
     return 0;
 }
@@ -1348,10 +1081,13 @@ int beom_multi_upload_local(beom_multi_handle M, const beom_state *win, const be
         if (!orphan) { m_err(errm, errm_len, "beom_multi_upload_local: band 0 of a ring needs the orphan row's state"); return -1; }
         double *wp[13], *op[13];
         state_ptrs(win, wp); state_ptrs(orphan, op);
+        const Spans from_win = spans_window_to_mini(M->band[0]), from_orphan = spans_orphan_to_mini(M->P.lm + 1);
         StateV a;
-        for (int f = 0; f < 13; ++f) a.a[f] = mini_from_window(wp[f], op[f], kState[f].outer(M->P.nlay), kState[f].inner, M->band[0]);
-        M_RC(beom_upload_state(M->mini, ptr(a.a[0]), ptr(a.a[1]), ptr(a.a[2]), ptr(a.a[3]), ptr(a.a[4]), ptr(a.a[5]), ptr(a.a[6]),
-                               ptr(a.a[7]), ptr(a.a[8]), ptr(a.a[9]), ptr(a.a[10]), ptr(a.a[11]), ptr(a.a[12]), errm, errm_len));
+        for (int f = 0; f < 13; ++f) {
+            a.a[f] = cut_rows<double>(wp[f], kState[f].outer(M->P.nlay), kState[f].inner, from_win);
+            copy_rows<double>(ptr(a.a[f]), op[f], kState[f].outer(M->P.nlay), kState[f].inner, from_orphan);
+        }
+        M_RC(upload_state_v(M->mini, a, errm, errm_len));
     }
     return 0;
 }
@@ -1364,17 +1100,14 @@ int beom_multi_download_local(beom_multi_handle M, beom_state *win, beom_state *
         M_RC(beom_download_state(M->eng[0], win->hlay, win->u, win->v, win->h_u, win->h_v, win->rs_h, win->dmdx, win->dmdy,
                                  win->v_cc, win->v_ll, win->tt3d, win->tb3d, win->tu3d, errm, errm_len));
     if (orphan && M->mini) {
-        const int nl = M->P.nlay, L = M->P.lm + 1;
-        const size_t n1m = (size_t)M->mini_rows.size() * L + 1, n1o = (size_t)L + 1;
+        const int nl = M->P.nlay;
+        const Spans out = spans_mini_to_orphan(M->P.lm + 1);
         double *op[13];
         state_ptrs(orphan, op);
         StateV a;
-        for (int f = 0; f < 13; ++f) if (op[f]) a.a[f].assign(kState[f].outer(nl) * n1m * kState[f].inner, 0.0);
-        M_RC(beom_download_state(M->mini, ptr(a.a[0]), ptr(a.a[1]), ptr(a.a[2]), ptr(a.a[3]), ptr(a.a[4]), ptr(a.a[5]), ptr(a.a[6]),
-                                 ptr(a.a[7]), ptr(a.a[8]), ptr(a.a[9]), ptr(a.a[10]), ptr(a.a[11]), ptr(a.a[12]), errm, errm_len));
-        const std::vector<int> one(1, 1);
-        for (int f = 0; f < 13; ++f)
-            paste(op[f], a.a[f], kState[f].outer(nl), kState[f].inner, n1o, n1m, L, (int)M->mini_rows.size(), 1, one, true);
+        for (int f = 0; f < 13; ++f) if (op[f]) a.a[f].assign(kState[f].outer(nl) * out.n1src * kState[f].inner, 0.0);
+        M_RC(download_state_v(M->mini, a, errm, errm_len));
+        for (int f = 0; f < 13; ++f) copy_rows(op[f], ptr(a.a[f]), kState[f].outer(nl), kState[f].inner, out);
     }
     return 0;
 }

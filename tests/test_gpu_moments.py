@@ -210,6 +210,36 @@ def test_bands_give_the_single_handles_bits(level, overlap):
         many.close()
 
 
+def test_bands_of_a_frame_with_land_give_the_single_handles_bits():
+    """Moments on 2 and 3 bands of a frame WITH land: the bands' rows differ in length, the global arrays take each band's
+    packed row ranges.  The island is an ellipse (half-axes 0.2 lm and 0.3 mm around (0.4 lm, 0.5 mm)): a disc of radius
+    0.2 lm would lie between the two seams of 3 bands, which fall near rows mm/3 and 2 mm/3."""
+    p, files = I.case_headline(48, 100, 2)
+    files = {k: np.array(v, dtype=np.float64) for k, v in files.items()}
+    x = np.arange(p.lm + 2)[:, None]; y = np.arange(p.mm + 2)[None, :]
+    land = ((x - 0.4 * p.lm) / (0.2 * p.lm)) ** 2 + ((y - 0.5 * p.mm) / (0.3 * p.mm)) ** 2 < 1.0
+    files["h_bo"][land] = 0.0
+    files["init"][land] = 0.0
+    p = p.replace(ndeg=I.get_nbr_deg_freedom(files["h_bo"]))
+    f = read_input_data(p, files=files)
+    e = capi.Engine(f)
+    assert e.is_embedded
+    want = _stepped(e, 3, 2)
+    e.close()
+    assert (want["count"], want["tstp_first"], want["tstp_last"]) == (6, 2, 12) and np.any(want["sum"][:, :, 1:] != 0.0)
+    row_len = np.bincount(f.subc[1, 1:], minlength=p.mm + 2)
+    for nb in (2, 3):
+        many = capi.MultiEngine(f, devices=[0] * nb)
+        assert many.count == nb
+        bands = [many.band(k) for k in range(nb)]
+        for k in range(nb - 1):                   # the island crosses every seam: the rows on both sides are short
+            assert bands[k + 1]["own0"] == bands[k]["own1"] + 1
+            assert row_len[bands[k]["own1"]] < p.lm + 1 and row_len[bands[k + 1]["own0"]] < p.lm + 1, (nb, k, bands)
+        got = _stepped(many, 3, 2)
+        _same_downloads(got, want, ("closed_2l with an island", nb))
+        many.close()
+
+
 def test_a_ring_of_bands_gives_the_single_handles_bits():
     """A frame periodic in y on 2 bands: the orphan row mm+1 comes from the companion frame's own moments."""
     f = copy.copy(_band_frame("jet_xyper_2l"))

@@ -226,6 +226,22 @@ def load(path: Optional[str] = None) -> C.CDLL:
         for name in ("beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track",
                      "beom_update_floats"):
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_multi_set_floats"):    # (likewise: an older build has no floats on bands)
+        ullp = C.POINTER(C.c_ulonglong)
+        vpp = C.POINTER(C.c_void_p)
+        lib.beom_multi_set_floats.argtypes = [MH, C.c_int64, ci, cp, ci]
+        lib.beom_multi_upload_floats.argtypes = [MH, dpp, dpp, ipp, cp, ci]
+        lib.beom_multi_download_floats.argtypes = [MH, dpp, dpp, ipp, ipp, cp, ci]
+        lib.beom_multi_update_floats.argtypes = [MH, ci]
+        lib.beom_band_floats_set.argtypes = [H, C.c_int64, ci, ci, ci, ci, ci, ci, ci, ci, ci, cp, ci]
+        lib.beom_band_floats_check.argtypes = [H, dpp, dpp, ullp, cp, ci]
+        lib.beom_band_floats_commit.argtypes = [H, ipp, cp, ci]
+        lib.beom_band_floats_launch.argtypes = [H, ci]
+        lib.beom_band_floats_ingest.argtypes = [H]
+        lib.beom_band_floats_boxes.argtypes = [H, vpp, vpp, vpp, vpp, C.POINTER(C.c_size_t)]
+        lib.beom_band_floats_download.argtypes = [H, dpp, dpp, ipp, ipp, ullp, cp, ci]
+        for name in MULTI_FLOAT_EXPORTS:
+            getattr(lib, name).restype = ci
     if hasattr(lib, "beom_set_moments"):         # (likewise: an older build has no moments)
         llp = C.POINTER(C.c_longlong)
         lib.beom_set_moments.argtypes = [H, ci, ci, cp, ci]
@@ -260,6 +276,11 @@ def load(path: Optional[str] = None) -> C.CDLL:
     return lib
 
 
+MULTI_FLOAT_EXPORTS = ("beom_multi_set_floats", "beom_multi_upload_floats", "beom_multi_download_floats", "beom_multi_update_floats",
+                       "beom_band_floats_set", "beom_band_floats_check", "beom_band_floats_commit", "beom_band_floats_launch",
+                       "beom_band_floats_ingest", "beom_band_floats_boxes", "beom_band_floats_download")
+ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
+
 EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "beom_info", "beom_download_diag", "beom_create", "beom_destroy", "beom_set_rigid_lid", "beom_download_pressure",
            "beom_upload_state", "beom_download_state", "beom_download_scratch", "beom_step",
            "beom_sync", "beom_update_h", "beom_update_mont_rvor_pvor_dive_kine",
@@ -281,7 +302,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
            "beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
-           "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments")
+           "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments") + MULTI_FLOAT_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -368,35 +389,47 @@ class _Tracers:
 class _Floats:
     """Lagrangian floats of a handle (beom_set_floats, include/beom_hip.h): positions x, y in grid units (cell (i, j) spans
     [i-1, i] x [j-1, j]), a fixed 1-based layer per float, moved by every step with Heun's method on the layer velocities.
-    Single handles only: a band refuses them."""
+    Shared by Engine and MultiEngine (floats on bands: replicated slots and hand-over records, no track recorder)."""
 
     nfloats = 0
     float_records = 0
+    _flt_multi = False
 
-    def set_floats(self, x, y, layer, records: int = 0, stride: int = 1):
+    def set_floats(self, x, y, layer, records: int = 0, stride: int = 1, capacity: int = 0):
         """Replaces the handle's floats by these (arrays of one length; an empty x frees them) and zeroes their `rejected`
         counters.  records > 0: a recorder of that many records (x, y, h) per float, one behind every step with
-        tstp % stride == 0 (download_float_track).  Between steps only."""
+        tstp % stride == 0 (download_float_track); single handles only.  capacity (MultiEngine): records an outbox holds per
+        side and step, 0 = max(4096, n / 8).  Between steps only."""
         x = np.ascontiguousarray(x, dtype=np.float64).ravel()
         y = np.ascontiguousarray(y, dtype=np.float64).ravel()
         layer = np.ascontiguousarray(np.broadcast_to(np.asarray(layer, dtype=np.int32), x.shape), dtype=np.int32)
         if y.shape != x.shape:
             raise BeomError("set_floats: x of %d positions, y of %d" % (x.size, y.size))
-        self._check(self.lib.beom_set_floats(self.h, x.size, int(records), int(stride), self._err, ERRLEN))
+        if self._flt_multi:
+            if records > 0:
+                raise BeomError("beom_hip error -6: set_floats: bands keep no track recorder (records = %d): a float's records would be "
+                                "spread over the bands it has visited; record on a single handle" % records)
+            free = lambda: self.lib.beom_multi_set_floats(self.h, 0, 0, None, 0)
+            self._check(self.lib.beom_multi_set_floats(self.h, x.size, int(capacity), self._err, ERRLEN))
+            upload = self.lib.beom_multi_upload_floats
+        else:
+            free = lambda: self.lib.beom_set_floats(self.h, 0, 0, 1, None, 0)
+            self._check(self.lib.beom_set_floats(self.h, x.size, int(records), int(stride), self._err, ERRLEN))
+            upload = self.lib.beom_upload_floats
         self.nfloats, self.float_records = 0, 0
         if x.size:
             try:
-                self._check(self.lib.beom_upload_floats(self.h, _dp(x), _dp(y), _ip(layer), self._err, ERRLEN))
+                self._check(upload(self.h, _dp(x), _dp(y), _ip(layer), self._err, ERRLEN))
             except BeomError:
-                self.lib.beom_set_floats(self.h, 0, 0, 1, None, 0)       # (refused positions: the handle carries no floats)
+                free()                                                   # (refused positions: the handle carries no floats)
                 raise
             self.nfloats, self.float_records = int(x.size), int(records)
 
     def download_floats(self) -> dict:
         n = self.nfloats
         out = {"x": np.zeros(n), "y": np.zeros(n), "layer": np.zeros(n, dtype=np.int32), "rejected": np.zeros(n, dtype=np.int32)}
-        self._check(self.lib.beom_download_floats(self.h, _dp(out["x"]), _dp(out["y"]), _ip(out["layer"]), _ip(out["rejected"]),
-                                                  self._err, ERRLEN))
+        fn = self.lib.beom_multi_download_floats if self._flt_multi else self.lib.beom_download_floats
+        self._check(fn(self.h, _dp(out["x"]), _dp(out["y"]), _ip(out["layer"]), _ip(out["rejected"]), self._err, ERRLEN))
         return out
 
     def download_float_track(self) -> dict:
@@ -410,7 +443,7 @@ class _Floats:
 
     def update_floats(self, stage: int):
         """Per-sweep entry: stage 1 or stage 2 of the scheme on the velocities as they stand (no record)."""
-        rc = self.lib.beom_update_floats(self.h, int(stage))
+        rc = (self.lib.beom_multi_update_floats if self._flt_multi else self.lib.beom_update_floats)(self.h, int(stage))
         if rc != 0:
             raise BeomError("beom_update_floats(stage %d) = %d (floats set and uploaded? stage 1 or 2?)" % (stage, rc))
 
@@ -691,7 +724,7 @@ class Engine(_Tracers, _Floats, _Moments):
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Moments):
+class MultiEngine(_Tracers, _Floats, _Moments):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""
@@ -721,6 +754,7 @@ class MultiEngine(_Tracers, _Moments):
     _check = Engine._check
     _trc_prefix = "beom_multi_"
     _mom_multi = True
+    _flt_multi = True
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
@@ -818,11 +852,16 @@ class MultiEngine(_Tracers, _Moments):
         self._check(self.lib.beom_multi_set_option(self.h, name.encode(), int(value)))
 
     def info(self, what: str) -> int:
-        """beom_info of band 0's handle (all bands of a frame run the same launches)."""
-        v = self.lib.beom_info(self.band_engine_handle(0), what.encode())
-        if v < 0:
-            raise BeomError("beom_info(%s) = %d" % (what, v))
-        return v
+        """beom_info of band 0's handle (all bands of a frame run the same launches); "float_handovers": the records ingested
+        so far, summed over the bands, as the latest download_floats read them."""
+        bands = range(self.count) if what == "float_handovers" else (0,)
+        total = 0
+        for k in bands:
+            v = self.lib.beom_info(self.band_engine_handle(k), what.encode())
+            if v < 0:
+                raise BeomError("beom_info(%s) = %d" % (what, v))
+            total += v
+        return total
 
     def band_engine_handle(self, k: int) -> C.c_void_p:
         h = C.c_void_p()

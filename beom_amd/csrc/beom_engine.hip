@@ -147,6 +147,14 @@ struct beom_engine {
     long long flt_launches = 0;        // beom_info "float_launches"
     bool cellmap_known = false;        // integ_cellmap (table path) and integ_xper / integ_yper are set
     std::vector<void *> flt_allocs;
+    // floats on a band of rows (beom_band_floats_*): the same arrays hold ALL floats of the frame; the band's rows, its two
+    // outboxes and inboxes (count + capacity records each) and the three device counts
+    bool flt_band = false;
+    FloatBand flt_fb{};
+    unsigned long long *flt_in_s = nullptr, *flt_in_n = nullptr;
+    int flt_xper = 0, flt_yper = 0;
+    double flt_fmm = 0.0;
+    long long flt_handovers = 0;       // beom_info "float_handovers": records ingested, as the latest download read it
     // moments (beom_set_moments; beom_moments.h): per field the reference, the shifted sum and, at level 3, the shifted
     // second moment, in arrays of the state's shape; the steps of the first and the latest sample
     int mom_level = 0, mom_stride = 1;
@@ -731,7 +739,16 @@ static FloatView float_view(const beom_engine *E, double *rec) {
 }
 static void launch_floats(beom_engine *E, int mode, double *rec) {
     const DevView &d = E->d;
-    const FloatView f = float_view(E, rec);
+    FloatView f = float_view(E, rec);
+    if (E->flt_band) {                 // a band: the frame's wraps and rows, not the window's
+        f.fmm = E->flt_fmm; f.xper = E->flt_xper; f.yper = E->flt_yper; f.cellmap = nullptr;
+        const dim3 g((unsigned)((E->nflt + BEOM_BLOCK - 1) / BEOM_BLOCK)), b(BEOM_BLOCK);
+        if (mode == 1) hipLaunchKernelGGL(k_floats_band<1>, g, b, 0, E->stream, d, f, E->flt_fb);
+        else if (mode == 2) hipLaunchKernelGGL(k_floats_band<2>, g, b, 0, E->stream, d, f, E->flt_fb);
+        else hipLaunchKernelGGL(k_floats_band<3>, g, b, 0, E->stream, d, f, E->flt_fb);
+        ++E->flt_launches;
+        return;
+    }
     const dim3 g((unsigned)((E->nflt + BEOM_BLOCK - 1) / BEOM_BLOCK)), b(BEOM_BLOCK);
 #define FLT_GO(m) do { if (E->dense) hipLaunchKernelGGL((k_floats<CellDense, m>), g, b, 0, E->stream, d, f); \
                        else hipLaunchKernelGGL((k_floats<CellGather, m>), g, b, 0, E->stream, d, f); } while (0)
@@ -1104,7 +1121,7 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
     if (tstp_first < 1 || nsteps < 0 || n_3d < 1) { set_err(errm, errm_len, "beom_step: bad arguments"); return -3; }
     if (E->P.flag_nudging && E->P.mcbc < 0.5 && !E->obc && !E->obc_set) { set_err(errm, errm_len, "beom_step: mcbc = 0 with nudging needs beom_set_open_boundaries (no_gradient_obc, private_mod.f95:2613-2679)"); return -6; }
     if (E->lid && !E->lid_ready) { set_err(errm, errm_len, "beom_step: rgld = 1 needs beom_set_rigid_lid (the Poisson operators Ow, Os, Osum_ and the lid pressure, private_mod.f95:505-563)"); return -6; }
-    const bool flt = E->nflt > 0;
+    const bool flt = E->nflt > 0 && !E->flt_band;      // (a band's floats are launched by beom_multi_step, around the exchange)
     if (flt && !E->flt_ready) { set_err(errm, errm_len, "beom_step: the handle's %lld floats have no positions yet (beom_upload_floats)", E->nflt); return -3; }
     if (flt && E->flt_nrec > 0) {          // the recorder must hold every record of the call: refused before anything is launched
         long long due = 0;
@@ -1456,6 +1473,7 @@ static void free_floats(beom_engine *E) {
     E->flt_x = E->flt_y = E->flt_k1x = E->flt_k1y = E->flt_xs = E->flt_ys = E->flt_rec = nullptr;
     E->flt_layer = E->flt_rej = nullptr;
     E->flt_first_dry = nullptr;
+    E->flt_band = false; E->flt_fb = FloatBand{}; E->flt_in_s = E->flt_in_n = nullptr; E->flt_handovers = 0;
 }
 // a zeroed device array of n elements of `size` bytes
 static int alloc_float_array(beom_engine *E, void *p, size_t n, size_t size, char *errm, int errm_len) {
@@ -1497,6 +1515,7 @@ int beom_set_floats(beom_handle E, int64_t n, int nrec, int stride, char *errm, 
 
 int beom_upload_floats(beom_handle E, const double *x, const double *y, const int32_t *layer, char *errm, int errm_len) {
     if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->flt_band) { set_err(errm, errm_len, "beom_upload_floats: this handle is a band; its floats belong to the multi handle (beom_multi_upload_floats)"); return -3; }
     if (E->nflt < 1) { set_err(errm, errm_len, "beom_upload_floats: the handle carries no float (beom_set_floats)"); return -3; }
     if (!x || !y || !layer) { set_err(errm, errm_len, "beom_upload_floats: null array"); return -1; }
     HIP_TRY(hipSetDevice(E->device));
@@ -1573,9 +1592,133 @@ int beom_download_float_track(beom_handle E, double *rec, int *count, int *tstp_
 int beom_update_floats(beom_handle E, int stage) {
     if (!E) return -1;
     if (hipSetDevice(E->device) != hipSuccess) return -9;
-    if (E->nflt < 1 || !E->flt_ready || (stage != 1 && stage != 2)) return -3;
+    if (E->nflt < 1 || !E->flt_ready || E->flt_band || (stage != 1 && stage != 2)) return -3;
     launch_floats(E, stage, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+// ---- floats on a band of rows: what beom_multi.hip builds its float calls from (include/beom_hip.h) ------------------------
+int beom_band_floats_set(beom_handle E, int64_t n, int capacity, int own0, int nown, int ghost_s, int has_south, int has_north,
+                         int frame_mm, int xper, int ring, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    free_floats(E);
+    if (n == 0) return 0;
+    if (n < 0 || capacity < 1 || !E->dense || !E->d.slab || nown < 1 || ghost_s < 0 || ghost_s + nown > E->d.M || own0 < 1 ||
+        own0 + nown - 1 > frame_mm + 1) {
+        set_err(errm, errm_len, "beom_band_floats_set: %lld floats, capacity %d, rows %d..%d (+%d) of %d on a window of %d rows: needs a dense band",
+                (long long)n, capacity, own0, own0 + nown - 1, ghost_s, frame_mm + 1, E->d.M);
+        return -3;
+    }
+    int rc = 0;
+    E->nflt = (long long)n;
+    const size_t m = (size_t)n, box = (size_t)kFloatRecordWords * ((size_t)capacity + 1);
+    for (double **a : {&E->flt_x, &E->flt_y, &E->flt_k1x, &E->flt_k1y, &E->flt_xs, &E->flt_ys})
+        if ((rc = alloc_float_array(E, a, m, sizeof(double), errm, errm_len))) { free_floats(E); return rc; }
+    for (int32_t **a : {&E->flt_layer, &E->flt_rej})
+        if ((rc = alloc_float_array(E, a, m, sizeof(int32_t), errm, errm_len))) { free_floats(E); return rc; }
+    if ((rc = alloc_float_array(E, &E->flt_first_dry, 1, sizeof(unsigned long long), errm, errm_len))) { free_floats(E); return rc; }
+    FloatBand fb{};
+    fb.own0 = own0; fb.nown = nown; fb.gs = ghost_s; fb.Mf = frame_mm + 1; fb.nring = ring ? frame_mm : 0; fb.capacity = capacity;
+    fb.lo = (ring || has_south) ? std::max(1, ghost_s + 1 - kFloatReach) : 1;
+    fb.hi = (ring || has_north) ? std::min(E->d.M - 1, ghost_s + nown + kFloatReach) : E->d.M;
+    if ((rc = alloc_float_array(E, &fb.stats, 4, sizeof(unsigned long long), errm, errm_len))) { free_floats(E); return rc; }
+    if (has_south && ((rc = alloc_float_array(E, &fb.box_s, box, sizeof(unsigned long long), errm, errm_len)) ||
+                      (rc = alloc_float_array(E, &E->flt_in_s, box, sizeof(unsigned long long), errm, errm_len)))) { free_floats(E); return rc; }
+    if (has_north && ((rc = alloc_float_array(E, &fb.box_n, box, sizeof(unsigned long long), errm, errm_len)) ||
+                      (rc = alloc_float_array(E, &E->flt_in_n, box, sizeof(unsigned long long), errm, errm_len)))) { free_floats(E); return rc; }
+    E->flt_fb = fb; E->flt_band = true;
+    E->flt_xper = xper != 0; E->flt_yper = ring != 0; E->flt_fmm = (double)frame_mm;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+// the candidates go to the scratch of stage 1; *first_dry = the smallest index of a float of this band's rows that does not
+// start in a wet cell (~0 = none).  Nothing the handle holds is replaced until beom_band_floats_commit.
+int beom_band_floats_check(beom_handle E, const double *x, const double *y, unsigned long long *first_dry, char *errm, int errm_len) {
+    if (!E || !x || !y || !first_dry) { set_err(errm, errm_len, "beom_band_floats_check: null argument"); return -1; }
+    if (!E->flt_band) { set_err(errm, errm_len, "beom_band_floats_check: the handle carries no band floats (beom_band_floats_set)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t n = (size_t)E->nflt;
+    const unsigned long long none = ~0ull;
+    HIP_TRY(hipMemcpyAsync(E->flt_xs, x, n * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_ys, y, n * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_first_dry, &none, sizeof(none), hipMemcpyHostToDevice, E->stream));
+    FloatView f = float_view(E, nullptr);
+    f.fmm = E->flt_fmm; f.xper = E->flt_xper; f.yper = E->flt_yper; f.cellmap = nullptr;
+    const dim3 g((unsigned)((E->nflt + BEOM_BLOCK - 1) / BEOM_BLOCK)), b(BEOM_BLOCK);
+    hipLaunchKernelGGL(k_floats_check_band, g, b, 0, E->stream, E->d, f, E->flt_fb, E->flt_first_dry);
+    HIP_TRY(hipMemcpyAsync(first_dry, E->flt_first_dry, sizeof(none), hipMemcpyDeviceToHost, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int beom_band_floats_commit(beom_handle E, const int32_t *layer, char *errm, int errm_len) {
+    if (!E || !layer) { set_err(errm, errm_len, "beom_band_floats_commit: null argument"); return -1; }
+    if (!E->flt_band) { set_err(errm, errm_len, "beom_band_floats_commit: the handle carries no band floats"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t n = (size_t)E->nflt, box = sizeof(unsigned long long) * kFloatRecordWords;
+    HIP_TRY(hipMemcpyAsync(E->flt_x, E->flt_xs, n * sizeof(double), hipMemcpyDeviceToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_y, E->flt_ys, n * sizeof(double), hipMemcpyDeviceToDevice, E->stream));
+    HIP_TRY(hipMemcpyAsync(E->flt_layer, layer, n * sizeof(int32_t), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipMemsetAsync(E->flt_rej, 0, n * sizeof(int32_t), E->stream));
+    HIP_TRY(hipMemsetAsync(E->flt_k1x, 0, n * sizeof(double), E->stream));
+    HIP_TRY(hipMemsetAsync(E->flt_k1y, 0, n * sizeof(double), E->stream));
+    HIP_TRY(hipMemsetAsync(E->flt_fb.stats, 0, 4 * sizeof(unsigned long long), E->stream));
+    for (unsigned long long *q : {E->flt_fb.box_s, E->flt_fb.box_n, E->flt_in_s, E->flt_in_n})
+        if (q) HIP_TRY(hipMemsetAsync(q, 0, box, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    E->flt_ready = true;
+    return 0;
+}
+
+int beom_band_floats_launch(beom_handle E, int mode) {
+    if (!E) return -1;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    if (!E->flt_band || !E->flt_ready || mode < 1 || mode > 3) return -3;
+    launch_floats(E, mode, nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int beom_band_floats_boxes(beom_handle E, void **out_s, void **out_n, void **in_s, void **in_n, size_t *bytes) {
+    if (!E || !E->flt_band) return -3;
+    if (out_s) *out_s = E->flt_fb.box_s;
+    if (out_n) *out_n = E->flt_fb.box_n;
+    if (in_s) *in_s = E->flt_in_s;
+    if (in_n) *in_n = E->flt_in_n;
+    if (bytes) *bytes = sizeof(unsigned long long) * kFloatRecordWords * ((size_t)E->flt_fb.capacity + 1);
+    return 0;
+}
+
+int beom_band_floats_ingest(beom_handle E) {
+    if (!E) return -1;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    if (!E->flt_band || !E->flt_ready) return -3;
+    FloatView f = float_view(E, nullptr);
+    const dim3 g((unsigned)((E->flt_fb.capacity + BEOM_BLOCK - 1) / BEOM_BLOCK), 2u), b(BEOM_BLOCK);
+    hipLaunchKernelGGL(k_floats_ingest, g, b, 0, E->stream, f, E->flt_fb, E->flt_in_s, E->flt_in_n);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int beom_band_floats_download(beom_handle E, double *x, double *y, int32_t *layer, int32_t *rejected, unsigned long long *stats3,
+                              char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (!E->flt_band) { set_err(errm, errm_len, "beom_band_floats_download: the handle carries no band floats"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t n = (size_t)E->nflt;
+    unsigned long long st[3] = {0, 0, 0};
+    if (x) HIP_TRY(hipMemcpyAsync(x, E->flt_x, n * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    if (y) HIP_TRY(hipMemcpyAsync(y, E->flt_y, n * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    if (layer) HIP_TRY(hipMemcpyAsync(layer, E->flt_layer, n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    if (rejected) HIP_TRY(hipMemcpyAsync(rejected, E->flt_rej, n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    HIP_TRY(hipMemcpyAsync(st, E->flt_fb.stats, sizeof(st), hipMemcpyDeviceToHost, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    E->flt_handovers = (long long)st[2];
+    if (stats3) for (int q = 0; q < 3; ++q) stats3[q] = st[q];
+    return 0;
 }
 
 // ---- moments (beom_moments.h) ----------------------------------------------------------------------------------------------
@@ -1728,6 +1871,7 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "floats")) return (int)std::min<long long>(E->nflt, 2000000000ll);
     if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
     if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far
+    if (!strcmp(what, "float_handovers")) return (int)std::min<long long>(E->flt_handovers, 2000000000ll);   // (bands; as of the latest download)
     if (!strcmp(what, "moments")) return E->mom_level;
     if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom_count, 2000000000ll);
     if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom_launches, 2000000000ll);     // all calls so far

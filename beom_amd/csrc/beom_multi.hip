@@ -280,6 +280,14 @@ struct beom_multi {
     // moments kept by every band (beom_multi_set_moments): the bands sample on request ("moments_by_caller"), the step whose
     // sample is still owed (0 = none) is taken where the main streams next join the exchange
     int mom_level = 0, mom_stride = 1, mom_due = 0;
+    // Lagrangian floats on the bands (beom_multi_set_floats): every band holds all nflt slots; flt_mode is the float launch
+    // owed where the main streams next join the exchange (0 none, 1 stage 1, 3 stage 2 + stage 1 of the next step)
+    long long nflt = 0;
+    int flt_cap = 0, flt_mode = 0;
+    bool flt_ready = false;
+    size_t flt_box_bytes = 0;
+    std::vector<hipEvent_t> flt_done, flt_copied;     // behind a band's float launch | behind its copies of the neighbours' outboxes
+    std::vector<void *> flt_out_s, flt_out_n, flt_in_s, flt_in_n;
     // companion frame of a y-periodic ring (lives with band 0): rows 1..kMiniLo, Mr-3..Mr, Mr+1
     beom_handle mini = nullptr;
     int mini_k = -1;               // local index of band 0, or -1 if band 0 is not here
@@ -349,6 +357,8 @@ void destroy_all(beom_multi *M) {
         if (k < (int)M->packed.size() && M->packed[k]) (void)hipEventDestroy(M->packed[k]);
         if (k < (int)M->landed.size() && M->landed[k]) (void)hipEventDestroy(M->landed[k]);
         if (k < (int)M->p1done.size() && M->p1done[k]) (void)hipEventDestroy(M->p1done[k]);
+        if (k < (int)M->flt_done.size() && M->flt_done[k]) (void)hipEventDestroy(M->flt_done[k]);
+        if (k < (int)M->flt_copied.size() && M->flt_copied[k]) (void)hipEventDestroy(M->flt_copied[k]);
         if (k < (int)M->comm_s.size() && M->comm_s[k]) (void)hipStreamDestroy(M->comm_s[k]);
         if (k < (int)M->main_s.size() && M->main_s[k]) (void)hipStreamDestroy(M->main_s[k]);
     }
@@ -888,6 +898,196 @@ int beom_multi_download_tracers(beom_multi_handle M, double *q, double *rq, char
     return 0;
 }
 
+// ---- Lagrangian floats (beom_set_floats) on the bands: replicated slots, the owner acts, a float that leaves its band's rows
+//      travels as one 64-byte record through an outbox (include/beom_hip.h "Floats on bands"; beom_floats.h) ----
+static bool multi_whole(const beom_multi *M) { return M->nb == 1 && !M->ring; }
+
+// is floor(y) + 1 a row of band b?  (the kernels' owner test, on the host)
+static bool band_owns(const beom_multi *M, const Band &b, double y) {
+    const double fy = std::floor(y);
+    const int lim = M->ring ? M->P.mm : M->P.mm + 1;
+    if (!(fy >= 0.0 && fy < (double)lim)) return false;
+    const int g = (int)fy + 1;
+    return g >= b.own0 && g <= b.own1;
+}
+
+int beom_multi_set_floats(beom_multi_handle M, int64_t n, int capacity, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_floats: an earlier step failed half way; destroy the handle"); return -30; }
+    if (n < 0 || capacity < 0) { m_err(errm, errm_len, "beom_multi_set_floats: %lld floats, capacity %d (n >= 0, capacity >= 0)", (long long)n, capacity); return -3; }
+    if (M->local_mode) {
+        m_err(errm, errm_len, "beom_multi_set_floats: a handle that holds one band's window does not carry floats: a float that leaves the band would "
+              "have to travel to another process (fixed-size messages over RCCL or shared memory), which is not built; use a handle created from the global arrays");
+        return -6;
+    }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    M->nflt = 0; M->flt_ready = false; M->flt_mode = 0;
+    if (multi_whole(M)) {
+        M_RC(beom_set_floats(M->eng[0], n, 0, 1, errm, errm_len));
+        M->nflt = (long long)n;
+        return 0;
+    }
+    if (capacity == 0) capacity = (int)std::min<long long>(std::max<long long>(4096, (long long)n / 8), 1ll << 24);
+    const int nb = M->n;
+    if (M->flt_done.empty()) {
+        M->flt_done.assign(nb, nullptr); M->flt_copied.assign(nb, nullptr);
+        for (int k = 0; k < nb; ++k) {
+            M_HIP(hipSetDevice(M->dev[k]));
+            M_HIP(hipEventCreateWithFlags(&M->flt_done[k], hipEventDisableTiming));
+            M_HIP(hipEventCreateWithFlags(&M->flt_copied[k], hipEventDisableTiming));
+        }
+    }
+    M->flt_out_s.assign(nb, nullptr); M->flt_out_n.assign(nb, nullptr); M->flt_in_s.assign(nb, nullptr); M->flt_in_n.assign(nb, nullptr);
+    for (int k = 0; k < nb; ++k) {
+        const Band &b = M->band[k];
+        const bool one = M->nb == 1;           // a ring of one band: nothing ever leaves it
+        M_RC(beom_band_floats_set(M->eng[k], n, capacity, b.own0, b.nown(), b.gs, !one && M->has_s(k), !one && M->has_n(k), M->P.mm, M->xper,
+                                  M->ring ? 1 : 0, errm, errm_len));
+        if (n > 0 && beom_band_floats_boxes(M->eng[k], &M->flt_out_s[k], &M->flt_out_n[k], &M->flt_in_s[k], &M->flt_in_n[k], &M->flt_box_bytes)) {
+            m_err(errm, errm_len, "beom_band_floats_boxes failed on band %d", b.index); return -3;
+        }
+    }
+    M->nflt = (long long)n; M->flt_cap = n > 0 ? capacity : 0;
+    return 0;
+}
+
+int beom_multi_upload_floats(beom_multi_handle M, const double *x, const double *y, const int32_t *layer, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->nflt < 1) { m_err(errm, errm_len, "beom_multi_upload_floats: the handle carries no float (beom_multi_set_floats)"); return -3; }
+    if (!x || !y || !layer) { m_err(errm, errm_len, "beom_multi_upload_floats: null array"); return -1; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (multi_whole(M)) {
+        M_RC(beom_upload_floats(M->eng[0], x, y, layer, errm, errm_len));
+        M->flt_ready = true;
+        return 0;
+    }
+    const unsigned long long none = ~0ull, n = (unsigned long long)M->nflt;
+    unsigned long long bad_layer = none, nobody = none, first_dry = none;
+    for (unsigned long long t = 0; t < n && bad_layer == none; ++t)
+        if (layer[t] < 1 || layer[t] > M->P.nlay) bad_layer = t;
+    for (unsigned long long t = 0; t < n && nobody == none; ++t) {
+        bool owned = false;
+        for (int k = 0; k < M->n && !owned; ++k) owned = band_owns(M, M->band[k], y[t]);
+        if (!owned) nobody = t;
+    }
+    for (int k = 0; k < M->n; ++k) {            // every band checks the floats of its rows
+        unsigned long long fd = none;
+        M_RC(beom_band_floats_check(M->eng[k], x, y, &fd, errm, errm_len));
+        if (fd < first_dry) first_dry = fd;
+    }
+    const unsigned long long first = std::min(bad_layer, std::min(nobody, first_dry));
+    if (first != none) {
+        if (first == bad_layer)
+            m_err(errm, errm_len, "beom_multi_upload_floats: float %llu has layer %d, outside 1..%d (nothing uploaded)", first, (int)layer[first], M->P.nlay);
+        else if (first == nobody)
+            m_err(errm, errm_len, "beom_multi_upload_floats: float %llu at (%.17g, %.17g) lies in no band's rows (row %.0f of 1..%d; nothing uploaded)",
+                  first, x[first], y[first], std::floor(y[first]) + 1.0, M->ring ? M->P.mm : M->P.mm + 1);
+        else
+            m_err(errm, errm_len, "beom_multi_upload_floats: float %llu at (%.17g, %.17g) does not start in a wet cell: cell (%.0f, %.0f) of the "
+                  "%d x %d frame is dry, land or outside (nothing uploaded)", first, x[first], y[first], std::floor(x[first]) + 1.0,
+                  std::floor(y[first]) + 1.0, M->P.lm, M->P.mm);
+        return -3;
+    }
+    for (int k = 0; k < M->n; ++k) M_RC(beom_band_floats_commit(M->eng[k], layer, errm, errm_len));
+    M->flt_ready = true; M->flt_mode = 0;
+    return 0;
+}
+
+int beom_multi_download_floats(beom_multi_handle M, double *x, double *y, int32_t *layer, int32_t *rejected, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->nflt < 1) { m_err(errm, errm_len, "beom_multi_download_floats: the handle carries no float (beom_multi_set_floats)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (multi_whole(M)) return beom_download_floats(M->eng[0], x, y, layer, rejected, errm, errm_len);
+    if (!M->flt_ready) { m_err(errm, errm_len, "beom_multi_download_floats: the floats have no positions yet (beom_multi_upload_floats)"); return -3; }
+    const size_t n = (size_t)M->nflt;
+    std::vector<double> bx(n), by(n);
+    std::vector<int32_t> br(n);
+    std::vector<unsigned char> claims(n, 0);
+    unsigned long long reach = 0, dropped = 0;
+    for (int k = 0; k < M->n; ++k) {
+        unsigned long long st[3] = {0, 0, 0};
+        M_RC(beom_band_floats_download(M->eng[k], bx.data(), by.data(), k == 0 ? layer : nullptr, br.data(), st, errm, errm_len));
+        reach += st[0]; dropped += st[1];
+        for (size_t t = 0; t < n; ++t) {
+            if (!band_owns(M, M->band[k], by[t])) continue;      // a stale copy: it points outside this band
+            if (claims[t] < 255) ++claims[t];
+            if (x) x[t] = bx[t];
+            if (y) y[t] = by[t];
+            if (rejected) rejected[t] = br[t];
+        }
+    }
+    if (reach) {
+        m_err(errm, errm_len, "beom_multi_download_floats: %llu lookups fell on rows of the frame outside their band's window (cdt |v| >= 1: a float moved "
+              "more than a row per stage); the positions are not valid", reach);
+        return BEOM_ERR_FLOAT_REACH;
+    }
+    if (dropped) {
+        m_err(errm, errm_len, "beom_multi_download_floats: %llu hand-over records were dropped by a full outbox (capacity %d records per side and step); "
+              "the positions are not valid: set a larger capacity", dropped, M->flt_cap);
+        return BEOM_ERR_FLOAT_OVERFLOW;
+    }
+    for (size_t t = 0; t < n; ++t)
+        if (claims[t] != 1) {
+            m_err(errm, errm_len, "beom_multi_download_floats: float %zu is claimed by %d bands instead of one", t, (int)claims[t]);
+            return BEOM_ERR_FLOAT_CLAIM;
+        }
+    return 0;
+}
+
+// a float launch on every band's main stream (which has joined the exchange: the ghost rows are the neighbours' values), and
+// behind a stage 2 the hand-over: every band copies its neighbours' outboxes, then ingests them.  Stream events only: a copy
+// waits for the sender's float launch; the ingest, which also empties this band's own outboxes, for the neighbours' copies.
+static int multi_float_launch(beom_multi *M, int mode, char *errm, int errm_len) {
+    const int n = M->n;
+    for (int k = 0; k < n; ++k)
+        if (beom_band_floats_launch(M->eng[k], mode)) { m_err(errm, errm_len, "beom_band_floats_launch failed on band %d", M->band[k].index); return -3; }
+    if (!(mode & 2) || M->nb == 1) return 0;
+    for (int k = 0; k < n; ++k) {
+        M_HIP(hipSetDevice(M->dev[k]));
+        M_HIP(hipEventRecord(M->flt_done[k], M->main_s[k]));
+    }
+    for (int k = 0; k < n; ++k) {
+        M_HIP(hipSetDevice(M->dev[k]));
+        if (M->has_s(k)) {          // what the south neighbour sent north
+            const int q = M->local_of(M->south_of(k));
+            M_HIP(hipStreamWaitEvent(M->main_s[k], M->flt_done[q], 0));
+            M_HIP(hipMemcpyPeerAsync(M->flt_in_s[k], M->dev[k], M->flt_out_n[q], M->dev[q], M->flt_box_bytes, M->main_s[k]));
+        }
+        if (M->has_n(k)) {
+            const int q = M->local_of(M->north_of(k));
+            M_HIP(hipStreamWaitEvent(M->main_s[k], M->flt_done[q], 0));
+            M_HIP(hipMemcpyPeerAsync(M->flt_in_n[k], M->dev[k], M->flt_out_s[q], M->dev[q], M->flt_box_bytes, M->main_s[k]));
+        }
+        M_HIP(hipEventRecord(M->flt_copied[k], M->main_s[k]));
+    }
+    for (int k = 0; k < n; ++k) {
+        M_HIP(hipSetDevice(M->dev[k]));
+        for (int q : {M->south_of(k), M->north_of(k)}) M_HIP(hipStreamWaitEvent(M->main_s[k], M->flt_copied[M->local_of(q)], 0));
+        if (beom_band_floats_ingest(M->eng[k])) { m_err(errm, errm_len, "beom_band_floats_ingest failed on band %d", M->band[k].index); return -3; }
+    }
+    return 0;
+}
+
+// every band's main stream joins the exchange in flight
+static int multi_join_exchange(beom_multi *M, char *errm, int errm_len) {
+    for (int k = 0; k < M->n; ++k) {
+        if (!M->pending[k]) continue;
+        M_HIP(hipSetDevice(M->dev[k]));
+        M_HIP(hipStreamWaitEvent(M->main_s[k], M->landed[k], 0));
+    }
+    return 0;
+}
+
+int beom_multi_update_floats(beom_multi_handle M, int stage) {
+    if (!M) return -1;
+    if (M->failed) return -30;
+    if (M->nflt < 1 || !M->flt_ready || (stage != 1 && stage != 2)) return -3;
+    if (multi_whole(M)) return beom_update_floats(M->eng[0], stage);
+    char errm[8]; const int errm_len = 0;
+    M_RC(multi_join_exchange(M, errm, errm_len));
+    return multi_float_launch(M, stage, errm, errm_len);
+}
+
 // ---- moments (beom_set_moments) on the bands: every band accumulates over all its rows, ghosts included, and the global
 //      arrays take the owned rows; a ring's row mm+1 comes from the companion frame, which samples behind its own steps ----
 int beom_multi_set_moments(beom_multi_handle M, int level, int stride, char *errm, int errm_len) {
@@ -1160,6 +1360,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
         M_HIP(hipStreamWaitEvent(M->main_s[k], M->landed[k], 0));
     }
     M_RC(multi_sample_due(M, errm, errm_len));          // the sample of the step before: its strips and ghost rows are in place
+    if (M->flt_mode) M_RC(multi_float_launch(M, M->flt_mode, errm, errm_len));      // the floats likewise, in front of anything that writes u, v
     // companion frame of a ring: rows 1..6 of band 0 and its south ghosts (= rows mm-3..mm) as they stand before this
     // step, then the companion's own step on its own stream
     if (M->mini) {
@@ -1288,6 +1489,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
         }
     }
     if (M->mom_level > 0 && t % M->mom_stride == 0) M->mom_due = t;
+    if (M->nflt > 0) M->flt_mode = 3;
     return 0;
 }
 
@@ -1299,21 +1501,24 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
     if (M->failed) { m_err(errm, errm_len, "beom_multi_step: an earlier step failed half way; destroy the handle"); return -30; }
     if (tstp_first < 1 || nsteps < 0 || n_3d < 1) { m_err(errm, errm_len, "beom_multi_step: bad arguments"); return -3; }
     if (M->nb == 1 && !M->ring) return beom_step(M->eng[0], tstp_first, nsteps, tres, dtd8, dt_r, rsta, n_3d, errm, errm_len);
+    if (M->nflt > 0 && !M->flt_ready) { m_err(errm, errm_len, "beom_multi_step: the handle's %lld floats have no positions yet (beom_multi_upload_floats)", M->nflt); return -3; }
+    M->flt_mode = (M->nflt > 0 && nsteps > 0) ? 1 : 0;          // stage 1 alone in front of the call's first step
     for (int t = tstp_first; t < tstp_first + nsteps; ++t) {
         const int rc = multi_one_step(M, t, tres, dtd8, dt_r, rsta, n_3d, errm, errm_len);
         if (rc) {       // streams and events are in an unknown order: refuse further steps, keep destroy safe
             M->failed = true;
             for (int k = 0; k < M->n; ++k) { (void)beom_set_stream(M->eng[k], (void *)M->main_s[k], 0); M->pending[k] = 0; }
+            M->flt_mode = 0;
             return rc;
         }
     }
-    if (M->mom_due) {            // the last step's sample: behind the same wait the next step would begin with
-        for (int k = 0; k < M->n; ++k) {
-            if (!M->pending[k]) continue;
-            M_HIP(hipSetDevice(M->dev[k]));
-            M_HIP(hipStreamWaitEvent(M->main_s[k], M->landed[k], 0));
-        }
+    if (M->mom_due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
+        M_RC(multi_join_exchange(M, errm, errm_len));
         M_RC(multi_sample_due(M, errm, errm_len));
+        if (M->flt_mode) {
+            M->flt_mode = 0;
+            M_RC(multi_float_launch(M, 2, errm, errm_len));
+        }
     }
     return 0;
 }

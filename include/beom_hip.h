@@ -321,7 +321,7 @@ int beom_update_tracers(beom_handle h, double gene, double ramp, double ctim);
  * beom_set_floats allocates n floats (n = 0 frees them; between steps only) and a track recorder of nrec records (0 = none):
  * behind stage 2 of every step with tstp % stride == 0, beom_step keeps (x, y, h) of every float on the device, h = hlay of
  * the home cell as the step leaves it.  It refuses (-6) handles that hold one band of rows (slab_mm != 0): a float leaves
- * its band.  beom_upload_floats sets positions and layers (1-based), zeroes `rejected` and empties the recorder; it refuses
+ * its band (bands carry floats through their multi handle: "Floats on bands" below).  beom_upload_floats sets positions and layers (1-based), zeroes `rejected` and empties the recorder; it refuses
  * (-3, naming the first offender, the handle's floats untouched) a layer outside 1..nlay and a position whose cell is not
  * wet.  beom_step then moves the floats: K steps of one call cost K + 1 float launches (stage 2 of a step and stage 1 of
  * the next read the same velocities); it refuses (-3), before launching anything, a call whose steps would write more
@@ -544,6 +544,63 @@ int beom_multi_set_moments(beom_multi_handle m, int level, int stride, char *err
 int beom_multi_reset_moments(beom_multi_handle m, char *errm, int errm_len);
 int beom_multi_download_moments(beom_multi_handle m, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
                                 int *tstp_last, char *errm, int errm_len);
+
+/* ---- Floats on bands (see beom_set_floats): Lagrangian floats on a frame cut into bands, every handle of
+ * beom_multi_create[_ex] (all bands in one process, any transport): chains with and without land, rings, a ring of one band.
+ * The positions are bit for bit a single handle's.
+ *   Replicated slots: every band holds the arrays of ALL n floats — x, y in GLOBAL grid units, layer, rejected, k1x, k1y,
+ *   xs, ys; slot t is float t on every band.  Owner test: in a float launch a band's thread t acts only if the home row
+ *   floor(y[t]) + 1 is one of the band's owned rows; every other lane reads y[t] and leaves.  a, b, the wraps and every sum
+ *   are formed from the global x, y as on a single handle; only the integer row of a lookup is translated into the window
+ *   (modulo mm on a ring; a row the window holds twice is taken where it is owned).  No row offset is ever subtracted from y.
+ *   Hand-over: K steps still cost K + 1 launches per band.  The launch behind step n finishes stage 2 for the band's floats
+ *   and runs stage 1 of step n + 1 on the new position even when that lies outside the band's rows: with cdt |u|, cdt |v| < 1
+ *   every lookup stays within 2 rows of the owned rows, and the 4 ghost rows hold the neighbour's owned values bit for bit.
+ *   For such a float the band appends one RECORD to its south or north OUTBOX (atomicAdd on a count in front of the records):
+ *     64 bytes = 8 words of 8 bytes: id, x, y, k1x, k1y, xs, ys (FP64 bits), rejected (int32 in the low half);
+ *     an outbox = the count at byte 0, record r at byte 64 (r + 1), `capacity` records.
+ *   The neighbour copies the outbox (hipMemcpyPeerAsync, count and capacity records) into an inbox and one k_floats_ingest
+ *   launch (capacity threads per inbox; thread i < count writes record i into slot id) takes them in; the order of records is
+ *   not deterministic, the result is (slot = id, no float depends on another).  Bands are coupled by stream events only: a
+ *   copy waits for the sender's float launch; the ingest, which also empties the band's own outboxes, waits for the
+ *   neighbours' copies of them.  The launch of step n sits on each band's main stream where it has joined the exchange of
+ *   step n (in front of everything of step n + 1 that writes u, v; once more, as stage 2 alone, behind the last step of a
+ *   beom_multi_step call; stage 1 alone in front of the first).  A handle without floats launches what it launched before.
+ *   Two conditions are COUNTED on the device and refuse beom_multi_download_floats:
+ *     BEOM_ERR_FLOAT_REACH     "out of reach": a lookup's row lies in the frame but outside the band's window (cdt |v| >= 1).
+ *                              The lane reads nothing outside the window: the cell counts as 0.
+ *     BEOM_ERR_FLOAT_OVERFLOW  an outbox was full and a record was dropped (more than `capacity` floats left a band
+ *                              through one side in one step).
+ *   and BEOM_ERR_FLOAT_CLAIM if a float is claimed (owner test on each band's own y) by other than exactly one band; stale
+ *   copies point outside their band, so exactly one band claims.
+ * beom_multi_set_floats: n floats (0 frees them), capacity records per outbox (0 = the default max(4096, n / 8)).  Refused
+ * with -6: handles that hold one band's window (beom_multi_create_local*): a float would have to travel between processes.
+ * There is no track recorder on bands.  One band that is the whole frame forwards to beom_set_floats etc.
+ * beom_multi_upload_floats: all or nothing as beom_upload_floats; every band checks the floats of its rows; the error (-3)
+ * names the smallest offending index over all bands: a layer outside 1..nlay, a dry start, or a float in no band's rows.
+ * beom_multi_download_floats takes every slot from its claimant.  beom_multi_update_floats: the per-sweep entry (stage 1 | 2
+ * on the state as it stands; the hand-over behind stage 2).  beom_info on a band's handle: "floats", "float_launches",
+ * "float_handovers" (records the band has ingested, as of the latest download).
+ * The beom_band_floats_* calls are the band-side pieces beom_multi_* is built from (a band = a dense slab handle): allocate
+ * for the rows own0..own0+nown-1 behind ghost_s ghost rows; check candidates / commit them; one float launch (mode 1, 2 or
+ * 3 = 2 then 1) or one ingest on the handle's stream; the four boxes' device addresses; the band's copy and its counts
+ * (stats3 = out of reach, dropped, ingested). */
+#define BEOM_ERR_FLOAT_REACH    (-41)
+#define BEOM_ERR_FLOAT_OVERFLOW (-42)
+#define BEOM_ERR_FLOAT_CLAIM    (-43)
+int beom_multi_set_floats(beom_multi_handle m, int64_t n, int capacity, char *errm, int errm_len);
+int beom_multi_upload_floats(beom_multi_handle m, const double *x, const double *y, const int32_t *layer, char *errm, int errm_len);
+int beom_multi_download_floats(beom_multi_handle m, double *x, double *y, int32_t *layer, int32_t *rejected, char *errm, int errm_len);
+int beom_multi_update_floats(beom_multi_handle m, int stage);
+int beom_band_floats_set(beom_handle h, int64_t n, int capacity, int own0, int nown, int ghost_s, int has_south, int has_north,
+                         int frame_mm, int xper, int ring, char *errm, int errm_len);
+int beom_band_floats_check(beom_handle h, const double *x, const double *y, unsigned long long *first_dry, char *errm, int errm_len);
+int beom_band_floats_commit(beom_handle h, const int32_t *layer, char *errm, int errm_len);
+int beom_band_floats_launch(beom_handle h, int mode);
+int beom_band_floats_ingest(beom_handle h);
+int beom_band_floats_boxes(beom_handle h, void **out_s, void **out_n, void **in_s, void **in_n, size_t *bytes);
+int beom_band_floats_download(beom_handle h, double *x, double *y, int32_t *layer, int32_t *rejected, unsigned long long *stats3,
+                              char *errm, int errm_len);
 
 /* Conservation integrals (see beom_integrals).  Global-array handles: every band forms the row sums of its OWNED rows; a
  * ring's row mm+1 duplicates row 1 and is all +0, so the companion frame is not asked; combined in global row order. */

@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_floats.h", "beom_moments.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_floats.h", "beom_moments.h", "beom_dense_host.h",
                "beom_bands_host.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -217,6 +217,11 @@ def load(path: Optional[str] = None) -> C.CDLL:
         for name in ("beom_set_tracers", "beom_upload_tracers", "beom_download_tracers", "beom_update_tracers",
                      "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers"):
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_tracer_scheme"):   # (likewise: an older build has one tracer scheme)
+        lib.beom_set_tracer_scheme.argtypes = [H, ci, cp, ci]
+        lib.beom_multi_set_tracer_scheme.argtypes = [MH, ci, cp, ci]
+        lib.beom_set_tracer_scheme.restype = ci
+        lib.beom_multi_set_tracer_scheme.restype = ci
     if hasattr(lib, "beom_set_floats"):          # (likewise: an older build has no floats)
         lib.beom_set_floats.argtypes = [H, C.c_int64, ci, ci, cp, ci]
         lib.beom_upload_floats.argtypes = [H, dpp, dpp, ipp, cp, ci]
@@ -300,6 +305,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_integrals", "beom_multi_integral_rows_local",
            "beom_set_tracers", "beom_upload_tracers", "beom_download_tracers", "beom_update_tracers",
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
+           "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
            "beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
            "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments") + MULTI_FLOAT_EXPORTS
@@ -343,6 +349,9 @@ def scale_integrals(raw: np.ndarray, prm: BeomParams) -> dict:
             "circulation": q[:, 3].copy(), "potential_J": 0.5 * rhon[0] * prm.grav * dl2 * float(raw[4 * nl])}
 
 
+TRACER_SCHEMES = {"upstream": 1, "limited": 2}
+
+
 class _Tracers:
     """Passive tracers of a handle (beom_set_tracers, include/beom_hip.h): shared by Engine and MultiEngine, whose C calls
     differ only by name.  Arrays: q, ctrg [ntrc, nlay, ndeg+1] (the layer CONTENT thickness x concentration, and the
@@ -358,6 +367,14 @@ class _Tracers:
         """Allocates n tracers (q, rq, ctrg = 0); n = 0 frees them.  Between steps only."""
         self._check(self._trc("set_tracers")(self.h, int(n), self._err, ERRLEN))
         self.ntrc = int(n)
+
+    def set_tracer_scheme(self, scheme):
+        """1 | "upstream" (the default) or 2 | "limited" (Koren's flux-limited third-order faces, beom_set_tracer_scheme).  Between
+        steps only; kept for the handle's life, whatever set_tracers does afterwards."""
+        scheme = TRACER_SCHEMES.get(scheme, scheme)
+        if isinstance(scheme, str):
+            raise BeomError("tracer scheme %r (1 | 'upstream', 2 | 'limited')" % (scheme,))
+        self._check(self._trc("set_tracer_scheme")(self.h, int(scheme), self._err, ERRLEN))
 
     def _trc_array(self, a, tail=()):
         if a is None:
@@ -657,7 +674,7 @@ class Engine(_Tracers, _Floats, _Moments):
         """beom_info: "stress_folded" (the last step formed its stress inside the momentum sweep: tt3d, tb3d, tu3d are
         then not kept current), "tile_rows", "biharm_tiled" (1: the handle's biharmonic viscosity, svis > 0, runs as the tiled
         sweep; 0 on the table path and with svis = 0), "uv_fused" (1: the last step's momentum ran as the fused u+v sweep),
-        "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did), "tracers", "floats",
+        "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did), "tracers", "tracer_scheme" (1 upstream, 2 limited), "floats",
         "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
         "moment_samples", "moment_launches"."""
         v = self.lib.beom_info(self.h, what.encode())

@@ -18,6 +18,7 @@
 #include "beom_kernels.h"
 #include "beom_integrals.h"
 #include "beom_tracers.h"
+#include "beom_tracers_lim.h"
 #include "beom_floats.h"
 #include "beom_moments.h"
 #include "beom_dense_host.h"
@@ -132,6 +133,7 @@ struct beom_engine {
     // passive tracers (beom_set_tracers; beom_tracers.h): the contents and the partner the sweep writes them to, the two
     // tendency levels (rotated by pointer), the relaxation concentration (allocated by its first upload)
     int ntrc = 0;
+    int trc_scheme = 1;                // 1 = upstream (k_tracers), 2 = flux-limited (k_tracers_lim); beom_set_tracer_scheme
     double *trc_q = nullptr, *trc_q_alt = nullptr, *trc_rq[2] = {nullptr, nullptr}, *trc_ctrg = nullptr;
     std::vector<void *> trc_allocs;
     // Lagrangian floats (beom_set_floats; beom_floats.h): positions, layers, rejected steps, stage 1's increment and
@@ -721,11 +723,24 @@ static void launch_h(beom_engine *E, double gene, double ramp, double ctim, bool
     else LAUNCH_CTX((k_update_h<CellGather, 0>), (k_update_h<CellDense, 0>), nz, E->d, gene, ramp, ctim, 0);
     if (rotate) rot2(E->d.rs);
 }
+// scheme 2 (beom_tracers_lim.h): the tiled kernel in the handle's tile geometry, or the table path
+template <int FORCE>
+static void launch_tracers_lim(beom_engine *E, const TrcView &tv, double gene, double ramp, double ctim) {
+    if (!E->dense) hipLaunchKernelGGL((k_tracers_lim<CellGather, FORCE>), CellGather::grid(E->d, E->d.nlay), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
+    else if (E->tile4) hipLaunchKernelGGL((k_tracers_lim<TrcTiled<1>, FORCE>), tracers_lim_grid<1>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
+    else hipLaunchKernelGGL((k_tracers_lim<TrcTiled<2>, FORCE>), tracers_lim_grid<2>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
+}
 // the tracer sweep of a step (beom_tracers.h): all tracers in one launch, in front of the step's update_h
 static void launch_tracers(beom_engine *E, double gene, double ramp, double ctim) {
     TrcView tv{E->ntrc, E->trc_ctrg ? 1 : 0, E->trc_q, E->trc_q_alt, E->trc_rq[0], E->trc_rq[1], E->trc_ctrg};
     const int nz = E->d.nlay;
-    if (E->d.has_nudg && E->d.has_tide) LAUNCH_CTX((k_tracers<CellGather, 2>), (k_tracers<CellDense, 2>), nz, E->d, tv, gene, ramp, ctim);
+    if (E->trc_scheme == 2) {
+        const int force = E->d.has_nudg ? (E->d.has_tide ? 2 : 1) : 0;
+        if (force == 2) launch_tracers_lim<2>(E, tv, gene, ramp, ctim);
+        else if (force == 1) launch_tracers_lim<1>(E, tv, gene, ramp, ctim);
+        else launch_tracers_lim<0>(E, tv, gene, ramp, ctim);
+    }
+    else if (E->d.has_nudg && E->d.has_tide) LAUNCH_CTX((k_tracers<CellGather, 2>), (k_tracers<CellDense, 2>), nz, E->d, tv, gene, ramp, ctim);
     else if (E->d.has_nudg) LAUNCH_CTX((k_tracers<CellGather, 1>), (k_tracers<CellDense, 1>), nz, E->d, tv, gene, ramp, ctim);
     else LAUNCH_CTX((k_tracers<CellGather, 0>), (k_tracers<CellDense, 0>), nz, E->d, tv, gene, ramp, ctim);
     swp(E->trc_q, E->trc_q_alt);
@@ -1436,6 +1451,14 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     return 0;
 }
 
+// the scheme of the tracer sweep; kept for the handle's life (beom_set_tracers leaves it).  The argument is looked at first
+int beom_set_tracer_scheme(beom_handle E, int scheme, char *errm, int errm_len) {
+    if (scheme != 1 && scheme != 2) { set_err(errm, errm_len, "beom_set_tracer_scheme: scheme %d (1 = upstream, 2 = limited)", scheme); return -3; }
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    E->trc_scheme = scheme;
+    return 0;
+}
+
 int beom_upload_tracers(beom_handle E, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len) {
     if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
     if (E->ntrc < 1) { set_err(errm, errm_len, "beom_upload_tracers: the handle carries no tracer (beom_set_tracers)"); return -3; }
@@ -1868,6 +1891,7 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "mont_history")) return E->last_mont_hist ? 1 : 0;
     if (!strcmp(what, "plain_sweeps")) return E->last_plain;
     if (!strcmp(what, "tracers")) return E->ntrc;
+    if (!strcmp(what, "tracer_scheme")) return E->trc_scheme;
     if (!strcmp(what, "floats")) return (int)std::min<long long>(E->nflt, 2000000000ll);
     if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
     if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far

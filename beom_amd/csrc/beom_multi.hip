@@ -863,6 +863,14 @@ int beom_multi_set_tracers(beom_multi_handle M, int ntrc, char *errm, int errm_l
     return 0;
 }
 
+int beom_multi_set_tracer_scheme(beom_multi_handle M, int scheme, char *errm, int errm_len) {
+    if (scheme != 1 && scheme != 2) { m_err(errm, errm_len, "beom_multi_set_tracer_scheme: scheme %d (1 = upstream, 2 = limited)", scheme); return -3; }
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracer_scheme: an earlier step failed half way; destroy the handle"); return -30; }
+    for (int k = 0; k < M->n; ++k) M_RC(beom_set_tracer_scheme(M->eng[k], scheme, errm, errm_len));
+    return 0;
+}
+
 int beom_multi_upload_tracers(beom_multi_handle M, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
     M_RC(tracers_refused(M, "beom_multi_upload_tracers", errm, errm_len));

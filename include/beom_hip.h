@@ -294,6 +294,34 @@ int beom_set_tracers(beom_handle h, int ntrc, char *errm, int errm_len);
 int beom_upload_tracers(beom_handle h, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len);
 int beom_download_tracers(beom_handle h, double *q, double *rq, char *errm, int errm_len);
 int beom_update_tracers(beom_handle h, double gene, double ramp, double ctim);
+/* The scheme of the tracer sweep, chosen per handle: 1 = the first-order upstream faces above (the default), 2 = "limited",
+ * a flux-limited third-order face.  Everything of beom_update_tracers stays except the face concentration cf.  For the face
+ * of cell x towards its back neighbour B (B = W(x) for Fu, B = S(x) for Fv), with F = the stored transport at x:
+ *   (U, D, UU) = F > 0 ? (B, x, back(B)) : (x, B, fwd(x))     back = W|S link, fwd = E|N link, each of the cell named
+ *   first      = wet(U) ? c(U) : c(D)                          (today's cf, no-gradient rule included)
+ *   if !(wet(U) && wet(D) && wet(UU))   cf = first
+ *   else  du = c(U) - c(UU);  dd = c(D) - c(U)
+ *         if (du*dd > 0.0)  m   = fmin(fmin(2.0*fabs(du), 2.0*fabs(dd)), fabs((du + 2.0*dd) * T3)),   T3 = 1.0/3.0 (FP64)
+ *                           lim = copysign(m, dd)
+ *         else              lim = +0.0
+ *         cf = c(U) + 0.5*lim
+ *   flux = F * cf
+ * All arithmetic is FP64, in this order, with no contraction.  This is Koren's limiter.  It is the kappa = 1/3 third-order
+ * upwind-biased face value where the field is smooth, clipped to stay between the upwind and downwind cell.
+ *  - Fu(E) and Fv(N) are the same expressions at cell E (N) with that cell's own links, as today.
+ *  - The links of the sentinel are all 0 and hlay(0) = 0.  So next to land, a dry cell or the frame's edge, the face falls
+ *    back to today's value.
+ *  - With every concentration equal, du = dd = 0, lim = +0.0 and cf = c(U) exactly.  Hence the identity with hlay.
+ * Limits (documented, not asserted by the engine):
+ *  - This is a method-of-lines limiter under the thickness equation's three-level time scheme.
+ *  - In the runs measured with the numpy restatement it preserved bounds for |u|dt/dl = 0.1 with |v|dt/dl = 0.05, and for
+ *    0.15 with 0.075.  That is the range measured; free-surface runs sit at about 0.01.
+ *  - It goes unstable at 0.25 + 0.125 (variance x3.8 over 40 steps).  Upstream itself goes unstable at 0.4 + 0.2.
+ * Returns -3 for any other scheme (the argument is looked at before the handle).  Between steps only.  The choice is kept on
+ * the handle for its life: beom_set_tracers does not reset it, and a handle without tracers just keeps it.  It may change
+ * between steps of a run; rq then holds the other scheme's tendencies, as after a restart from another scheme's files.
+ * beom_info(h, "tracer_scheme") returns it. */
+int beom_set_tracer_scheme(beom_handle h, int scheme, char *errm, int errm_len);
 
 /* ---- Lagrangian (isopycnal) floats carried by the layer velocities (no reference routine; DESIGN.md f-N7).  A float has a
  * position (x, y) in FP64 grid units and a fixed layer l.  Cell (i, j) spans [i-1, i] x [j-1, j]; u(p) sits on the cell's west
@@ -531,6 +559,9 @@ int beom_multi_download_local(beom_multi_handle h, beom_state *window, beom_stat
  * periodic in y (the ring's companion frame does not carry q yet) and handles that hold one band's window
  * (beom_multi_create_local*: their shared-memory segment and RCCL counts are sized at creation). */
 int beom_multi_set_tracers(beom_multi_handle m, int ntrc, char *errm, int errm_len);
+/* beom_set_tracer_scheme on every band.  Scheme 2 reaches two rows; the four ghost rows and the exchange of q suffice, so
+ * cut steps stay cut and no buffer changes.  (beom_multi_set_tracers refuses rings and rank-local handles as before.) */
+int beom_multi_set_tracer_scheme(beom_multi_handle m, int scheme, char *errm, int errm_len);
 int beom_multi_upload_tracers(beom_multi_handle m, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len);
 int beom_multi_download_tracers(beom_multi_handle m, double *q, double *rq, char *errm, int errm_len);
 

@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_floats.h", "beom_moments.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_dense_host.h",
                "beom_bands_host.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -259,6 +259,17 @@ def load(path: Optional[str] = None) -> C.CDLL:
         for name in ("beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
                      "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments"):
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_tracer_moments"):  # (likewise: an older build has no tracer moments)
+        llp = C.POINTER(C.c_longlong)
+        lib.beom_set_tracer_moments.argtypes = [H, ci, ci, cp, ci]
+        lib.beom_reset_tracer_moments.argtypes = [H]
+        lib.beom_sample_tracer_moments.argtypes = [H]
+        lib.beom_download_tracer_moments.argtypes = [H, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
+        lib.beom_multi_set_tracer_moments.argtypes = [MH, ci, ci, cp, ci]
+        lib.beom_multi_reset_tracer_moments.argtypes = [MH, cp, ci]
+        lib.beom_multi_download_tracer_moments.argtypes = [MH, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
+        for name in TRACER_MOMENT_EXPORTS:
+            getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
                  "beom_multi_stats", "beom_multi_create_ex", "beom_multi_describe", "beom_multi_engine",
@@ -284,6 +295,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
 MULTI_FLOAT_EXPORTS = ("beom_multi_set_floats", "beom_multi_upload_floats", "beom_multi_download_floats", "beom_multi_update_floats",
                        "beom_band_floats_set", "beom_band_floats_check", "beom_band_floats_commit", "beom_band_floats_launch",
                        "beom_band_floats_ingest", "beom_band_floats_boxes", "beom_band_floats_download")
+TRACER_MOMENT_EXPORTS = ("beom_set_tracer_moments", "beom_reset_tracer_moments", "beom_sample_tracer_moments",
+                         "beom_download_tracer_moments", "beom_multi_set_tracer_moments", "beom_multi_reset_tracer_moments",
+                         "beom_multi_download_tracer_moments")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
 
 EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "beom_info", "beom_download_diag", "beom_create", "beom_destroy", "beom_set_rigid_lid", "beom_download_pressure",
@@ -308,7 +322,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
            "beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
-           "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments") + MULTI_FLOAT_EXPORTS
+           "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments") + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -512,7 +526,56 @@ class _Moments:
         return out
 
 
-class Engine(_Tracers, _Floats, _Moments):
+TRACER_MOMENT_QUANTITIES = ("q", "c", "fu", "fv")     # content, concentration, upstream face fluxes through the W and S faces
+
+
+class _TracerMoments:
+    """Time means of the tracers' content, concentration and upstream face fluxes, and the concentration's second moment
+    (beom_set_tracer_moments, include/beom_hip.h): sums shifted by the first sample, kept on the device and fed behind every
+    step with tstp % stride == 0, with a level, stride and count of their own.  Shared by Engine and MultiEngine."""
+
+    tracer_moment_level = 0
+
+    def _tmom(self, name):
+        return getattr(self.lib, ("beom_multi_" if self._mom_multi else "beom_") + name)
+
+    def set_tracer_moments(self, level: int, stride: int = 1):
+        """level 1: ref, sum of q and c; 2: and of fu, fv; 3: and the second moment of c; 0 frees.  Between steps only, after
+        set_tracers."""
+        self._check(self._tmom("set_tracer_moments")(self.h, int(level), int(stride), self._err, ERRLEN))
+        self.tracer_moment_level = int(level)
+
+    def reset_tracer_moments(self):
+        """count = 0: the next sample is a first sample (no memory moves)."""
+        if self._mom_multi:
+            self._check(self.lib.beom_multi_reset_tracer_moments(self.h, self._err, ERRLEN))
+        else:
+            rc = self.lib.beom_reset_tracer_moments(self.h)
+            if rc != 0:
+                raise BeomError("beom_hip error %d: beom_reset_tracer_moments (tracer moments set?)" % rc)
+
+    def download_tracer_moments(self) -> dict:
+        """count, tstp_first, tstp_last; the raw ref, sum [quantities, ntrc, nlay, ndeg+1] (TRACER_MOMENT_QUANTITIES; two of them
+        at level 1) and, at level 3, sq [ntrc, nlay, ndeg+1]; the derived mean = ref + sum/count and, at level 3,
+        var_c = sq/count - (sum_c/count)**2."""
+        lv = self.info("tracer_moments")
+        nq = 4 if lv >= 2 else 2
+        shape = (self.ntrc, self.p.nlay, self.p.ndeg + 1)
+        ref, sm = np.zeros((nq,) + shape), np.zeros((nq,) + shape)
+        sq = np.zeros(shape) if lv >= 3 else None
+        count, t0, t1 = C.c_longlong(0), C.c_int(0), C.c_int(0)
+        self._check(self._tmom("download_tracer_moments")(self.h, _dp(ref), _dp(sm), _dp(sq), C.byref(count), C.byref(t0),
+                                                          C.byref(t1), self._err, ERRLEN))
+        out = {"count": int(count.value), "tstp_first": int(t0.value), "tstp_last": int(t1.value), "ref": ref, "sum": sm}
+        n = float(max(out["count"], 1))
+        out["mean"] = ref + sm / n
+        if sq is not None:
+            out["sq"] = sq
+            out["var_c"] = sq / n - (sm[1] / n) * (sm[1] / n)
+        return out
+
+
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
@@ -676,7 +739,8 @@ class Engine(_Tracers, _Floats, _Moments):
         sweep; 0 on the table path and with svis = 0), "uv_fused" (1: the last step's momentum ran as the fused u+v sweep),
         "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did), "tracers", "tracer_scheme" (1 upstream, 2 limited), "floats",
         "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
-        "moment_samples", "moment_launches"."""
+        "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
+        "tracer_moment_launches"."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))
@@ -737,11 +801,17 @@ class Engine(_Tracers, _Floats, _Moments):
         if rc != 0:
             raise BeomError("beom_hip error %d: beom_sample_moments (moments set?)" % rc)
 
+    def sample_tracer_moments(self):
+        """Per-sweep entry: one sample of the tracers and the state as they stand, whatever the stride."""
+        rc = self.lib.beom_sample_tracer_moments(self.h)
+        if rc != 0:
+            raise BeomError("beom_hip error %d: beom_sample_tracer_moments (tracer moments set?)" % rc)
+
     def rebuild_fluxes(self): self._check(self.lib.beom_rebuild_fluxes(self.h))
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""

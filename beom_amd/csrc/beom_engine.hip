@@ -21,6 +21,7 @@
 #include "beom_tracers_lim.h"
 #include "beom_floats.h"
 #include "beom_moments.h"
+#include "beom_tracer_moments.h"
 #include "beom_dense_host.h"
 
 namespace {
@@ -167,6 +168,13 @@ struct beom_engine {
     double *mom_ref[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *mom_sum[5] = {nullptr, nullptr, nullptr, nullptr, nullptr},
            *mom_sq[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<void *> mom_allocs;
+    // tracer moments (beom_set_tracer_moments; beom_tracer_moments.h): per quantity q, c, fu, fv the reference and the shifted
+    // sum, at level 3 the shifted second moment of c, in arrays of the tracers' shape; level, stride and count of their own
+    int tmom_level = 0, tmom_stride = 1;
+    long long tmom_count = 0, tmom_launches = 0;
+    int tmom_first = 0, tmom_last = 0;
+    double *tmom_ref[4] = {nullptr, nullptr, nullptr, nullptr}, *tmom_sum[4] = {nullptr, nullptr, nullptr, nullptr}, *tmom_sq = nullptr;
+    std::vector<void *> tmom_allocs;
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -484,6 +492,7 @@ int beom_destroy(beom_handle E) {
     for (void *p : E->trc_allocs) (void)hipFree(p);
     for (void *p : E->flt_allocs) (void)hipFree(p);
     for (void *p : E->mom_allocs) (void)hipFree(p);
+    for (void *p : E->tmom_allocs) (void)hipFree(p);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -798,6 +807,21 @@ static void launch_moments(beom_engine *E, int tstp) {
     ++E->mom_count;
     ++E->mom_launches;
 }
+// one sample of the tracer moments (beom_tracer_moments.h) of q, hlay, h_u, h_v as they stand, recorded under step tstp
+static void launch_tracer_moments(beom_engine *E, int tstp) {
+    double *const *r = E->tmom_ref, *const *s = E->tmom_sum;
+    const TrcMomentView m{E->ntrc, E->trc_q, r[0], r[1], r[2], r[3], s[0], s[1], s[2], s[3], E->tmom_sq};
+    const int nz = E->d.nlay;
+    const bool first = E->tmom_count == 0;
+#define TMOM_GO(lv) do { if (first) LAUNCH_CTX((k_tracer_moments<CellGather, lv, true>), (k_tracer_moments<CellDense, lv, true>), nz, E->d, m); \
+                         else LAUNCH_CTX((k_tracer_moments<CellGather, lv, false>), (k_tracer_moments<CellDense, lv, false>), nz, E->d, m); } while (0)
+    if (E->tmom_level == 1) TMOM_GO(1); else if (E->tmom_level == 2) TMOM_GO(2); else TMOM_GO(3);
+#undef TMOM_GO
+    if (first) E->tmom_first = tstp;
+    E->tmom_last = tstp;
+    ++E->tmom_count;
+    ++E->tmom_launches;
+}
 template <class CTX>
 static bool launch_mont_all(beom_engine *E) {
     const dim3 g = CTX::grid(E->d, 1), b(BEOM_BLOCK);
@@ -1109,6 +1133,7 @@ static void one_step(beom_engine *E, int tstp, const StepScalars &s, int flt = -
     if (flt >= 0) launch_floats_after(E, tstp, !(flt & 2));
     E->last_tstp = tstp;
     if (E->mom_level > 0 && !E->mom_by_caller && tstp % E->mom_stride == 0) launch_moments(E, tstp);
+    if (E->tmom_level > 0 && !E->mom_by_caller && tstp % E->tmom_stride == 0) launch_tracer_moments(E, tstp);
 }
 
 // rows [jlo, jlo+nrows) of hlay,u,v,h_u,h_v  ->  dbuf (device memory, 5*nlay*nrows*(lm+1) doubles); the *2 forms move a second
@@ -1417,6 +1442,7 @@ int beom_integrals(beom_handle E, double *out, char *errm, int errm_len) {
 }
 
 // ---- passive tracers (beom_tracers.h) -----------------------------------------------------------------------------------
+static void free_tracer_moments(beom_engine *E);
 static void free_tracers(beom_engine *E) {
     for (void *p : E->trc_allocs) (void)hipFree(p);
     E->trc_allocs.clear();
@@ -1441,6 +1467,7 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
+    if (ntrc != E->ntrc) free_tracer_moments(E);      // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
@@ -1826,6 +1853,89 @@ int beom_download_moments(beom_handle E, double *ref, double *sum, double *sq, l
     return 0;
 }
 
+// ---- tracer moments (beom_tracer_moments.h) ----------------------------------------------------------------------------------
+static void free_tracer_moments(beom_engine *E) {
+    for (void *p : E->tmom_allocs) (void)hipFree(p);
+    E->tmom_allocs.clear();
+    E->tmom_level = 0; E->tmom_stride = 1; E->tmom_count = 0; E->tmom_first = E->tmom_last = 0;
+    for (int k = 0; k < 4; ++k) E->tmom_ref[k] = E->tmom_sum[k] = nullptr;
+    E->tmom_sq = nullptr;
+}
+// a zeroed array of the tracers' shape [ntrc][nlay][n1], cell 1 aligned as dev_alloc's
+static int alloc_tracer_moment_array(beom_engine *E, double **p, char *errm, int errm_len) {
+    void *q = nullptr;
+    const size_t n = (size_t)E->ntrc * E->d.nlay * (size_t)E->d.n1 + 16;
+    HIP_TRY(hipMalloc(&q, n * sizeof(double)));
+    E->tmom_allocs.push_back(q);
+    HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(double), E->stream));
+    *p = (double *)q + 15;
+    return 0;
+}
+
+int beom_set_tracer_moments(beom_handle E, int level, int stride, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (level < 0 || level > 3 || stride < 1) { set_err(errm, errm_len, "beom_set_tracer_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
+    if (level > 0 && E->ntrc < 1) { set_err(errm, errm_len, "beom_set_tracer_moments: the handle carries no tracer (beom_set_tracers comes first)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    free_tracer_moments(E);
+    if (level == 0) return 0;
+    int rc = 0;
+    const int nq = level >= 2 ? 4 : 2;
+    for (int k = 0; k < nq && !rc; ++k) {
+        rc = alloc_tracer_moment_array(E, &E->tmom_ref[k], errm, errm_len);
+        if (!rc) rc = alloc_tracer_moment_array(E, &E->tmom_sum[k], errm, errm_len);
+    }
+    if (!rc && level >= 3) rc = alloc_tracer_moment_array(E, &E->tmom_sq, errm, errm_len);
+    if (rc) { free_tracer_moments(E); return rc; }
+    E->tmom_level = level; E->tmom_stride = stride;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int beom_reset_tracer_moments(beom_handle E) {
+    if (!E) return -1;
+    if (E->tmom_level < 1) return -3;
+    E->tmom_count = 0; E->tmom_first = E->tmom_last = 0;
+    return 0;
+}
+
+int beom_sample_tracer_moments(beom_handle E) {
+    if (!E) return -1;
+    if (E->tmom_level < 1 || E->ntrc < 1) return -3;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    launch_tracer_moments(E, E->last_tstp);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int beom_download_tracer_moments(beom_handle E, double *ref, double *sum, double *sq, long long *count, int *tstp_first, int *tstp_last,
+                                 char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->tmom_level < 1) { set_err(errm, errm_len, "beom_download_tracer_moments: the handle keeps no tracer moments (beom_set_tracer_moments)"); return -3; }
+    if (sq && E->tmom_level < 3) { set_err(errm, errm_len, "beom_download_tracer_moments: the second moment is kept at level 3, this handle has level %d", E->tmom_level); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t outer = (size_t)E->ntrc * (size_t)E->d.nlay, slab = ((size_t)E->d.ndeg + 1) * outer;
+    const int nq = E->tmom_level >= 2 ? 4 : 2;
+    if (count) *count = E->tmom_count;
+    if (tstp_first) *tstp_first = E->tmom_first;
+    if (tstp_last) *tstp_last = E->tmom_last;
+    if (E->tmom_count == 0) {          // nothing sampled yet: the arrays hold whatever an earlier average left
+        if (ref) std::fill(ref, ref + nq * slab, 0.0);
+        if (sum) std::fill(sum, sum + nq * slab, 0.0);
+        if (sq) std::fill(sq, sq + slab, 0.0);
+        return 0;
+    }
+    int rc;
+    for (int k = 0; k < nq; ++k) {
+        if (ref && (rc = copy_out(E, ref + k * slab, E->tmom_ref[k], outer, errm, errm_len))) return rc;
+        if (sum && (rc = copy_out(E, sum + k * slab, E->tmom_sum[k], outer, errm, errm_len))) return rc;
+    }
+    if (sq && (rc = copy_out(E, sq, E->tmom_sq, outer, errm, errm_len))) return rc;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)
 // of nudged open-boundary segments, Fortran storage.  Activates no_gradient_obc after the
 // momentum sweeps of every step when flag_nudging and mcbc < 0.5 (:2201-2204, 2285-2288).
@@ -1896,6 +2006,9 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
     if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far
     if (!strcmp(what, "float_handovers")) return (int)std::min<long long>(E->flt_handovers, 2000000000ll);   // (bands; as of the latest download)
+    if (!strcmp(what, "tracer_moments")) return E->tmom_level;
+    if (!strcmp(what, "tracer_moment_samples")) return (int)std::min<long long>(E->tmom_count, 2000000000ll);
+    if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom_launches, 2000000000ll);     // all calls so far
     if (!strcmp(what, "moments")) return E->mom_level;
     if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom_count, 2000000000ll);
     if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom_launches, 2000000000ll);     // all calls so far

@@ -280,6 +280,7 @@ struct beom_multi {
     // moments kept by every band (beom_multi_set_moments): the bands sample on request ("moments_by_caller"), the step whose
     // sample is still owed (0 = none) is taken where the main streams next join the exchange
     int mom_level = 0, mom_stride = 1, mom_due = 0;
+    int tmom_level = 0, tmom_stride = 1, tmom_due = 0;      // the tracer moments likewise (beom_multi_set_tracer_moments)
     // Lagrangian floats on the bands (beom_multi_set_floats): every band holds all nflt slots; flt_mode is the float launch
     // owed where the main streams next join the exchange (0 none, 1 stage 1, 3 stage 2 + stage 1 of the next step)
     long long nflt = 0;
@@ -847,6 +848,7 @@ int beom_multi_set_tracers(beom_multi_handle M, int ntrc, char *errm, int errm_l
     M_RC(tracers_refused(M, "beom_multi_set_tracers", errm, errm_len));
     M_RC(beom_multi_sync(M, errm, errm_len));
     for (int k = 0; k < M->n; ++k) M_RC(beom_set_tracers(M->eng[k], ntrc, errm, errm_len));
+    if (ntrc != M->ntrc) { M->tmom_level = 0; M->tmom_stride = 1; M->tmom_due = 0; }      // (the bands freed their tracer moments)
     M->ntrc = ntrc;
     if (M->nb == 1) return 0;
     // the exchange buffers for 5 + ntrc fields (nothing is in flight after the sync)
@@ -1147,6 +1149,63 @@ int beom_multi_download_moments(beom_multi_handle M, double *ref, double *sum, d
     return 0;
 }
 
+// ---- tracer moments (beom_set_tracer_moments) on the bands: every band samples over its whole window, behind the wait for
+//      the landed ghost rows (the S row of a band's first owned row then holds the neighbour's owned values), and the global
+//      arrays take the owned rows.  Rings and handles that hold one band's window carry no tracers, hence none of this. ----
+static int tracer_moments_refused(beom_multi *M, const char *who, char *errm, int errm_len) {
+    if (M->local_mode) { m_err(errm, errm_len, "%s: a handle that holds one band's window carries no tracers (its exchange is sized at creation), so there is nothing to average", who); return -6; }
+    if (M->ring) { m_err(errm, errm_len, "%s: bands of a frame periodic in y carry no tracers (the ring's companion frame has no q), so there is nothing to average; use a single handle", who); return -6; }
+    return 0;
+}
+
+int beom_multi_set_tracer_moments(beom_multi_handle M, int level, int stride, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: an earlier step failed half way; destroy the handle"); return -30; }
+    if (level < 0 || level > 3 || stride < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
+    M_RC(tracer_moments_refused(M, "beom_multi_set_tracer_moments", errm, errm_len));
+    if (level > 0 && M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: the handle carries no tracer (beom_multi_set_tracers comes first)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    for (int k = 0; k < M->n; ++k) {
+        M_RC(beom_set_tracer_moments(M->eng[k], level, stride, errm, errm_len));
+        if (beom_set_option(M->eng[k], "moments_by_caller", M->nb == 1 ? 0 : 1)) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: option refused"); return -3; }
+    }
+    M->tmom_level = level; M->tmom_stride = stride; M->tmom_due = 0;
+    return 0;
+}
+
+int beom_multi_reset_tracer_moments(beom_multi_handle M, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    M_RC(tracer_moments_refused(M, "beom_multi_reset_tracer_moments", errm, errm_len));
+    if (M->tmom_level < 1) { m_err(errm, errm_len, "beom_multi_reset_tracer_moments: the handle keeps no tracer moments (beom_multi_set_tracer_moments)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    for (int k = 0; k < M->n; ++k) M_RC(beom_reset_tracer_moments(M->eng[k]));
+    M->tmom_due = 0;
+    return 0;
+}
+
+int beom_multi_download_tracer_moments(beom_multi_handle M, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
+                                       int *tstp_last, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    M_RC(tracer_moments_refused(M, "beom_multi_download_tracer_moments", errm, errm_len));
+    if (M->tmom_level < 1) { m_err(errm, errm_len, "beom_multi_download_tracer_moments: the handle keeps no tracer moments (beom_multi_set_tracer_moments)"); return -3; }
+    if (sq && M->tmom_level < 3) { m_err(errm, errm_len, "beom_multi_download_tracer_moments: the second moment is kept at level 3, this handle has level %d", M->tmom_level); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (M->nb == 1) return beom_download_tracer_moments(M->eng[0], ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
+    const size_t per = (size_t)M->ntrc * M->P.nlay, nq = M->tmom_level >= 2 ? 4 : 2;
+    double *dst[3] = {ref, sum, sq};
+    const size_t outer[3] = {nq * per, nq * per, per};
+    for (const Part &p : parts(M)) {
+        std::vector<double> a[3];
+        for (int f = 0; f < 3; ++f) if (dst[f]) a[f].assign(outer[f] * p.n1(), 0.0);
+        long long cnt = 0;
+        int t0 = 0, t1 = 0;
+        M_RC(beom_download_tracer_moments(p.eng, ptr(a[0]), ptr(a[1]), ptr(a[2]), &cnt, &t0, &t1, errm, errm_len));
+        if (p.k == 0) { if (count) *count = cnt; if (tstp_first) *tstp_first = t0; if (tstp_last) *tstp_last = t1; }
+        for (int f = 0; f < 3; ++f) copy_rows(dst[f], ptr(a[f]), outer[f], 1, p.out);
+    }
+    return 0;
+}
+
 // ---- output records of all bands (SURVEY §8f N2 for the multi-device handle): as beom_download_outputs /
 //      beom_download_diag with GLOBAL (ndeg, nlay) real*4 records; every band forms its rows on its device.
 int beom_multi_download_outputs(beom_multi_handle M, const float *h0r4, float *eta, float *u4, float *v4,
@@ -1349,10 +1408,12 @@ int beom_multi_profile_stop(beom_multi_handle M, double *ms, int *launches, char
 // separate u and v sweeps, option "overlap" = 0) run whole, the exchange after them.
 // the moments' sample a step left owing, on every band's main stream (which has joined the exchange of that step)
 static int multi_sample_due(beom_multi *M, char *errm, int errm_len) {
-    if (!M->mom_due) return 0;
-    for (int k = 0; k < M->n; ++k)
+    for (int k = 0; k < M->n && M->mom_due; ++k)
         if (beom_sample_moments(M->eng[k])) { m_err(errm, errm_len, "beom_sample_moments failed on band %d (step %d)", M->band[k].index, M->mom_due); return -3; }
     M->mom_due = 0;
+    for (int k = 0; k < M->n && M->tmom_due; ++k)
+        if (beom_sample_tracer_moments(M->eng[k])) { m_err(errm, errm_len, "beom_sample_tracer_moments failed on band %d (step %d)", M->band[k].index, M->tmom_due); return -3; }
+    M->tmom_due = 0;
     return 0;
 }
 
@@ -1497,6 +1558,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
         }
     }
     if (M->mom_level > 0 && t % M->mom_stride == 0) M->mom_due = t;
+    if (M->tmom_level > 0 && t % M->tmom_stride == 0) M->tmom_due = t;
     if (M->nflt > 0) M->flt_mode = 3;
     return 0;
 }
@@ -1520,7 +1582,7 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
             return rc;
         }
     }
-    if (M->mom_due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
+    if (M->mom_due || M->tmom_due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
         M_RC(multi_join_exchange(M, errm, errm_len));
         M_RC(multi_sample_due(M, errm, errm_len));
         if (M->flt_mode) {

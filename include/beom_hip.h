@@ -397,6 +397,43 @@ int beom_sample_moments(beom_handle h);
 int beom_download_moments(beom_handle h, double *ref, double *sum, double *sq, long long *count, int *tstp_first, int *tstp_last,
                           char *errm, int errm_len);
 
+/* ---- Tracer moments: time means of a tracer's content, concentration and face fluxes and the variance of its concentration,
+ * accumulated on the device (no reference routine; DESIGN.md f-N9).  With t the tracer, l the layer, p a real cell and
+ * W, S = neig(5|7, p), c(x) is trc_conc of beom_tracers.h, c(x) = hlay(x,l) > 0 ? q(x,l,t)/hlay(x,l) : +0.0, and four
+ * quantities k = 0..3 are sampled:
+ *   x_q  = q(p,l,t)                 the content
+ *   x_c  = c(p)                     the concentration
+ *   x_fu = h_u(p,l) * cf            cf exactly from trc_face (upstream, no-gradient rule) between W and p:
+ *                                   (a, b) = h_u(p,l) > 0 ? (W, p) : (p, W),  cf = hlay(a,l) > 0 ? c(a) : c(b)
+ *   x_fv = h_v(p,l) * cf            likewise between S and p with h_v
+ * They feed the moments' own shifted sums (see beom_set_moments), all FP64, no contraction, in this order:
+ *   first sample after beom_set_tracer_moments / beom_reset_tracer_moments:  ref_k = x_k;  S_k = +0.0;  Q = +0.0;  count = 1
+ *   every later sample:  d_k = x_k - ref_k;  S_k = S_k + d_k;  Q = Q + d_c*d_c  (the product rounded, then added);  count += 1
+ * Derived by the caller: mean = ref + S/count; var_c = Q/count - (S_c/count)*(S_c/count).
+ *   level 1: ref, S of q and c        level 2: level 1 plus ref, S of fu, fv        level 3: level 2 plus Q of (c, c)
+ * (4 / 8 / 9 more arrays of the tracers' size; 3 + 15 ntrc words of traffic per cell-layer and level-3 sample, 3 + 10 ntrc for
+ * a first sample.)  A SAMPLE is taken at the very end of step tstp of beom_step when tstp % stride == 0, where the field
+ * moments' sample sits.  The q, hlay, h_u, h_v standing there are exactly what the next step's tracer sweep reads, so under
+ * scheme 1 the sampled x_fu, x_fv are bit for bit the face fluxes Fu(p), Fv(p) that sweep applies: the mean content budget
+ * closes against the mean of the model's own fluxes.  Under scheme 2 (beom_set_tracer_scheme) they are STILL the upstream
+ * faces, not the limited ones the sweep applies.  Slots that are no real cell are not part of the contract; a download
+ * returns +0.0 at index 0.
+ * Level, stride and count are the tracer moments' own, independent of beom_set_moments.  beom_set_tracer_moments: level = 0
+ * frees, stride >= 1; allocates, count = 0; between steps only; -3 for a level outside 0..3 or stride < 1, and -3 for a handle
+ * without tracers.  beom_set_tracers with another count frees them; beom_upload_state and beom_upload_tracers do NOT reset
+ * them: a restart continues the average.  beom_reset_tracer_moments sets count = 0 and moves no memory.
+ * beom_sample_tracer_moments is the per-sweep entry: one sample of the state as it stands, whatever the stride, recorded
+ * under the step number of the handle's last step.  beom_download_tracer_moments: any array pointer may be NULL; layout
+ * ref[ipnt + (ndeg+1)*((ilay-1) + nlay*(t + ntrc*k))] (sum alike; sq without k), level 1 fills k = 0..1 only; -3 if sq is
+ * asked for below level 3 or the handle keeps no tracer moments; with count = 0 it returns zeros and no error.  beom_info:
+ * "tracer_moments" (the level), "tracer_moment_samples", "tracer_moment_launches".  The option "moments_by_caller" governs
+ * these samples as it does the field moments'. */
+int beom_set_tracer_moments(beom_handle h, int level, int stride, char *errm, int errm_len);
+int beom_reset_tracer_moments(beom_handle h);
+int beom_sample_tracer_moments(beom_handle h);
+int beom_download_tracer_moments(beom_handle h, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
+                                 int *tstp_last, char *errm, int errm_len);
+
 /* ---- Conservation integrals of the state as it stands between two steps (no reference routine: the reference's test
  * case 3 forms them from the output files, testcases/conservation.m:116-211).  All FP64, raw sums over the frame:
  *   out[(l-1)*4 + 0]  vol   sum of mk_n*h                                    layer volume / dl^2
@@ -575,6 +612,16 @@ int beom_multi_set_moments(beom_multi_handle m, int level, int stride, char *err
 int beom_multi_reset_moments(beom_multi_handle m, char *errm, int errm_len);
 int beom_multi_download_moments(beom_multi_handle m, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
                                 int *tstp_last, char *errm, int errm_len);
+
+/* Tracer moments on a frame cut into bands (see beom_set_tracer_moments): GLOBAL arrays assembled from every band's OWNED
+ * rows; the bits are a single handle's.  Every band samples over its whole window where the bands' field moments are sampled:
+ * behind the wait for the landed ghost rows, so the S row of a band's first owned row holds the neighbour's owned values.
+ * Refused with -6, as tracers themselves are: bands of a frame periodic in y (a ring) and handles that hold one band's
+ * window (beom_multi_create_local*). */
+int beom_multi_set_tracer_moments(beom_multi_handle m, int level, int stride, char *errm, int errm_len);
+int beom_multi_reset_tracer_moments(beom_multi_handle m, char *errm, int errm_len);
+int beom_multi_download_tracer_moments(beom_multi_handle m, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
+                                       int *tstp_last, char *errm, int errm_len);
 
 /* ---- Floats on bands (see beom_set_floats): Lagrangian floats on a frame cut into bands, every handle of
  * beom_multi_create[_ex] (all bands in one process, any transport): chains with and without land, rings, a ring of one band.

@@ -23,7 +23,7 @@ CLASS = {"k_update_h": "update_h", "k_update_mont": "update_mont",  # first matc
          "k_update_uv<CellGather, true>": "update_u", "k_update_uv<CellGather, false>": "update_v",
          "k_mont_visc": "update_mont+update_viscosity", "k_uv_fused": "update_u+update_v",
          "k_integral_rows": "integral_rows", "k_integral_chunks": "integral_chunks", "k_tracers": "tracers", "k_floats": "floats",
-         "k_moments": "moments"}
+         "k_moments": "moments", "k_tracer_moments": "tracer_moments"}
 
 
 def classify(name):

@@ -247,28 +247,16 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.beom_band_floats_download.argtypes = [H, dpp, dpp, ipp, ipp, ullp, cp, ci]
         for name in MULTI_FLOAT_EXPORTS:
             getattr(lib, name).restype = ci
-    if hasattr(lib, "beom_set_moments"):         # (likewise: an older build has no moments)
-        llp = C.POINTER(C.c_longlong)
-        lib.beom_set_moments.argtypes = [H, ci, ci, cp, ci]
-        lib.beom_reset_moments.argtypes = [H]
-        lib.beom_sample_moments.argtypes = [H]
-        lib.beom_download_moments.argtypes = [H, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
-        lib.beom_multi_set_moments.argtypes = [MH, ci, ci, cp, ci]
-        lib.beom_multi_reset_moments.argtypes = [MH, cp, ci]
-        lib.beom_multi_download_moments.argtypes = [MH, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
-        for name in ("beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
-                     "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments"):
-            getattr(lib, name).restype = ci
-    if hasattr(lib, "beom_set_tracer_moments"):  # (likewise: an older build has no tracer moments)
-        llp = C.POINTER(C.c_longlong)
-        lib.beom_set_tracer_moments.argtypes = [H, ci, ci, cp, ci]
-        lib.beom_reset_tracer_moments.argtypes = [H]
-        lib.beom_sample_tracer_moments.argtypes = [H]
-        lib.beom_download_tracer_moments.argtypes = [H, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
-        lib.beom_multi_set_tracer_moments.argtypes = [MH, ci, ci, cp, ci]
-        lib.beom_multi_reset_tracer_moments.argtypes = [MH, cp, ci]
-        lib.beom_multi_download_tracer_moments.argtypes = [MH, dpp, dpp, dpp, llp, C.POINTER(ci), C.POINTER(ci), cp, ci]
-        for name in TRACER_MOMENT_EXPORTS:
+    for stem, names in (("moments", MOMENT_EXPORTS), ("tracer_moments", TRACER_MOMENT_EXPORTS)):
+        if not hasattr(lib, "beom_set_" + stem):     # (likewise: an older build has no moments, or no tracer moments)
+            continue
+        ip, llp = C.POINTER(ci), C.POINTER(C.c_longlong)
+        for pre, T, err in (("beom_", H, []), ("beom_multi_", MH, [cp, ci])):
+            getattr(lib, pre + "set_" + stem).argtypes = [T, ci, ci, cp, ci]
+            getattr(lib, pre + "reset_" + stem).argtypes = [T] + err
+            getattr(lib, pre + "download_" + stem).argtypes = [T, dpp, dpp, dpp, llp, ip, ip, cp, ci]
+        getattr(lib, "beom_sample_" + stem).argtypes = [H]
+        for name in names:
             getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
@@ -295,6 +283,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
 MULTI_FLOAT_EXPORTS = ("beom_multi_set_floats", "beom_multi_upload_floats", "beom_multi_download_floats", "beom_multi_update_floats",
                        "beom_band_floats_set", "beom_band_floats_check", "beom_band_floats_commit", "beom_band_floats_launch",
                        "beom_band_floats_ingest", "beom_band_floats_boxes", "beom_band_floats_download")
+MOMENT_EXPORTS = ("beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
+                  "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments")
 TRACER_MOMENT_EXPORTS = ("beom_set_tracer_moments", "beom_reset_tracer_moments", "beom_sample_tracer_moments",
                          "beom_download_tracer_moments", "beom_multi_set_tracer_moments", "beom_multi_reset_tracer_moments",
                          "beom_multi_download_tracer_moments")
@@ -321,8 +311,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           "beom_set_moments", "beom_reset_moments", "beom_sample_moments", "beom_download_moments",
-           "beom_multi_set_moments", "beom_multi_reset_moments", "beom_multi_download_moments") + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -479,100 +468,102 @@ class _Floats:
             raise BeomError("beom_update_floats(stage %d) = %d (floats set and uploaded? stage 1 or 2?)" % (stage, rc))
 
 
-MOMENT_FIELDS = ("hlay", "u", "v", "h_u", "h_v")
-MOMENT_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 3), (2, 4))      # the five second moments: (h,h) (u,u) (v,v) (u,h_u) (v,h_v)
-
-
-class _Moments:
-    """Time means and second moments of the layer fields (beom_set_moments, include/beom_hip.h): sums shifted by the first
-    sample, kept on the device and fed behind every step with tstp % stride == 0.  Shared by Engine and MultiEngine."""
+class _Accum:
+    """What _Moments and _TracerMoments share: set, reset and download of a device-side time accumulator through the exports
+    beom_[multi_]{set,reset,download}_<stem>, the level asked of the handle (info(<stem>))."""
 
     _mom_multi = False
-    moment_level = 0
 
-    def set_moments(self, level: int, stride: int = 1):
-        """level 1: ref, sum of hlay, u, v; 2: and of h_u, h_v; 3: and the five second moments; 0 frees.  Between steps only."""
-        fn = self.lib.beom_multi_set_moments if self._mom_multi else self.lib.beom_set_moments
-        self._check(fn(self.h, int(level), int(stride), self._err, ERRLEN))
-        self.moment_level = int(level)
+    def _accum_fn(self, op, stem):
+        return getattr(self.lib, "%s%s_%s" % ("beom_multi_" if self._mom_multi else "beom_", op, stem))
 
-    def reset_moments(self):
-        """count = 0: the next sample is a first sample (no memory moves)."""
+    def _accum_set(self, stem, level, stride):
+        self._check(self._accum_fn("set", stem)(self.h, int(level), int(stride), self._err, ERRLEN))
+
+    def _accum_plain(self, op, stem, what):
+        """reset or sample on a single handle: no message comes back, only a code."""
+        rc = getattr(self.lib, "beom_%s_%s" % (op, stem))(self.h)
+        if rc != 0:
+            raise BeomError("beom_hip error %d: beom_%s_%s (%s set?)" % (rc, op, stem, what))
+
+    def _accum_reset(self, stem, what):
         if self._mom_multi:
-            self._check(self.lib.beom_multi_reset_moments(self.h, self._err, ERRLEN))
+            self._check(self._accum_fn("reset", stem)(self.h, self._err, ERRLEN))
         else:
-            rc = self.lib.beom_reset_moments(self.h)
-            if rc != 0:
-                raise BeomError("beom_hip error %d: beom_reset_moments (moments set?)" % rc)
+            self._accum_plain("reset", stem, what)
 
-    def download_moments(self) -> dict:
-        """count, tstp_first, tstp_last; the raw ref, sum [fields, nlay, ndeg+1] and, at level 3, sq [5, nlay, ndeg+1]; the
-        derived mean = ref + sum/count and, at level 3, var = sq/count - (sum_a/count)*(sum_b/count) (var[0..2] the variances
-        of hlay, u, v; var[3..4] the covariances of (u, h_u), (v, h_v))."""
-        lv = self.moment_level
-        nf = 5 if lv >= 2 else 3
-        shape = (self.p.nlay, self.p.ndeg + 1)
-        ref, sm = np.zeros((nf,) + shape), np.zeros((nf,) + shape)
-        sq = np.zeros((5,) + shape) if lv >= 3 else None
+    def _accum_download(self, stem, lv, counts, nsq, shape, var_key, var):
+        """ref, sum [counts[lv >= 2], *shape], at level 3 sq [*nsq, *shape] (nsq a tuple) and out[var_key] = var(sq/n, sum/n)."""
+        nq = counts[lv >= 2]
+        ref, sm = np.zeros((nq,) + shape), np.zeros((nq,) + shape)
+        sq = np.zeros(nsq + shape) if lv >= 3 else None
         count, t0, t1 = C.c_longlong(0), C.c_int(0), C.c_int(0)
-        fn = self.lib.beom_multi_download_moments if self._mom_multi else self.lib.beom_download_moments
-        self._check(fn(self.h, _dp(ref), _dp(sm), _dp(sq), C.byref(count), C.byref(t0), C.byref(t1), self._err, ERRLEN))
+        self._check(self._accum_fn("download", stem)(self.h, _dp(ref), _dp(sm), _dp(sq), C.byref(count), C.byref(t0),
+                                                     C.byref(t1), self._err, ERRLEN))
         out = {"count": int(count.value), "tstp_first": int(t0.value), "tstp_last": int(t1.value), "ref": ref, "sum": sm}
         n = float(max(out["count"], 1))
         out["mean"] = ref + sm / n
         if sq is not None:
             out["sq"] = sq
-            out["var"] = np.stack([sq[m] / n - (sm[a] / n) * (sm[b] / n) for m, (a, b) in enumerate(MOMENT_PAIRS)])
+            out[var_key] = var(sq / n, sm / n)
         return out
+
+
+MOMENT_FIELDS = ("hlay", "u", "v", "h_u", "h_v")
+MOMENT_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 3), (2, 4))      # the five second moments: (h,h) (u,u) (v,v) (u,h_u) (v,h_v)
+
+
+class _Moments(_Accum):
+    """Time means and second moments of the layer fields (beom_set_moments, include/beom_hip.h): sums shifted by the first
+    sample, kept on the device and fed behind every step with tstp % stride == 0.  Shared by Engine and MultiEngine."""
+
+    moment_level = 0
+
+    def set_moments(self, level: int, stride: int = 1):
+        """level 1: ref, sum of hlay, u, v; 2: and of h_u, h_v; 3: and the five second moments; 0 frees.  Between steps only."""
+        self._accum_set("moments", level, stride)
+        self.moment_level = int(level)
+
+    def reset_moments(self):
+        """count = 0: the next sample is a first sample (no memory moves)."""
+        self._accum_reset("moments", "moments")
+
+    def download_moments(self) -> dict:
+        """count, tstp_first, tstp_last; the raw ref, sum [fields, nlay, ndeg+1] and, at level 3, sq [5, nlay, ndeg+1]; the
+        derived mean = ref + sum/count and, at level 3, var = sq/count - (sum_a/count)*(sum_b/count) (var[0..2] the variances
+        of hlay, u, v; var[3..4] the covariances of (u, h_u), (v, h_v))."""
+        self.moment_level = self.info("moments")
+        return self._accum_download("moments", self.moment_level, (3, 5), (5,), (self.p.nlay, self.p.ndeg + 1), "var",
+                                    lambda q, m: np.stack([q[k] - m[a] * m[b] for k, (a, b) in enumerate(MOMENT_PAIRS)]))
 
 
 TRACER_MOMENT_QUANTITIES = ("q", "c", "fu", "fv")     # content, concentration, upstream face fluxes through the W and S faces
 
 
-class _TracerMoments:
+class _TracerMoments(_Accum):
     """Time means of the tracers' content, concentration and upstream face fluxes, and the concentration's second moment
     (beom_set_tracer_moments, include/beom_hip.h): sums shifted by the first sample, kept on the device and fed behind every
     step with tstp % stride == 0, with a level, stride and count of their own.  Shared by Engine and MultiEngine."""
 
     tracer_moment_level = 0
 
-    def _tmom(self, name):
-        return getattr(self.lib, ("beom_multi_" if self._mom_multi else "beom_") + name)
-
     def set_tracer_moments(self, level: int, stride: int = 1):
         """level 1: ref, sum of q and c; 2: and of fu, fv; 3: and the second moment of c; 0 frees.  Between steps only, after
         set_tracers."""
-        self._check(self._tmom("set_tracer_moments")(self.h, int(level), int(stride), self._err, ERRLEN))
+        self._accum_set("tracer_moments", level, stride)
         self.tracer_moment_level = int(level)
 
     def reset_tracer_moments(self):
         """count = 0: the next sample is a first sample (no memory moves)."""
-        if self._mom_multi:
-            self._check(self.lib.beom_multi_reset_tracer_moments(self.h, self._err, ERRLEN))
-        else:
-            rc = self.lib.beom_reset_tracer_moments(self.h)
-            if rc != 0:
-                raise BeomError("beom_hip error %d: beom_reset_tracer_moments (tracer moments set?)" % rc)
+        self._accum_reset("tracer_moments", "tracer moments")
 
     def download_tracer_moments(self) -> dict:
         """count, tstp_first, tstp_last; the raw ref, sum [quantities, ntrc, nlay, ndeg+1] (TRACER_MOMENT_QUANTITIES; two of them
         at level 1) and, at level 3, sq [ntrc, nlay, ndeg+1]; the derived mean = ref + sum/count and, at level 3,
         var_c = sq/count - (sum_c/count)**2."""
-        lv = self.info("tracer_moments")
-        nq = 4 if lv >= 2 else 2
-        shape = (self.ntrc, self.p.nlay, self.p.ndeg + 1)
-        ref, sm = np.zeros((nq,) + shape), np.zeros((nq,) + shape)
-        sq = np.zeros(shape) if lv >= 3 else None
-        count, t0, t1 = C.c_longlong(0), C.c_int(0), C.c_int(0)
-        self._check(self._tmom("download_tracer_moments")(self.h, _dp(ref), _dp(sm), _dp(sq), C.byref(count), C.byref(t0),
-                                                          C.byref(t1), self._err, ERRLEN))
-        out = {"count": int(count.value), "tstp_first": int(t0.value), "tstp_last": int(t1.value), "ref": ref, "sum": sm}
-        n = float(max(out["count"], 1))
-        out["mean"] = ref + sm / n
-        if sq is not None:
-            out["sq"] = sq
-            out["var_c"] = sq / n - (sm[1] / n) * (sm[1] / n)
-        return out
+        self.tracer_moment_level = self.info("tracer_moments")
+        return self._accum_download("tracer_moments", self.tracer_moment_level, (2, 4), (), (self.ntrc, self.p.nlay, self.p.ndeg + 1),
+                                    "var_c", lambda q, m: q - m[1] * m[1])
 
 
 class Engine(_Tracers, _Floats, _Moments, _TracerMoments):
@@ -797,15 +788,11 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments):
     def update_v(self, ilay, gene, ramp, ctim): self._check(self.lib.beom_update_v(self.h, ilay, gene, ramp, ctim))
     def sample_moments(self):
         """Per-sweep entry: one sample of the state as it stands, whatever the stride."""
-        rc = self.lib.beom_sample_moments(self.h)
-        if rc != 0:
-            raise BeomError("beom_hip error %d: beom_sample_moments (moments set?)" % rc)
+        self._accum_plain("sample", "moments", "moments")
 
     def sample_tracer_moments(self):
         """Per-sweep entry: one sample of the tracers and the state as they stand, whatever the stride."""
-        rc = self.lib.beom_sample_tracer_moments(self.h)
-        if rc != 0:
-            raise BeomError("beom_hip error %d: beom_sample_tracer_moments (tracer moments set?)" % rc)
+        self._accum_plain("sample", "tracer_moments", "tracer moments")
 
     def rebuild_fluxes(self): self._check(self.lib.beom_rebuild_fluxes(self.h))
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))

@@ -67,6 +67,39 @@ struct StepTimer {        // optional HIP-event bracket around each kernel class
     void end() { if (!open) return; hipEvent_t b; (void)hipEventCreate(&b); (void)hipEventRecord(b, st); ev.push_back(b); open = false; }
 };
 
+// A time accumulator kept on the device: field moments and tracer moments share everything on the host but their kernels.
+// The constant part: how many quantities have a reference and a shifted sum at level 1 and at levels 2 and 3, how many
+// second moments level 3 adds, whether an array has the tracers' shape (else the state's), and the texts of the refusals.
+struct AccumKind {
+    int n1, n2, nsq;
+    bool per_tracer;
+    const char *bad_args, *no_tracer, *none, *no_sq;      // (no_tracer: null where no tracer is needed)
+};
+constexpr AccumKind kFieldMoments{3, 5, 5, false,
+    "beom_set_moments: level %d, stride %d (level 0..3, stride >= 1)", nullptr,
+    "beom_download_moments: the handle keeps no moments (beom_set_moments)",
+    "beom_download_moments: the second moments are kept at level 3, this handle has level %d"};
+constexpr AccumKind kTracerMoments{2, 4, 1, true,
+    "beom_set_tracer_moments: level %d, stride %d (level 0..3, stride >= 1)",
+    "beom_set_tracer_moments: the handle carries no tracer (beom_set_tracers comes first)",
+    "beom_download_tracer_moments: the handle keeps no tracer moments (beom_set_tracer_moments)",
+    "beom_download_tracer_moments: the second moment is kept at level 3, this handle has level %d"};
+struct Accum {
+    const AccumKind *kind;
+    int level = 0, stride = 1;
+    long long count = 0, launches = 0; // samples since the last reset | all launches so far
+    int first = 0, last = 0;           // the steps of the first and the latest sample
+    double *ref[5] = {}, *sum[5] = {}, *sq[5] = {};
+    std::vector<void *> allocs;
+};
+static bool accum_due(const Accum &A, int tstp) { return A.level > 0 && tstp % A.stride == 0; }
+static void accum_note_sample(Accum &A, int tstp) {      // the tail of a sample's launch
+    if (A.count == 0) A.first = tstp;
+    A.last = tstp;
+    ++A.count;
+    ++A.launches;
+}
+
 struct beom_engine {
     beom_params P;
     int device = 0;
@@ -160,21 +193,12 @@ struct beom_engine {
     long long flt_handovers = 0;       // beom_info "float_handovers": records ingested, as the latest download read it
     // moments (beom_set_moments; beom_moments.h): per field the reference, the shifted sum and, at level 3, the shifted
     // second moment, in arrays of the state's shape; the steps of the first and the latest sample
-    int mom_level = 0, mom_stride = 1;
+    Accum mom{&kFieldMoments};
     bool mom_by_caller = false;        // option "moments_by_caller": beom_step takes no sample by itself
-    long long mom_count = 0, mom_launches = 0;
-    int mom_first = 0, mom_last = 0;
     int last_tstp = 0;                 // the last step taken (beom_step, beom_step_phase)
-    double *mom_ref[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *mom_sum[5] = {nullptr, nullptr, nullptr, nullptr, nullptr},
-           *mom_sq[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<void *> mom_allocs;
     // tracer moments (beom_set_tracer_moments; beom_tracer_moments.h): per quantity q, c, fu, fv the reference and the shifted
     // sum, at level 3 the shifted second moment of c, in arrays of the tracers' shape; level, stride and count of their own
-    int tmom_level = 0, tmom_stride = 1;
-    long long tmom_count = 0, tmom_launches = 0;
-    int tmom_first = 0, tmom_last = 0;
-    double *tmom_ref[4] = {nullptr, nullptr, nullptr, nullptr}, *tmom_sum[4] = {nullptr, nullptr, nullptr, nullptr}, *tmom_sq = nullptr;
-    std::vector<void *> tmom_allocs;
+    Accum tmom{&kTracerMoments};
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -182,18 +206,36 @@ static int leave_mont_history(beom_engine *E);
 
 namespace {
 
-// Device arrays of doubles start 15 elements into their allocation so that cell index 1 is 128-byte
-// aligned (hipMalloc aligns to 256 B); see DevView::P.
+// A device array of n elements, zeroed unless told otherwise, owned by `owner` (free_list).
 template <class T>
-int dev_alloc(beom_engine *E, T **p, size_t n, char *errm, int errm_len, bool zero = true) {
+int alloc_plain(beom_engine *E, std::vector<void *> &owner, T **p, size_t n, char *errm, int errm_len, bool zero = true) {
     void *q = nullptr;
-    const size_t lead = sizeof(T) == 8 ? 15 : 0;
-    HIP_TRY(hipMalloc(&q, (n + lead + 1) * sizeof(T)));
-    E->allocs.push_back(q);
-    if (zero) HIP_TRY(hipMemsetAsync(q, 0, (n + lead + 1) * sizeof(T), E->stream));
-    *p = (T *)q + lead;
+    HIP_TRY(hipMalloc(&q, n * sizeof(T)));
+    owner.push_back(q);
+    if (zero) HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(T), E->stream));
+    *p = (T *)q;
     return 0;
 }
+// Device arrays of doubles start kLead elements into their allocation so that cell index 1 is 128-byte
+// aligned (hipMalloc aligns to 256 B); see DevView::P.  n + kLead + 1 elements are allocated.
+constexpr size_t kLead = 15;
+template <class T>
+int alloc_aligned(beom_engine *E, std::vector<void *> &owner, T **p, size_t n, char *errm, int errm_len, bool zero = true) {
+    const int rc = alloc_plain(E, owner, p, n + kLead + 1, errm, errm_len, zero);
+    if (!rc) *p += kLead;
+    return rc;
+}
+void free_list(std::vector<void *> &owner) {
+    for (void *p : owner) (void)hipFree(p);
+    owner.clear();
+}
+template <class T>
+int dev_alloc(beom_engine *E, T **p, size_t n, char *errm, int errm_len, bool zero = true) {
+    return sizeof(T) == 8 ? alloc_aligned(E, E->allocs, p, n, errm, errm_len, zero) : alloc_plain(E, E->allocs, p, n + 1, errm, errm_len, zero);
+}
+// elements of an array of the state's shape [nlay][n1] and of the tracers' shape [ntrc][nlay][n1]
+size_t state_cells(const beom_engine *E) { return (size_t)E->d.nlay * (size_t)E->d.n1; }
+size_t tracer_cells(const beom_engine *E) { return (size_t)E->ntrc * state_cells(E); }
 
 // one slice [0:ndeg][inner] (x K interleaved levels, level m) of a caller array <-> its device array
 template <class T, bool REMAP = false>
@@ -488,11 +530,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (void *p : E->allocs) (void)hipFree(p);
-    for (void *p : E->trc_allocs) (void)hipFree(p);
-    for (void *p : E->flt_allocs) (void)hipFree(p);
-    for (void *p : E->mom_allocs) (void)hipFree(p);
-    for (void *p : E->tmom_allocs) (void)hipFree(p);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -792,35 +830,29 @@ static void launch_floats_after(beom_engine *E, int tstp, bool then_stage1) {
 // one sample of the moments (beom_moments.h) of the fields as they stand, recorded under step tstp
 static void launch_moments(beom_engine *E, int tstp) {
     const DevView &d = E->d;
-    double *const *r = E->mom_ref, *const *s = E->mom_sum, *const *q = E->mom_sq;
+    double *const *r = E->mom.ref, *const *s = E->mom.sum, *const *q = E->mom.sq;
     const MomentView m{(long long)d.nlay * d.n1, d.hlay, d.u, d.v, d.h_u, d.h_v, r[0], r[1], r[2], r[3], r[4],
                        s[0], s[1], s[2], s[3], s[4], q[0], q[1], q[2], q[3], q[4]};
     const long long pairs = (m.n - 1) / 2;
     const dim3 g((unsigned)std::max<long long>(1, std::min<long long>((pairs + BEOM_BLOCK - 1) / BEOM_BLOCK, 2048))), b(BEOM_BLOCK);
-    const bool first = E->mom_count == 0;
+    const bool first = E->mom.count == 0;
 #define MOM_GO(lv) do { if (first) hipLaunchKernelGGL((k_moments<lv, true>), g, b, 0, E->stream, m); \
                         else hipLaunchKernelGGL((k_moments<lv, false>), g, b, 0, E->stream, m); } while (0)
-    if (E->mom_level == 1) MOM_GO(1); else if (E->mom_level == 2) MOM_GO(2); else MOM_GO(3);
+    if (E->mom.level == 1) MOM_GO(1); else if (E->mom.level == 2) MOM_GO(2); else MOM_GO(3);
 #undef MOM_GO
-    if (first) E->mom_first = tstp;
-    E->mom_last = tstp;
-    ++E->mom_count;
-    ++E->mom_launches;
+    accum_note_sample(E->mom, tstp);
 }
 // one sample of the tracer moments (beom_tracer_moments.h) of q, hlay, h_u, h_v as they stand, recorded under step tstp
 static void launch_tracer_moments(beom_engine *E, int tstp) {
-    double *const *r = E->tmom_ref, *const *s = E->tmom_sum;
-    const TrcMomentView m{E->ntrc, E->trc_q, r[0], r[1], r[2], r[3], s[0], s[1], s[2], s[3], E->tmom_sq};
+    double *const *r = E->tmom.ref, *const *s = E->tmom.sum;
+    const TrcMomentView m{E->ntrc, E->trc_q, r[0], r[1], r[2], r[3], s[0], s[1], s[2], s[3], E->tmom.sq[0]};
     const int nz = E->d.nlay;
-    const bool first = E->tmom_count == 0;
+    const bool first = E->tmom.count == 0;
 #define TMOM_GO(lv) do { if (first) LAUNCH_CTX((k_tracer_moments<CellGather, lv, true>), (k_tracer_moments<CellDense, lv, true>), nz, E->d, m); \
                          else LAUNCH_CTX((k_tracer_moments<CellGather, lv, false>), (k_tracer_moments<CellDense, lv, false>), nz, E->d, m); } while (0)
-    if (E->tmom_level == 1) TMOM_GO(1); else if (E->tmom_level == 2) TMOM_GO(2); else TMOM_GO(3);
+    if (E->tmom.level == 1) TMOM_GO(1); else if (E->tmom.level == 2) TMOM_GO(2); else TMOM_GO(3);
 #undef TMOM_GO
-    if (first) E->tmom_first = tstp;
-    E->tmom_last = tstp;
-    ++E->tmom_count;
-    ++E->tmom_launches;
+    accum_note_sample(E->tmom, tstp);
 }
 template <class CTX>
 static bool launch_mont_all(beom_engine *E) {
@@ -1132,8 +1164,8 @@ static void one_step(beom_engine *E, int tstp, const StepScalars &s, int flt = -
     E->d.stress_fold = 0;
     if (flt >= 0) launch_floats_after(E, tstp, !(flt & 2));
     E->last_tstp = tstp;
-    if (E->mom_level > 0 && !E->mom_by_caller && tstp % E->mom_stride == 0) launch_moments(E, tstp);
-    if (E->tmom_level > 0 && !E->mom_by_caller && tstp % E->tmom_stride == 0) launch_tracer_moments(E, tstp);
+    if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
+    if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
 }
 
 // rows [jlo, jlo+nrows) of hlay,u,v,h_u,h_v  ->  dbuf (device memory, 5*nlay*nrows*(lm+1) doubles); the *2 forms move a second
@@ -1442,24 +1474,12 @@ int beom_integrals(beom_handle E, double *out, char *errm, int errm_len) {
 }
 
 // ---- passive tracers (beom_tracers.h) -----------------------------------------------------------------------------------
-static void free_tracer_moments(beom_engine *E);
+static void accum_free(Accum &A);
 static void free_tracers(beom_engine *E) {
-    for (void *p : E->trc_allocs) (void)hipFree(p);
-    E->trc_allocs.clear();
+    free_list(E->trc_allocs);
     E->ntrc = 0;
     E->trc_q = E->trc_q_alt = E->trc_rq[0] = E->trc_rq[1] = E->trc_ctrg = nullptr;
 }
-// a zeroed array of the tracers' shape [ntrc][nlay][n1], cell 1 aligned as dev_alloc's
-static int alloc_tracer_array(beom_engine *E, double **p, char *errm, int errm_len) {
-    void *q = nullptr;
-    const size_t n = (size_t)E->ntrc * E->d.nlay * (size_t)E->d.n1 + 16;
-    HIP_TRY(hipMalloc(&q, n * sizeof(double)));
-    E->trc_allocs.push_back(q);
-    HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(double), E->stream));
-    *p = (double *)q + 15;
-    return 0;
-}
-
 int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
     if (ntrc < 0 || ntrc > BEOM_MAX_TRACERS) { set_err(errm, errm_len, "beom_set_tracers: %d tracers (0..%d)", ntrc, BEOM_MAX_TRACERS); return -3; }
@@ -1467,13 +1487,13 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    if (ntrc != E->ntrc) free_tracer_moments(E);      // (their arrays have the tracers' shape)
+    if (ntrc != E->ntrc) accum_free(E->tmom);         // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
     int rc = 0;
     for (double **a : {&E->trc_q, &E->trc_q_alt, &E->trc_rq[0], &E->trc_rq[1]})
-        if ((rc = alloc_tracer_array(E, a, errm, errm_len))) { free_tracers(E); return rc; }
+        if ((rc = alloc_aligned(E, E->trc_allocs, a, tracer_cells(E), errm, errm_len))) { free_tracers(E); return rc; }
     HIP_TRY(hipStreamSynchronize(E->stream));
     return 0;
 }
@@ -1492,7 +1512,7 @@ int beom_upload_tracers(beom_handle E, const double *q, const double *rq, const 
     HIP_TRY(hipSetDevice(E->device));
     const int outer = E->ntrc * E->d.nlay;
     int rc;
-    if (ctrg && !E->trc_ctrg && (rc = alloc_tracer_array(E, &E->trc_ctrg, errm, errm_len))) return rc;
+    if (ctrg && !E->trc_ctrg && (rc = alloc_aligned(E, E->trc_allocs, &E->trc_ctrg, tracer_cells(E), errm, errm_len))) return rc;
     if ((rc = copy_in(E, E->trc_q, q, (size_t)outer, errm, errm_len))) return rc;
     if ((rc = copy_in(E, E->trc_ctrg, ctrg, (size_t)outer, errm, errm_len))) return rc;
     if ((rc = hist_in(E, E->trc_rq, 2, rq, errm, errm_len, outer))) return rc;
@@ -1516,8 +1536,7 @@ int beom_download_tracers(beom_handle E, double *q, double *rq, char *errm, int 
 
 // ---- Lagrangian floats (beom_floats.h) -------------------------------------------------------------------------------------
 static void free_floats(beom_engine *E) {
-    for (void *p : E->flt_allocs) (void)hipFree(p);
-    E->flt_allocs.clear();
+    free_list(E->flt_allocs);
     E->nflt = 0; E->flt_ready = false; E->flt_nrec = 0; E->flt_stride = 1;
     E->flt_rec_tstp.clear();
     E->flt_x = E->flt_y = E->flt_k1x = E->flt_k1y = E->flt_xs = E->flt_ys = E->flt_rec = nullptr;
@@ -1525,16 +1544,6 @@ static void free_floats(beom_engine *E) {
     E->flt_first_dry = nullptr;
     E->flt_band = false; E->flt_fb = FloatBand{}; E->flt_in_s = E->flt_in_n = nullptr; E->flt_handovers = 0;
 }
-// a zeroed device array of n elements of `size` bytes
-static int alloc_float_array(beom_engine *E, void *p, size_t n, size_t size, char *errm, int errm_len) {
-    void *q = nullptr;
-    HIP_TRY(hipMalloc(&q, n * size));
-    E->flt_allocs.push_back(q);
-    HIP_TRY(hipMemsetAsync(q, 0, n * size, E->stream));
-    *(void **)p = q;
-    return 0;
-}
-
 int beom_set_floats(beom_handle E, int64_t n, int nrec, int stride, char *errm, int errm_len) {
     if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
     if (n < 0 || nrec < 0 || stride < 1) { set_err(errm, errm_len, "beom_set_floats: %lld floats, %d records, stride %d (n >= 0, nrec >= 0, stride >= 1)", (long long)n, nrec, stride); return -3; }
@@ -1553,11 +1562,11 @@ int beom_set_floats(beom_handle E, int64_t n, int nrec, int stride, char *errm, 
     E->nflt = (long long)n;
     const size_t m = (size_t)n;
     for (double **a : {&E->flt_x, &E->flt_y, &E->flt_k1x, &E->flt_k1y, &E->flt_xs, &E->flt_ys})
-        if ((rc = alloc_float_array(E, a, m, sizeof(double), errm, errm_len))) { free_floats(E); return rc; }
+        if ((rc = alloc_plain(E, E->flt_allocs, a, m, errm, errm_len))) { free_floats(E); return rc; }
     for (int32_t **a : {&E->flt_layer, &E->flt_rej})
-        if ((rc = alloc_float_array(E, a, m, sizeof(int32_t), errm, errm_len))) { free_floats(E); return rc; }
-    if ((rc = alloc_float_array(E, &E->flt_first_dry, 1, sizeof(unsigned long long), errm, errm_len))) { free_floats(E); return rc; }
-    if (nrec > 0 && (rc = alloc_float_array(E, &E->flt_rec, 3 * m * (size_t)nrec, sizeof(double), errm, errm_len))) { free_floats(E); return rc; }
+        if ((rc = alloc_plain(E, E->flt_allocs, a, m, errm, errm_len))) { free_floats(E); return rc; }
+    if ((rc = alloc_plain(E, E->flt_allocs, &E->flt_first_dry, 1, errm, errm_len))) { free_floats(E); return rc; }
+    if (nrec > 0 && (rc = alloc_plain(E, E->flt_allocs, &E->flt_rec, 3 * m * (size_t)nrec, errm, errm_len))) { free_floats(E); return rc; }
     E->flt_nrec = nrec; E->flt_stride = stride;
     HIP_TRY(hipStreamSynchronize(E->stream));
     return 0;
@@ -1665,19 +1674,19 @@ int beom_band_floats_set(beom_handle E, int64_t n, int capacity, int own0, int n
     E->nflt = (long long)n;
     const size_t m = (size_t)n, box = (size_t)kFloatRecordWords * ((size_t)capacity + 1);
     for (double **a : {&E->flt_x, &E->flt_y, &E->flt_k1x, &E->flt_k1y, &E->flt_xs, &E->flt_ys})
-        if ((rc = alloc_float_array(E, a, m, sizeof(double), errm, errm_len))) { free_floats(E); return rc; }
+        if ((rc = alloc_plain(E, E->flt_allocs, a, m, errm, errm_len))) { free_floats(E); return rc; }
     for (int32_t **a : {&E->flt_layer, &E->flt_rej})
-        if ((rc = alloc_float_array(E, a, m, sizeof(int32_t), errm, errm_len))) { free_floats(E); return rc; }
-    if ((rc = alloc_float_array(E, &E->flt_first_dry, 1, sizeof(unsigned long long), errm, errm_len))) { free_floats(E); return rc; }
+        if ((rc = alloc_plain(E, E->flt_allocs, a, m, errm, errm_len))) { free_floats(E); return rc; }
+    if ((rc = alloc_plain(E, E->flt_allocs, &E->flt_first_dry, 1, errm, errm_len))) { free_floats(E); return rc; }
     FloatBand fb{};
     fb.own0 = own0; fb.nown = nown; fb.gs = ghost_s; fb.Mf = frame_mm + 1; fb.nring = ring ? frame_mm : 0; fb.capacity = capacity;
     fb.lo = (ring || has_south) ? std::max(1, ghost_s + 1 - kFloatReach) : 1;
     fb.hi = (ring || has_north) ? std::min(E->d.M - 1, ghost_s + nown + kFloatReach) : E->d.M;
-    if ((rc = alloc_float_array(E, &fb.stats, 4, sizeof(unsigned long long), errm, errm_len))) { free_floats(E); return rc; }
-    if (has_south && ((rc = alloc_float_array(E, &fb.box_s, box, sizeof(unsigned long long), errm, errm_len)) ||
-                      (rc = alloc_float_array(E, &E->flt_in_s, box, sizeof(unsigned long long), errm, errm_len)))) { free_floats(E); return rc; }
-    if (has_north && ((rc = alloc_float_array(E, &fb.box_n, box, sizeof(unsigned long long), errm, errm_len)) ||
-                      (rc = alloc_float_array(E, &E->flt_in_n, box, sizeof(unsigned long long), errm, errm_len)))) { free_floats(E); return rc; }
+    if ((rc = alloc_plain(E, E->flt_allocs, &fb.stats, 4, errm, errm_len))) { free_floats(E); return rc; }
+    if (has_south && ((rc = alloc_plain(E, E->flt_allocs, &fb.box_s, box, errm, errm_len)) ||
+                      (rc = alloc_plain(E, E->flt_allocs, &E->flt_in_s, box, errm, errm_len)))) { free_floats(E); return rc; }
+    if (has_north && ((rc = alloc_plain(E, E->flt_allocs, &fb.box_n, box, errm, errm_len)) ||
+                      (rc = alloc_plain(E, E->flt_allocs, &E->flt_in_n, box, errm, errm_len)))) { free_floats(E); return rc; }
     E->flt_fb = fb; E->flt_band = true;
     E->flt_xper = xper != 0; E->flt_yper = ring != 0; E->flt_fmm = (double)frame_mm;
     HIP_TRY(hipStreamSynchronize(E->stream));
@@ -1771,169 +1780,103 @@ int beom_band_floats_download(beom_handle E, double *x, double *y, int32_t *laye
     return 0;
 }
 
-// ---- moments (beom_moments.h) ----------------------------------------------------------------------------------------------
-static void free_moments(beom_engine *E) {
-    for (void *p : E->mom_allocs) (void)hipFree(p);
-    E->mom_allocs.clear();
-    E->mom_level = 0; E->mom_stride = 1; E->mom_count = 0; E->mom_first = E->mom_last = 0;
-    for (int f = 0; f < 5; ++f) E->mom_ref[f] = E->mom_sum[f] = E->mom_sq[f] = nullptr;
+// ---- the time accumulators: moments (beom_moments.h) and tracer moments (beom_tracer_moments.h) ----------------------------
+static void accum_free(Accum &A) {
+    free_list(A.allocs);
+    A.level = 0; A.stride = 1; A.count = 0; A.first = A.last = 0;
+    for (int f = 0; f < 5; ++f) A.ref[f] = A.sum[f] = A.sq[f] = nullptr;
 }
-// a zeroed array of the state's shape [nlay][n1], element 1 aligned as dev_alloc's
-static int alloc_moment_array(beom_engine *E, double **p, char *errm, int errm_len) {
-    void *q = nullptr;
-    const size_t n = (size_t)E->d.nlay * (size_t)E->d.n1 + 16;
-    HIP_TRY(hipMalloc(&q, n * sizeof(double)));
-    E->mom_allocs.push_back(q);
-    HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(double), E->stream));
-    *p = (double *)q + 15;
+
+// level 0 frees; else zeroed arrays for the level's quantities.  A failed allocation frees them all and leaves level 0
+static int accum_set(beom_engine *E, Accum beom_engine::*which, int level, int stride, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    Accum &A = E->*which;
+    const AccumKind &K = *A.kind;
+    if (level < 0 || level > 3 || stride < 1) { set_err(errm, errm_len, K.bad_args, level, stride); return -3; }
+    if (K.no_tracer && level > 0 && E->ntrc < 1) { set_err(errm, errm_len, "%s", K.no_tracer); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    accum_free(A);
+    if (level == 0) return 0;
+    int rc = 0;
+    const size_t n = K.per_tracer ? tracer_cells(E) : state_cells(E);
+    const int nq = level >= 2 ? K.n2 : K.n1;
+    for (int f = 0; f < nq && !rc; ++f) {
+        rc = alloc_aligned(E, A.allocs, &A.ref[f], n, errm, errm_len);
+        if (!rc) rc = alloc_aligned(E, A.allocs, &A.sum[f], n, errm, errm_len);
+    }
+    for (int m = 0; m < K.nsq && !rc && level >= 3; ++m) rc = alloc_aligned(E, A.allocs, &A.sq[m], n, errm, errm_len);
+    if (rc) { accum_free(A); return rc; }
+    A.level = level; A.stride = stride;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+static int accum_reset(Accum &A) {
+    if (A.level < 1) return -3;
+    A.count = 0; A.first = A.last = 0;
+    return 0;
+}
+
+// ref, sum [quantities][rows][0:ndeg] and sq [second moments][rows][0:ndeg] of the caller (null: not wanted)
+static int accum_download(beom_engine *E, Accum beom_engine::*which, double *ref, double *sum, double *sq, long long *count,
+                          int *tstp_first, int *tstp_last, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    const Accum &A = E->*which;
+    if (A.level < 1) { set_err(errm, errm_len, "%s", A.kind->none); return -3; }
+    if (sq && A.level < 3) { set_err(errm, errm_len, A.kind->no_sq, A.level); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t rows = (size_t)(A.kind->per_tracer ? E->ntrc : 1) * (size_t)E->d.nlay, slab = ((size_t)E->d.ndeg + 1) * rows;
+    const int nq = A.level >= 2 ? A.kind->n2 : A.kind->n1, nsq = A.kind->nsq;
+    if (count) *count = A.count;
+    if (tstp_first) *tstp_first = A.first;
+    if (tstp_last) *tstp_last = A.last;
+    if (A.count == 0) {                // nothing sampled yet: the arrays hold whatever an earlier average left
+        if (ref) std::fill(ref, ref + nq * slab, 0.0);
+        if (sum) std::fill(sum, sum + nq * slab, 0.0);
+        if (sq) std::fill(sq, sq + nsq * slab, 0.0);
+        return 0;
+    }
+    int rc;
+    for (int f = 0; f < nq; ++f) {
+        if (ref && (rc = copy_out(E, ref + f * slab, A.ref[f], rows, errm, errm_len))) return rc;
+        if (sum && (rc = copy_out(E, sum + f * slab, A.sum[f], rows, errm, errm_len))) return rc;
+    }
+    for (int m = 0; m < nsq && sq; ++m)
+        if ((rc = copy_out(E, sq + m * slab, A.sq[m], rows, errm, errm_len))) return rc;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int beom_set_moments(beom_handle E, int level, int stride, char *errm, int errm_len) {
-    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (level < 0 || level > 3 || stride < 1) { set_err(errm, errm_len, "beom_set_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
-    HIP_TRY(hipSetDevice(E->device));
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    free_moments(E);
-    if (level == 0) return 0;
-    int rc = 0;
-    const int nf = level >= 2 ? 5 : 3;
-    for (int f = 0; f < nf && !rc; ++f) {
-        rc = alloc_moment_array(E, &E->mom_ref[f], errm, errm_len);
-        if (!rc) rc = alloc_moment_array(E, &E->mom_sum[f], errm, errm_len);
-    }
-    for (int m = 0; m < 5 && !rc && level >= 3; ++m) rc = alloc_moment_array(E, &E->mom_sq[m], errm, errm_len);
-    if (rc) { free_moments(E); return rc; }
-    E->mom_level = level; E->mom_stride = stride;
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    return 0;
+    return accum_set(E, &beom_engine::mom, level, stride, errm, errm_len);
+}
+int beom_set_tracer_moments(beom_handle E, int level, int stride, char *errm, int errm_len) {
+    return accum_set(E, &beom_engine::tmom, level, stride, errm, errm_len);
 }
 
-int beom_reset_moments(beom_handle E) {
-    if (!E) return -1;
-    if (E->mom_level < 1) return -3;
-    E->mom_count = 0; E->mom_first = E->mom_last = 0;
-    return 0;
-}
+int beom_reset_moments(beom_handle E) { return E ? accum_reset(E->mom) : -1; }
+int beom_reset_tracer_moments(beom_handle E) { return E ? accum_reset(E->tmom) : -1; }
 
-int beom_sample_moments(beom_handle E) {
+static int accum_sample(beom_engine *E, Accum beom_engine::*which, void (*launch)(beom_engine *, int)) {
     if (!E) return -1;
-    if (E->mom_level < 1) return -3;
+    const Accum &A = E->*which;
+    if (A.level < 1 || (A.kind->per_tracer && E->ntrc < 1)) return -3;
     if (hipSetDevice(E->device) != hipSuccess) return -9;
-    launch_moments(E, E->last_tstp);
+    launch(E, E->last_tstp);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
+int beom_sample_moments(beom_handle E) { return accum_sample(E, &beom_engine::mom, launch_moments); }
+int beom_sample_tracer_moments(beom_handle E) { return accum_sample(E, &beom_engine::tmom, launch_tracer_moments); }
 
 int beom_download_moments(beom_handle E, double *ref, double *sum, double *sq, long long *count, int *tstp_first, int *tstp_last,
                           char *errm, int errm_len) {
-    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (E->mom_level < 1) { set_err(errm, errm_len, "beom_download_moments: the handle keeps no moments (beom_set_moments)"); return -3; }
-    if (sq && E->mom_level < 3) { set_err(errm, errm_len, "beom_download_moments: the second moments are kept at level 3, this handle has level %d", E->mom_level); return -3; }
-    HIP_TRY(hipSetDevice(E->device));
-    const size_t nl = (size_t)E->d.nlay, slab = ((size_t)E->d.ndeg + 1) * nl;
-    const int nf = E->mom_level >= 2 ? 5 : 3;
-    if (count) *count = E->mom_count;
-    if (tstp_first) *tstp_first = E->mom_first;
-    if (tstp_last) *tstp_last = E->mom_last;
-    if (E->mom_count == 0) {           // nothing sampled yet: the arrays hold whatever an earlier average left
-        if (ref) std::fill(ref, ref + nf * slab, 0.0);
-        if (sum) std::fill(sum, sum + nf * slab, 0.0);
-        if (sq) std::fill(sq, sq + 5 * slab, 0.0);
-        return 0;
-    }
-    int rc;
-    for (int f = 0; f < nf; ++f) {
-        if (ref && (rc = copy_out(E, ref + f * slab, E->mom_ref[f], nl, errm, errm_len))) return rc;
-        if (sum && (rc = copy_out(E, sum + f * slab, E->mom_sum[f], nl, errm, errm_len))) return rc;
-    }
-    for (int m = 0; m < 5 && sq; ++m)
-        if ((rc = copy_out(E, sq + m * slab, E->mom_sq[m], nl, errm, errm_len))) return rc;
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return accum_download(E, &beom_engine::mom, ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
 }
-
-// ---- tracer moments (beom_tracer_moments.h) ----------------------------------------------------------------------------------
-static void free_tracer_moments(beom_engine *E) {
-    for (void *p : E->tmom_allocs) (void)hipFree(p);
-    E->tmom_allocs.clear();
-    E->tmom_level = 0; E->tmom_stride = 1; E->tmom_count = 0; E->tmom_first = E->tmom_last = 0;
-    for (int k = 0; k < 4; ++k) E->tmom_ref[k] = E->tmom_sum[k] = nullptr;
-    E->tmom_sq = nullptr;
-}
-// a zeroed array of the tracers' shape [ntrc][nlay][n1], cell 1 aligned as dev_alloc's
-static int alloc_tracer_moment_array(beom_engine *E, double **p, char *errm, int errm_len) {
-    void *q = nullptr;
-    const size_t n = (size_t)E->ntrc * E->d.nlay * (size_t)E->d.n1 + 16;
-    HIP_TRY(hipMalloc(&q, n * sizeof(double)));
-    E->tmom_allocs.push_back(q);
-    HIP_TRY(hipMemsetAsync(q, 0, n * sizeof(double), E->stream));
-    *p = (double *)q + 15;
-    return 0;
-}
-
-int beom_set_tracer_moments(beom_handle E, int level, int stride, char *errm, int errm_len) {
-    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (level < 0 || level > 3 || stride < 1) { set_err(errm, errm_len, "beom_set_tracer_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
-    if (level > 0 && E->ntrc < 1) { set_err(errm, errm_len, "beom_set_tracer_moments: the handle carries no tracer (beom_set_tracers comes first)"); return -3; }
-    HIP_TRY(hipSetDevice(E->device));
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    free_tracer_moments(E);
-    if (level == 0) return 0;
-    int rc = 0;
-    const int nq = level >= 2 ? 4 : 2;
-    for (int k = 0; k < nq && !rc; ++k) {
-        rc = alloc_tracer_moment_array(E, &E->tmom_ref[k], errm, errm_len);
-        if (!rc) rc = alloc_tracer_moment_array(E, &E->tmom_sum[k], errm, errm_len);
-    }
-    if (!rc && level >= 3) rc = alloc_tracer_moment_array(E, &E->tmom_sq, errm, errm_len);
-    if (rc) { free_tracer_moments(E); return rc; }
-    E->tmom_level = level; E->tmom_stride = stride;
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    return 0;
-}
-
-int beom_reset_tracer_moments(beom_handle E) {
-    if (!E) return -1;
-    if (E->tmom_level < 1) return -3;
-    E->tmom_count = 0; E->tmom_first = E->tmom_last = 0;
-    return 0;
-}
-
-int beom_sample_tracer_moments(beom_handle E) {
-    if (!E) return -1;
-    if (E->tmom_level < 1 || E->ntrc < 1) return -3;
-    if (hipSetDevice(E->device) != hipSuccess) return -9;
-    launch_tracer_moments(E, E->last_tstp);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
 int beom_download_tracer_moments(beom_handle E, double *ref, double *sum, double *sq, long long *count, int *tstp_first, int *tstp_last,
                                  char *errm, int errm_len) {
-    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (E->tmom_level < 1) { set_err(errm, errm_len, "beom_download_tracer_moments: the handle keeps no tracer moments (beom_set_tracer_moments)"); return -3; }
-    if (sq && E->tmom_level < 3) { set_err(errm, errm_len, "beom_download_tracer_moments: the second moment is kept at level 3, this handle has level %d", E->tmom_level); return -3; }
-    HIP_TRY(hipSetDevice(E->device));
-    const size_t outer = (size_t)E->ntrc * (size_t)E->d.nlay, slab = ((size_t)E->d.ndeg + 1) * outer;
-    const int nq = E->tmom_level >= 2 ? 4 : 2;
-    if (count) *count = E->tmom_count;
-    if (tstp_first) *tstp_first = E->tmom_first;
-    if (tstp_last) *tstp_last = E->tmom_last;
-    if (E->tmom_count == 0) {          // nothing sampled yet: the arrays hold whatever an earlier average left
-        if (ref) std::fill(ref, ref + nq * slab, 0.0);
-        if (sum) std::fill(sum, sum + nq * slab, 0.0);
-        if (sq) std::fill(sq, sq + slab, 0.0);
-        return 0;
-    }
-    int rc;
-    for (int k = 0; k < nq; ++k) {
-        if (ref && (rc = copy_out(E, ref + k * slab, E->tmom_ref[k], outer, errm, errm_len))) return rc;
-        if (sum && (rc = copy_out(E, sum + k * slab, E->tmom_sum[k], outer, errm, errm_len))) return rc;
-    }
-    if (sq && (rc = copy_out(E, sq, E->tmom_sq, outer, errm, errm_len))) return rc;
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return accum_download(E, &beom_engine::tmom, ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
 }
 
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)
@@ -2006,12 +1949,12 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
     if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far
     if (!strcmp(what, "float_handovers")) return (int)std::min<long long>(E->flt_handovers, 2000000000ll);   // (bands; as of the latest download)
-    if (!strcmp(what, "tracer_moments")) return E->tmom_level;
-    if (!strcmp(what, "tracer_moment_samples")) return (int)std::min<long long>(E->tmom_count, 2000000000ll);
-    if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom_launches, 2000000000ll);     // all calls so far
-    if (!strcmp(what, "moments")) return E->mom_level;
-    if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom_count, 2000000000ll);
-    if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom_launches, 2000000000ll);     // all calls so far
+    if (!strcmp(what, "tracer_moments")) return E->tmom.level;
+    if (!strcmp(what, "tracer_moment_samples")) return (int)std::min<long long>(E->tmom.count, 2000000000ll);
+    if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom.launches, 2000000000ll);     // all calls so far
+    if (!strcmp(what, "moments")) return E->mom.level;
+    if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom.count, 2000000000ll);
+    if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom.launches, 2000000000ll);     // all calls so far
     if (!strcmp(what, "lid_sweeps")) return (int)std::min<long long>(E->lid_sweeps, 2000000000ll);        // Gauss-Seidel sweeps kept, all steps so far
     if (!strcmp(what, "lid_solves")) return (int)std::min<long long>(E->lid_solves, 2000000000ll);
     if (!strcmp(what, "lid_launches")) return (int)std::min<long long>(E->lid_launches, 2000000000ll);

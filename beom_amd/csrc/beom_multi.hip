@@ -279,8 +279,8 @@ struct beom_multi {
     int ntrc = 0;                  // passive tracers carried by every band (beom_multi_set_tracers): q joins the exchange
     // moments kept by every band (beom_multi_set_moments): the bands sample on request ("moments_by_caller"), the step whose
     // sample is still owed (0 = none) is taken where the main streams next join the exchange
-    int mom_level = 0, mom_stride = 1, mom_due = 0;
-    int tmom_level = 0, tmom_stride = 1, tmom_due = 0;      // the tracer moments likewise (beom_multi_set_tracer_moments)
+    struct Moments { int level = 0, stride = 1, due = 0; };
+    Moments mom, tmom;             // (tmom: the tracer moments likewise, beom_multi_set_tracer_moments)
     // Lagrangian floats on the bands (beom_multi_set_floats): every band holds all nflt slots; flt_mode is the float launch
     // owed where the main streams next join the exchange (0 none, 1 stage 1, 3 stage 2 + stage 1 of the next step)
     long long nflt = 0;
@@ -848,7 +848,7 @@ int beom_multi_set_tracers(beom_multi_handle M, int ntrc, char *errm, int errm_l
     M_RC(tracers_refused(M, "beom_multi_set_tracers", errm, errm_len));
     M_RC(beom_multi_sync(M, errm, errm_len));
     for (int k = 0; k < M->n; ++k) M_RC(beom_set_tracers(M->eng[k], ntrc, errm, errm_len));
-    if (ntrc != M->ntrc) { M->tmom_level = 0; M->tmom_stride = 1; M->tmom_due = 0; }      // (the bands freed their tracer moments)
+    if (ntrc != M->ntrc) M->tmom = {};       // (the bands freed their tracer moments)
     M->ntrc = ntrc;
     if (M->nb == 1) return 0;
     // the exchange buffers for 5 + ntrc fields (nothing is in flight after the sync)
@@ -1099,111 +1099,125 @@ int beom_multi_update_floats(beom_multi_handle M, int stage) {
 }
 
 // ---- moments (beom_set_moments) on the bands: every band accumulates over all its rows, ghosts included, and the global
-//      arrays take the owned rows; a ring's row mm+1 comes from the companion frame, which samples behind its own steps ----
-int beom_multi_set_moments(beom_multi_handle M, int level, int stride, char *errm, int errm_len) {
-    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_moments: an earlier step failed half way; destroy the handle"); return -30; }
-    if (level < 0 || level > 3 || stride < 1) { m_err(errm, errm_len, "beom_multi_set_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
-    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_set_moments: a handle that holds one band's window does not keep moments yet (its global arrays are nowhere assembled); use a handle created from the global arrays"); return -6; }
-    M_RC(beom_multi_sync(M, errm, errm_len));
-    const bool single = M->nb == 1 && !M->ring;       // steps through beom_step: the handle samples by itself
-    for (int k = 0; k < M->n; ++k) {
-        M_RC(beom_set_moments(M->eng[k], level, stride, errm, errm_len));
-        if (beom_set_option(M->eng[k], "moments_by_caller", single ? 0 : 1)) { m_err(errm, errm_len, "beom_multi_set_moments: option refused"); return -3; }
-    }
-    if (M->mini) M_RC(beom_set_moments(M->mini, level, stride, errm, errm_len));
-    M->mom_level = level; M->mom_stride = stride; M->mom_due = 0;
+//      arrays take the owned rows; a ring's row mm+1 comes from the companion frame, which samples behind its own steps.
+//      Tracer moments (beom_set_tracer_moments) likewise: every band samples over its whole window, behind the wait for
+//      the landed ghost rows (the S row of a band's first owned row then holds the neighbour's owned values).  Rings and
+//      handles that hold one band's window carry no tracers, hence no tracer moments. ----
+static int moments_refused(beom_multi *M, const char *text, char *errm, int errm_len) {
+    if (M->local_mode && text) { m_err(errm, errm_len, "%s", text); return -6; }
     return 0;
 }
-
-int beom_multi_reset_moments(beom_multi_handle M, char *errm, int errm_len) {
-    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    if (M->mom_level < 1) { m_err(errm, errm_len, "beom_multi_reset_moments: the handle keeps no moments (beom_multi_set_moments)"); return -3; }
-    M_RC(beom_multi_sync(M, errm, errm_len));
-    for (int k = 0; k < M->n; ++k) M_RC(beom_reset_moments(M->eng[k]));
-    if (M->mini) M_RC(beom_reset_moments(M->mini));
-    M->mom_due = 0;
-    return 0;
-}
-
-int beom_multi_download_moments(beom_multi_handle M, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
-                                int *tstp_last, char *errm, int errm_len) {
-    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_moments: this handle holds a window and keeps no moments"); return -6; }
-    if (M->mom_level < 1) { m_err(errm, errm_len, "beom_multi_download_moments: the handle keeps no moments (beom_multi_set_moments)"); return -3; }
-    if (sq && M->mom_level < 3) { m_err(errm, errm_len, "beom_multi_download_moments: the second moments are kept at level 3, this handle has level %d", M->mom_level); return -3; }
-    M_RC(beom_multi_sync(M, errm, errm_len));
-    if (M->nb == 1 && !M->ring) return beom_download_moments(M->eng[0], ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
-    const int nl = M->P.nlay, nf = M->mom_level >= 2 ? 5 : 3;
-    double *dst[3] = {ref, sum, sq};
-    const size_t outer[3] = {(size_t)nf * nl, (size_t)nf * nl, (size_t)5 * nl};
-    for (const Part &p : parts(M)) {
-        std::vector<double> a[3];
-        for (int f = 0; f < 3; ++f) if (dst[f]) a[f].assign(outer[f] * p.n1(), 0.0);
-        long long cnt = 0;
-        int t0 = 0, t1 = 0;
-        M_RC(beom_download_moments(p.eng, ptr(a[0]), ptr(a[1]), ptr(a[2]), &cnt, &t0, &t1, errm, errm_len));
-        if (p.k == 0) { if (count) *count = cnt; if (tstp_first) *tstp_first = t0; if (tstp_last) *tstp_last = t1; }
-        for (int f = 0; f < 3; ++f) copy_rows(dst[f], ptr(a[f]), outer[f], 1, p.out);
-    }
-    return 0;
-}
-
-// ---- tracer moments (beom_set_tracer_moments) on the bands: every band samples over its whole window, behind the wait for
-//      the landed ghost rows (the S row of a band's first owned row then holds the neighbour's owned values), and the global
-//      arrays take the owned rows.  Rings and handles that hold one band's window carry no tracers, hence none of this. ----
 static int tracer_moments_refused(beom_multi *M, const char *who, char *errm, int errm_len) {
     if (M->local_mode) { m_err(errm, errm_len, "%s: a handle that holds one band's window carries no tracers (its exchange is sized at creation), so there is nothing to average", who); return -6; }
     if (M->ring) { m_err(errm, errm_len, "%s: bands of a frame periodic in y carry no tracers (the ring's companion frame has no q), so there is nothing to average; use a single handle", who); return -6; }
     return 0;
 }
 
-int beom_multi_set_tracer_moments(beom_multi_handle M, int level, int stride, char *errm, int errm_len) {
+// What tells the two accumulators apart on the bands: the record, the engine's entry points, who is refused (and what the
+// refusal of set, reset and download is told), the quantities at level 1 and at levels 2 and 3, the second moments, the
+// arrays' outer size, and the texts.
+struct MomentKind {
+    beom_multi::Moments beom_multi::*rec;
+    int (*set)(beom_handle, int, int, char *, int);
+    int (*reset)(beom_handle);
+    int (*sample)(beom_handle);
+    int (*download)(beom_handle, double *, double *, double *, long long *, int *, int *, char *, int);
+    int (*refused)(beom_multi *, const char *, char *, int);
+    const char *refusal[3];
+    int n1, n2, nsq;
+    bool per_tracer;
+    const char *failed, *bad_args, *no_tracer, *option, *reset_none, *none, *no_sq, *sample_failed;
+};
+static const MomentKind kFieldMoments{
+    &beom_multi::mom, beom_set_moments, beom_reset_moments, beom_sample_moments, beom_download_moments, moments_refused,
+    {"beom_multi_set_moments: a handle that holds one band's window does not keep moments yet (its global arrays are nowhere assembled); use a handle created from the global arrays",
+     nullptr, "beom_multi_download_moments: this handle holds a window and keeps no moments"},
+    3, 5, 5, false,
+    "beom_multi_set_moments: an earlier step failed half way; destroy the handle",
+    "beom_multi_set_moments: level %d, stride %d (level 0..3, stride >= 1)", nullptr,
+    "beom_multi_set_moments: option refused",
+    "beom_multi_reset_moments: the handle keeps no moments (beom_multi_set_moments)",
+    "beom_multi_download_moments: the handle keeps no moments (beom_multi_set_moments)",
+    "beom_multi_download_moments: the second moments are kept at level 3, this handle has level %d",
+    "beom_sample_moments failed on band %d (step %d)"};
+static const MomentKind kTracerMoments{
+    &beom_multi::tmom, beom_set_tracer_moments, beom_reset_tracer_moments, beom_sample_tracer_moments, beom_download_tracer_moments,
+    tracer_moments_refused,
+    {"beom_multi_set_tracer_moments", "beom_multi_reset_tracer_moments", "beom_multi_download_tracer_moments"},
+    2, 4, 1, true,
+    "beom_multi_set_tracer_moments: an earlier step failed half way; destroy the handle",
+    "beom_multi_set_tracer_moments: level %d, stride %d (level 0..3, stride >= 1)",
+    "beom_multi_set_tracer_moments: the handle carries no tracer (beom_multi_set_tracers comes first)",
+    "beom_multi_set_tracer_moments: option refused",
+    "beom_multi_reset_tracer_moments: the handle keeps no tracer moments (beom_multi_set_tracer_moments)",
+    "beom_multi_download_tracer_moments: the handle keeps no tracer moments (beom_multi_set_tracer_moments)",
+    "beom_multi_download_tracer_moments: the second moment is kept at level 3, this handle has level %d",
+    "beom_sample_tracer_moments failed on band %d (step %d)"};
+
+// (the companion frame, M->mini, exists on rings only: the tracer moments, which refuse rings, never reach it)
+static int multi_set_accum(beom_multi *M, const MomentKind &K, int level, int stride, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: an earlier step failed half way; destroy the handle"); return -30; }
-    if (level < 0 || level > 3 || stride < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: level %d, stride %d (level 0..3, stride >= 1)", level, stride); return -3; }
-    M_RC(tracer_moments_refused(M, "beom_multi_set_tracer_moments", errm, errm_len));
-    if (level > 0 && M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: the handle carries no tracer (beom_multi_set_tracers comes first)"); return -3; }
+    if (M->failed) { m_err(errm, errm_len, "%s", K.failed); return -30; }
+    if (level < 0 || level > 3 || stride < 1) { m_err(errm, errm_len, K.bad_args, level, stride); return -3; }
+    M_RC(K.refused(M, K.refusal[0], errm, errm_len));
+    if (K.no_tracer && level > 0 && M->ntrc < 1) { m_err(errm, errm_len, "%s", K.no_tracer); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
     for (int k = 0; k < M->n; ++k) {
-        M_RC(beom_set_tracer_moments(M->eng[k], level, stride, errm, errm_len));
-        if (beom_set_option(M->eng[k], "moments_by_caller", M->nb == 1 ? 0 : 1)) { m_err(errm, errm_len, "beom_multi_set_tracer_moments: option refused"); return -3; }
+        M_RC(K.set(M->eng[k], level, stride, errm, errm_len));
+        // a whole frame steps through beom_step: the handle samples by itself
+        if (beom_set_option(M->eng[k], "moments_by_caller", multi_whole(M) ? 0 : 1)) { m_err(errm, errm_len, "%s", K.option); return -3; }
     }
-    M->tmom_level = level; M->tmom_stride = stride; M->tmom_due = 0;
+    if (M->mini) M_RC(K.set(M->mini, level, stride, errm, errm_len));
+    M->*K.rec = {level, stride, 0};
     return 0;
 }
 
-int beom_multi_reset_tracer_moments(beom_multi_handle M, char *errm, int errm_len) {
+static int multi_reset_accum(beom_multi *M, const MomentKind &K, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    M_RC(tracer_moments_refused(M, "beom_multi_reset_tracer_moments", errm, errm_len));
-    if (M->tmom_level < 1) { m_err(errm, errm_len, "beom_multi_reset_tracer_moments: the handle keeps no tracer moments (beom_multi_set_tracer_moments)"); return -3; }
+    M_RC(K.refused(M, K.refusal[1], errm, errm_len));
+    if ((M->*K.rec).level < 1) { m_err(errm, errm_len, "%s", K.reset_none); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
-    for (int k = 0; k < M->n; ++k) M_RC(beom_reset_tracer_moments(M->eng[k]));
-    M->tmom_due = 0;
+    for (int k = 0; k < M->n; ++k) M_RC(K.reset(M->eng[k]));
+    if (M->mini) M_RC(K.reset(M->mini));
+    (M->*K.rec).due = 0;
     return 0;
 }
 
-int beom_multi_download_tracer_moments(beom_multi_handle M, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
-                                       int *tstp_last, char *errm, int errm_len) {
+static int multi_download_accum(beom_multi *M, const MomentKind &K, double *ref, double *sum, double *sq, long long *count,
+                                int *tstp_first, int *tstp_last, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    M_RC(tracer_moments_refused(M, "beom_multi_download_tracer_moments", errm, errm_len));
-    if (M->tmom_level < 1) { m_err(errm, errm_len, "beom_multi_download_tracer_moments: the handle keeps no tracer moments (beom_multi_set_tracer_moments)"); return -3; }
-    if (sq && M->tmom_level < 3) { m_err(errm, errm_len, "beom_multi_download_tracer_moments: the second moment is kept at level 3, this handle has level %d", M->tmom_level); return -3; }
+    M_RC(K.refused(M, K.refusal[2], errm, errm_len));
+    const int level = (M->*K.rec).level;
+    if (level < 1) { m_err(errm, errm_len, "%s", K.none); return -3; }
+    if (sq && level < 3) { m_err(errm, errm_len, K.no_sq, level); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
-    if (M->nb == 1) return beom_download_tracer_moments(M->eng[0], ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
-    const size_t per = (size_t)M->ntrc * M->P.nlay, nq = M->tmom_level >= 2 ? 4 : 2;
+    if (multi_whole(M)) return K.download(M->eng[0], ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
+    const size_t per = (size_t)(K.per_tracer ? M->ntrc : 1) * M->P.nlay, nq = level >= 2 ? K.n2 : K.n1;
     double *dst[3] = {ref, sum, sq};
-    const size_t outer[3] = {nq * per, nq * per, per};
+    const size_t outer[3] = {nq * per, nq * per, K.nsq * per};
     for (const Part &p : parts(M)) {
         std::vector<double> a[3];
         for (int f = 0; f < 3; ++f) if (dst[f]) a[f].assign(outer[f] * p.n1(), 0.0);
         long long cnt = 0;
         int t0 = 0, t1 = 0;
-        M_RC(beom_download_tracer_moments(p.eng, ptr(a[0]), ptr(a[1]), ptr(a[2]), &cnt, &t0, &t1, errm, errm_len));
+        M_RC(K.download(p.eng, ptr(a[0]), ptr(a[1]), ptr(a[2]), &cnt, &t0, &t1, errm, errm_len));
         if (p.k == 0) { if (count) *count = cnt; if (tstp_first) *tstp_first = t0; if (tstp_last) *tstp_last = t1; }
         for (int f = 0; f < 3; ++f) copy_rows(dst[f], ptr(a[f]), outer[f], 1, p.out);
     }
     return 0;
+}
+
+int beom_multi_set_moments(beom_multi_handle M, int level, int stride, char *errm, int errm_len) { return multi_set_accum(M, kFieldMoments, level, stride, errm, errm_len); }
+int beom_multi_set_tracer_moments(beom_multi_handle M, int level, int stride, char *errm, int errm_len) { return multi_set_accum(M, kTracerMoments, level, stride, errm, errm_len); }
+int beom_multi_reset_moments(beom_multi_handle M, char *errm, int errm_len) { return multi_reset_accum(M, kFieldMoments, errm, errm_len); }
+int beom_multi_reset_tracer_moments(beom_multi_handle M, char *errm, int errm_len) { return multi_reset_accum(M, kTracerMoments, errm, errm_len); }
+int beom_multi_download_moments(beom_multi_handle M, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
+                                int *tstp_last, char *errm, int errm_len) {
+    return multi_download_accum(M, kFieldMoments, ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
+}
+int beom_multi_download_tracer_moments(beom_multi_handle M, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
+                                       int *tstp_last, char *errm, int errm_len) {
+    return multi_download_accum(M, kTracerMoments, ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
 }
 
 // ---- output records of all bands (SURVEY §8f N2 for the multi-device handle): as beom_download_outputs /
@@ -1408,12 +1422,12 @@ int beom_multi_profile_stop(beom_multi_handle M, double *ms, int *launches, char
 // separate u and v sweeps, option "overlap" = 0) run whole, the exchange after them.
 // the moments' sample a step left owing, on every band's main stream (which has joined the exchange of that step)
 static int multi_sample_due(beom_multi *M, char *errm, int errm_len) {
-    for (int k = 0; k < M->n && M->mom_due; ++k)
-        if (beom_sample_moments(M->eng[k])) { m_err(errm, errm_len, "beom_sample_moments failed on band %d (step %d)", M->band[k].index, M->mom_due); return -3; }
-    M->mom_due = 0;
-    for (int k = 0; k < M->n && M->tmom_due; ++k)
-        if (beom_sample_tracer_moments(M->eng[k])) { m_err(errm, errm_len, "beom_sample_tracer_moments failed on band %d (step %d)", M->band[k].index, M->tmom_due); return -3; }
-    M->tmom_due = 0;
+    for (const MomentKind *K : {&kFieldMoments, &kTracerMoments}) {
+        int &due = (M->*K->rec).due;
+        for (int k = 0; k < M->n && due; ++k)
+            if (K->sample(M->eng[k])) { m_err(errm, errm_len, K->sample_failed, M->band[k].index, due); return -3; }
+        due = 0;
+    }
     return 0;
 }
 
@@ -1557,8 +1571,8 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
             M->pending[k] = 1;
         }
     }
-    if (M->mom_level > 0 && t % M->mom_stride == 0) M->mom_due = t;
-    if (M->tmom_level > 0 && t % M->tmom_stride == 0) M->tmom_due = t;
+    for (beom_multi::Moments *m : {&M->mom, &M->tmom})
+        if (m->level > 0 && t % m->stride == 0) m->due = t;
     if (M->nflt > 0) M->flt_mode = 3;
     return 0;
 }
@@ -1582,7 +1596,7 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
             return rc;
         }
     }
-    if (M->mom_due || M->tmom_due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
+    if (M->mom.due || M->tmom.due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
         M_RC(multi_join_exchange(M, errm, errm_len));
         M_RC(multi_sample_due(M, errm, errm_len));
         if (M->flt_mode) {

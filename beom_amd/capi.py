@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_dense_host.h",
                "beom_bands_host.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -258,6 +258,17 @@ def load(path: Optional[str] = None) -> C.CDLL:
         getattr(lib, "beom_sample_" + stem).argtypes = [H]
         for name in names:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_series"):          # (likewise: an older build has no series)
+        ip = C.POINTER(ci)
+        lib.beom_series_count.argtypes = [ci, ci]
+        lib.beom_set_series.argtypes = [H, ci, ci, ci, cp, ci]
+        lib.beom_band_set_series.argtypes = [H, ci, ci, ci, ci, ci, cp, ci]
+        lib.beom_sample_series.argtypes = [H]
+        lib.beom_download_series.argtypes = [H, dpp, ip, ip, cp, ci]
+        lib.beom_multi_set_series.argtypes = [MH, ci, ci, ci, cp, ci]
+        lib.beom_multi_download_series.argtypes = [MH, dpp, ip, ip, cp, ci]
+        for name in SERIES_EXPORTS:
+            getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
                  "beom_multi_stats", "beom_multi_create_ex", "beom_multi_describe", "beom_multi_engine",
@@ -288,6 +299,8 @@ MOMENT_EXPORTS = ("beom_set_moments", "beom_reset_moments", "beom_sample_moments
 TRACER_MOMENT_EXPORTS = ("beom_set_tracer_moments", "beom_reset_tracer_moments", "beom_sample_tracer_moments",
                          "beom_download_tracer_moments", "beom_multi_set_tracer_moments", "beom_multi_reset_tracer_moments",
                          "beom_multi_download_tracer_moments")
+SERIES_EXPORTS = ("beom_series_count", "beom_set_series", "beom_sample_series", "beom_download_series", "beom_band_set_series",
+                  "beom_multi_set_series", "beom_multi_download_series")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
 
 EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "beom_info", "beom_download_diag", "beom_create", "beom_destroy", "beom_set_rigid_lid", "beom_download_pressure",
@@ -311,7 +324,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -566,7 +579,53 @@ class _TracerMoments(_Accum):
                                     "var_c", lambda q, m: q - m[1] * m[1])
 
 
-class Engine(_Tracers, _Floats, _Moments, _TracerMoments):
+class _Series:
+    """A record of the row sums per sampled step, kept on the device (beom_set_series, include/beom_hip.h): the quantities of
+    integral_rows for every row of the frame and, at level 2, the row sums of the layer transports h_u, h_v, written behind
+    every step with tstp % stride == 0 without a host copy.  Shared by Engine and MultiEngine."""
+
+    series_level = 0
+    series_records = 0
+    _ser_multi = False
+
+    def set_series(self, level: int, stride: int = 1, records: int = 64):
+        """level 1: vol, ke, ens, circ per layer and eta2 per row; 2: and tu, tv per layer; 0 frees.  `records`: what the
+        recorder holds between two download_series (a step call that would overflow it is refused).  Between steps only."""
+        fn = self.lib.beom_multi_set_series if self._ser_multi else self.lib.beom_set_series
+        self._check(fn(self.h, int(level), int(stride), int(records), self._err, ERRLEN))
+        self.series_level, self.series_records = int(level), (int(records) if level else 0)
+
+    def download_series(self) -> dict:
+        """The records held, oldest first, and empties the recorder.  count, tstp[n]; rows[n, M, cnt] (M = mm+1 rows in global
+        order); raw[n, 4*nlay+1] = combine_integral_rows per record (scale_integrals gives the figures); the views vol, ke,
+        ens, circ [n, M, nlay] and eta2 [n, M]; at level 2 tu, tv [n, M, nlay], the row sums of the stored transports h_u,
+        h_v (thickness * velocity through a cell's W resp. S face, m^2/s), and psi[n, M, nlay] = dl * cumsum(tv, layers):
+        the volume transport (m^3/s) above the base of layer l through the south faces of row j."""
+        nl, M = self.p.nlay, self.p.mm + 1
+        fn = self.lib.beom_multi_download_series if self._ser_multi else self.lib.beom_download_series
+        if self.series_level < 1:                                        # (the library says why)
+            self._check(fn(self.h, None, None, None, self._err, ERRLEN))
+            raise BeomError("download_series: the handle keeps no series (set_series)")
+        cnt = self.lib.beom_series_count(nl, self.series_level)
+        rows = np.zeros((max(self.series_records, 1), M, cnt))
+        tstp = (C.c_int * max(self.series_records, 1))()
+        count = C.c_int(0)
+        self._check(fn(self.h, _dp(rows), tstp, C.byref(count), self._err, ERRLEN))
+        n = count.value
+        rows = rows[:n].copy()
+        q = rows[:, :, :4 * nl].reshape(n, M, nl, 4)
+        out = {"count": n, "tstp": np.array(list(tstp)[:n], dtype=np.int64), "rows": rows,
+               "raw": np.array([combine_integral_rows(r[:, :4 * nl + 1]) for r in rows]).reshape(n, 4 * nl + 1),
+               "eta2": rows[:, :, 4 * nl]}
+        for k, name in enumerate(INTEGRAL_NAMES):
+            out[name] = q[..., k]
+        if self.series_level >= 2:
+            out["tu"], out["tv"] = rows[:, :, 4 * nl + 1:5 * nl + 1], rows[:, :, 5 * nl + 1:6 * nl + 1]
+            out["psi"] = float(self.p.dl) * np.cumsum(out["tv"], axis=2)
+        return out
+
+
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
@@ -731,7 +790,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments):
         "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did), "tracers", "tracer_scheme" (1 upstream, 2 limited), "floats",
         "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
         "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
-        "tracer_moment_launches"."""
+        "tracer_moment_launches", "series" (the series' level), "series_records" (records its recorder holds)."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))
@@ -794,11 +853,17 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments):
         """Per-sweep entry: one sample of the tracers and the state as they stand, whatever the stride."""
         self._accum_plain("sample", "tracer_moments", "tracer moments")
 
+    def sample_series(self):
+        """Per-sweep entry: one record of the fields as they stand, under the last step's number, whatever the stride."""
+        rc = self.lib.beom_sample_series(self.h)
+        if rc != 0:
+            raise BeomError("beom_hip error %d: beom_sample_series (series set? recorder full?)" % rc)
+
     def rebuild_fluxes(self): self._check(self.lib.beom_rebuild_fluxes(self.h))
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""
@@ -829,6 +894,7 @@ class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments):
     _trc_prefix = "beom_multi_"
     _mom_multi = True
     _flt_multi = True
+    _ser_multi = True
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:

@@ -17,6 +17,7 @@
 #include "beom_dev.h"
 #include "beom_kernels.h"
 #include "beom_integrals.h"
+#include "beom_series.h"
 #include "beom_tracers.h"
 #include "beom_tracers_lim.h"
 #include "beom_floats.h"
@@ -162,6 +163,7 @@ struct beom_engine {
     // conservation integrals (beom_integral_rows): chunk sums and row sums of up to M rows, allocated on the first call; on
     // the table path also the packed cell of every (i, j) and the wraps read off neig
     double *integ_part = nullptr, *integ_rows = nullptr;
+    int integ_count = 0;               // entries per row the two are sized for (the series at level 2 asks for more)
     int32_t *integ_cellmap = nullptr;
     int integ_xper = 0, integ_yper = 0;
     // passive tracers (beom_set_tracers; beom_tracers.h): the contents and the partner the sweep writes them to, the two
@@ -199,6 +201,13 @@ struct beom_engine {
     // tracer moments (beom_set_tracer_moments; beom_tracer_moments.h): per quantity q, c, fu, fv the reference and the shifted
     // sum, at level 3 the shifted second moment of c, in arrays of the tracers' shape; level, stride and count of their own
     Accum tmom{&kTracerMoments};
+    // series (beom_set_series; beom_series.h): a recorder [nrec][ser_rows][count] of the row sums of local rows ser_jlo ..
+    // ser_jlo+ser_rows-1, one record behind every step with tstp % stride == 0, with the step of every held record
+    int ser_level = 0, ser_stride = 1, ser_nrec = 0, ser_jlo = 1, ser_rows = 0;
+    bool ser_by_caller = false;        // a band: beom_step takes no record by itself (beom_band_set_series)
+    double *ser_rec = nullptr;
+    std::vector<int> ser_tstp;         // (its size = the records held)
+    std::vector<void *> ser_allocs;
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -530,7 +539,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -854,6 +863,29 @@ static void launch_tracer_moments(beom_engine *E, int tstp) {
 #undef TMOM_GO
     accum_note_sample(E->tmom, tstp);
 }
+// one record of the series (beom_series.h) of the fields as they stand into the next free slot, under step tstp
+static bool series_due(const beom_engine *E, int tstp) {
+    return E->ser_level > 0 && tstp % E->ser_stride == 0 && (int)E->ser_tstp.size() < E->ser_nrec;
+}
+static void launch_series(beom_engine *E, int tstp) {
+    const DevView &d = E->d;
+    const int count = (E->ser_level >= 2 ? 6 : 4) * d.nlay + 1, nch = (d.L + 63) / 64;
+    int nchp2 = 1, width = 1;
+    while (nchp2 < nch) nchp2 <<= 1;
+    while (width < d.L && width < 64) width <<= 1;
+    double *rec = E->ser_rec + E->ser_tstp.size() * (size_t)E->ser_rows * count;
+    const dim3 g((unsigned)nch, (unsigned)((E->ser_rows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
+    const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
+#define SER_GO(kern) do { if (E->dense) hipLaunchKernelGGL(kern<true>, g, b, 0, E->stream, d, E->ser_jlo, E->ser_rows, width, \
+                                                           E->integ_xper, E->integ_yper, map, E->integ_part); \
+                          else hipLaunchKernelGGL(kern<false>, g, b, 0, E->stream, d, E->ser_jlo, E->ser_rows, width, \
+                                                  E->integ_xper, E->integ_yper, map, E->integ_part); } while (0)
+    if (E->ser_level == 1) SER_GO(k_integral_rows); else SER_GO(k_series_rows);
+#undef SER_GO
+    hipLaunchKernelGGL(k_integral_chunks, dim3((unsigned)E->ser_rows), dim3(64), 0, E->stream,
+                       (const double *)E->integ_part, rec, count, nch, nchp2);
+    E->ser_tstp.push_back(tstp);
+}
 template <class CTX>
 static bool launch_mont_all(beom_engine *E) {
     const dim3 g = CTX::grid(E->d, 1), b(BEOM_BLOCK);
@@ -1166,6 +1198,7 @@ static void one_step(beom_engine *E, int tstp, const StepScalars &s, int flt = -
     E->last_tstp = tstp;
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
+    if (!E->ser_by_caller && series_due(E, tstp)) launch_series(E, tstp);
 }
 
 // rows [jlo, jlo+nrows) of hlay,u,v,h_u,h_v  ->  dbuf (device memory, 5*nlay*nrows*(lm+1) doubles); the *2 forms move a second
@@ -1203,6 +1236,17 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
             set_err(errm, errm_len, "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
                     "empty it with beom_download_float_track, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
                     E->flt_stride, held, E->flt_nrec);
+            return -3;
+        }
+    }
+    if (E->ser_level > 0 && !E->ser_by_caller) {      // the series' recorder likewise
+        long long due = 0;
+        for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp) due += tstp % E->ser_stride == 0;
+        const long long held = (long long)E->ser_tstp.size();
+        if (held + due > E->ser_nrec) {
+            set_err(errm, errm_len, "beom_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
+                    "empty it with beom_download_series, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
+                    E->ser_stride, held, E->ser_nrec);
             return -3;
         }
     }
@@ -1421,6 +1465,29 @@ static int ensure_cellmap(beom_engine *E, char *errm, int errm_len) {
     return 0;
 }
 
+// The chunk sums and row sums of up to M rows of `count` entries each: allocated on the first use, again when a later user
+// (the series at level 2) asks for more entries per row.
+static int ensure_integ_scratch(beom_engine *E, int count, char *errm, int errm_len) {
+    if (E->integ_count >= count) return 0;
+    const DevView &d = E->d;
+    const int nch = (d.L + 63) / 64;
+    if (E->integ_part) {
+        HIP_TRY(hipStreamSynchronize(E->stream));
+        for (double **p : {&E->integ_part, &E->integ_rows}) {
+            E->allocs.erase(std::remove(E->allocs.begin(), E->allocs.end(), (void *)*p), E->allocs.end());
+            (void)hipFree(*p);
+            *p = nullptr;
+        }
+        E->integ_count = 0;
+    }
+    HIP_TRY(hipMalloc((void **)&E->integ_part, (size_t)d.M * nch * count * sizeof(double)));
+    E->allocs.push_back(E->integ_part);
+    HIP_TRY(hipMalloc((void **)&E->integ_rows, (size_t)d.M * count * sizeof(double)));
+    E->allocs.push_back(E->integ_rows);
+    E->integ_count = count;
+    return 0;
+}
+
 int beom_integral_rows(beom_handle E, int jlo, int nrows, double *rows, char *errm, int errm_len) {
     if (!E || !rows) { set_err(errm, errm_len, "beom_integral_rows: null argument"); return -1; }
     DevView &d = E->d;
@@ -1429,12 +1496,7 @@ int beom_integral_rows(beom_handle E, int jlo, int nrows, double *rows, char *er
     const int count = 4 * d.nlay + 1, nch = (d.L + 63) / 64, nchp2 = pow2_ceil(nch);
     const int width = std::min(64, pow2_ceil(d.L));
     if (nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "beom_integral_rows: rows of more than %d columns", 64 * 64 * kIntegralMaxGroups); return -4; }
-    if (!E->integ_part) {
-        HIP_TRY(hipMalloc((void **)&E->integ_part, (size_t)d.M * nch * count * sizeof(double)));
-        E->allocs.push_back(E->integ_part);
-        HIP_TRY(hipMalloc((void **)&E->integ_rows, (size_t)d.M * count * sizeof(double)));
-        E->allocs.push_back(E->integ_rows);
-    }
+    if (const int rc = ensure_integ_scratch(E, count, errm, errm_len)) return rc;
     if (const int rc = ensure_cellmap(E, errm, errm_len)) return rc;
     const dim3 g((unsigned)nch, (unsigned)((nrows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
     if (E->dense) hipLaunchKernelGGL(k_integral_rows<true>, g, b, 0, E->stream, d, jlo, nrows, width, E->integ_xper, E->integ_yper,
@@ -1471,6 +1533,73 @@ int beom_integrals(beom_handle E, double *out, char *errm, int errm_len) {
     const int rc = beom_integral_rows(E, 1, M, rows.data(), errm, errm_len);
     if (rc) return rc;
     return beom_integral_combine(rows.data(), M, count, out);
+}
+
+// ---- series of row sums (beom_series.h) ----------------------------------------------------------------------------------
+int beom_series_count(int nlay, int level) { return (level >= 2 ? 6 : 4) * nlay + 1; }
+
+static void series_free(beom_engine *E) {
+    free_list(E->ser_allocs);
+    E->ser_level = 0; E->ser_stride = 1; E->ser_nrec = 0; E->ser_jlo = 1; E->ser_rows = 0; E->ser_by_caller = false;
+    E->ser_rec = nullptr;
+    E->ser_tstp.clear();
+}
+
+// level 0 frees; else a recorder of nrec records of local rows jlo .. jlo+nrows-1.  A failed allocation leaves level 0
+static int series_set(beom_engine *E, const char *who, int level, int stride, int nrec, int jlo, int nrows, bool by_caller,
+                      char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (level < 0 || level > 2 || (level > 0 && (stride < 1 || nrec < 1))) {
+        set_err(errm, errm_len, "%s: level %d, stride %d, %d records (level 0..2, stride >= 1, records >= 1)", who, level, stride, nrec);
+        return -3;
+    }
+    const DevView &d = E->d;
+    if (level > 0 && (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M)) { set_err(errm, errm_len, "%s: rows %d..%d outside 1..%d", who, jlo, jlo + nrows - 1, d.M); return -3; }
+    if (level > 0 && pow2_ceil((d.L + 63) / 64) / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    series_free(E);
+    if (level == 0) return 0;
+    const int count = beom_series_count(d.nlay, level);
+    int rc = ensure_integ_scratch(E, count, errm, errm_len);
+    if (!rc) rc = ensure_cellmap(E, errm, errm_len);
+    if (!rc) rc = alloc_aligned(E, E->ser_allocs, &E->ser_rec, (size_t)nrec * nrows * count, errm, errm_len);
+    if (rc) { series_free(E); return rc; }
+    E->ser_level = level; E->ser_stride = stride; E->ser_nrec = nrec; E->ser_jlo = jlo; E->ser_rows = nrows; E->ser_by_caller = by_caller;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int beom_set_series(beom_handle E, int level, int stride, int nrec, char *errm, int errm_len) {
+    return series_set(E, "beom_set_series", level, stride, nrec, 1, E ? E->d.M : 0, false, errm, errm_len);
+}
+
+int beom_band_set_series(beom_handle E, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len) {
+    return series_set(E, "beom_band_set_series", level, stride, nrec, jlo, nrows, true, errm, errm_len);
+}
+
+int beom_sample_series(beom_handle E) {
+    if (!E) return -1;
+    if (E->ser_level < 1 || (int)E->ser_tstp.size() >= E->ser_nrec) return -3;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    launch_series(E, E->last_tstp);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int beom_download_series(beom_handle E, double *rows, int *tstp, int *count, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->ser_level < 1) { set_err(errm, errm_len, "beom_download_series: the handle keeps no series (beom_set_series)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t n = E->ser_tstp.size(), per = (size_t)E->ser_rows * beom_series_count(E->d.nlay, E->ser_level);
+    if (rows && n) {
+        HIP_TRY(hipMemcpyAsync(rows, E->ser_rec, n * per * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+        HIP_TRY(hipStreamSynchronize(E->stream));
+        HIP_TRY(hipGetLastError());
+    }
+    if (tstp) std::copy(E->ser_tstp.begin(), E->ser_tstp.end(), tstp);
+    if (count) *count = (int)n;
+    E->ser_tstp.clear();
+    return 0;
 }
 
 // ---- passive tracers (beom_tracers.h) -----------------------------------------------------------------------------------
@@ -1952,6 +2081,8 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_moments")) return E->tmom.level;
     if (!strcmp(what, "tracer_moment_samples")) return (int)std::min<long long>(E->tmom.count, 2000000000ll);
     if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom.launches, 2000000000ll);     // all calls so far
+    if (!strcmp(what, "series")) return E->ser_level;
+    if (!strcmp(what, "series_records")) return (int)E->ser_tstp.size();
     if (!strcmp(what, "moments")) return E->mom.level;
     if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom.count, 2000000000ll);
     if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom.launches, 2000000000ll);     // all calls so far

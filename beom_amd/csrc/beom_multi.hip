@@ -281,6 +281,10 @@ struct beom_multi {
     // sample is still owed (0 = none) is taken where the main streams next join the exchange
     struct Moments { int level = 0, stride = 1, due = 0; };
     Moments mom, tmom;             // (tmom: the tracer moments likewise, beom_multi_set_tracer_moments)
+    // series kept by every band over its owned rows (beom_multi_set_series): the record a step left owing is taken where the
+    // moments' sample is; the steps of the records held (every band holds as many)
+    struct Series { int level = 0, stride = 1, nrec = 0, due = 0; std::vector<int> tstp; };
+    Series ser;
     // Lagrangian floats on the bands (beom_multi_set_floats): every band holds all nflt slots; flt_mode is the float launch
     // owed where the main streams next join the exchange (0 none, 1 stage 1, 3 stage 2 + stage 1 of the next step)
     long long nflt = 0;
@@ -1352,6 +1356,56 @@ int beom_multi_integral_rows_local(beom_multi_handle M, int *own0, int *own1, do
     return band_integral_rows(M, 0, rows, errm, errm_len);
 }
 
+// Series (beom_series.h) of a frame cut into bands: a band owns whole rows, so its records' rows are the frame's.
+int beom_multi_set_series(beom_multi_handle M, int level, int stride, int nrec, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_series: an earlier step failed half way; destroy the handle"); return -30; }
+    if (level < 0 || level > 2 || (level > 0 && (stride < 1 || nrec < 1))) {
+        m_err(errm, errm_len, "beom_multi_set_series: level %d, stride %d, %d records (level 0..2, stride >= 1, records >= 1)", level, stride, nrec);
+        return -3;
+    }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_set_series: a handle that holds one band's window keeps no series (its rows are nowhere assembled); use a handle created from the global arrays"); return -6; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    M->ser = {};
+    int rc = 0;
+    for (int k = 0; k < M->n && !rc; ++k) {
+        const Band &s = M->band[k];
+        rc = multi_whole(M) ? beom_set_series(M->eng[k], level, stride, nrec, errm, errm_len)
+                            : beom_band_set_series(M->eng[k], level, stride, nrec, s.gs + 1, s.nown(), errm, errm_len);
+    }
+    if (rc) {                           // all bands or none
+        for (int k = 0; k < M->n; ++k) (void)beom_set_series(M->eng[k], 0, 1, 1, nullptr, 0);
+        return rc;
+    }
+    M->ser.level = level; M->ser.stride = stride; M->ser.nrec = nrec;
+    return 0;
+}
+
+int beom_multi_download_series(beom_multi_handle M, double *rows, int *tstp, int *count, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_series: this handle holds a window and keeps no series"); return -6; }
+    if (M->ser.level < 1) { m_err(errm, errm_len, "beom_multi_download_series: the handle keeps no series (beom_multi_set_series)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (multi_whole(M)) return beom_download_series(M->eng[0], rows, tstp, count, errm, errm_len);
+    const size_t n = M->ser.tstp.size(), cnt = (size_t)beom_series_count(M->P.nlay, M->ser.level), Mg = (size_t)M->P.mm + 1;
+    // (a ring's orphan row mm+1 duplicates row 1: every sum of it is +0, the companion frame is not asked)
+    if (rows) std::fill(rows, rows + n * Mg * cnt, 0.0);
+    for (int k = 0; k < M->n; ++k) {
+        const Band &s = M->band[k];
+        const size_t per = (size_t)s.nown() * cnt;
+        std::vector<double> a(rows ? n * per : 0);
+        int held = 0;
+        M_RC(beom_download_series(M->eng[k], rows ? ptr(a) : nullptr, nullptr, &held, errm, errm_len));
+        if ((size_t)held != n) { m_err(errm, errm_len, "beom_multi_download_series: band %d holds %d records, the handle %zu", s.index, held, n); return -3; }
+        for (size_t r = 0; r < n && rows; ++r)
+            std::copy(a.begin() + r * per, a.begin() + (r + 1) * per, rows + (r * Mg + (size_t)(s.own0 - 1)) * cnt);
+    }
+    if (tstp) std::copy(M->ser.tstp.begin(), M->ser.tstp.end(), tstp);
+    if (count) *count = (int)n;
+    M->ser.tstp.clear();
+    return 0;
+}
+
 int beom_multi_upload_local(beom_multi_handle M, const beom_state *win, const beom_state *orphan, char *errm, int errm_len) {
     if (!M || !win) { m_err(errm, errm_len, "null argument"); return -1; }
     if (!M->local_mode) { m_err(errm, errm_len, "beom_multi_upload_local: this handle was created from global arrays"); return -3; }
@@ -1427,6 +1481,12 @@ static int multi_sample_due(beom_multi *M, char *errm, int errm_len) {
         for (int k = 0; k < M->n && due; ++k)
             if (K->sample(M->eng[k])) { m_err(errm, errm_len, K->sample_failed, M->band[k].index, due); return -3; }
         due = 0;
+    }
+    if (M->ser.due) {
+        for (int k = 0; k < M->n; ++k)
+            if (beom_sample_series(M->eng[k])) { m_err(errm, errm_len, "beom_sample_series failed on band %d (step %d)", M->band[k].index, M->ser.due); return -3; }
+        M->ser.tstp.push_back(M->ser.due);
+        M->ser.due = 0;
     }
     return 0;
 }
@@ -1573,6 +1633,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
     }
     for (beom_multi::Moments *m : {&M->mom, &M->tmom})
         if (m->level > 0 && t % m->stride == 0) m->due = t;
+    if (M->ser.level > 0 && t % M->ser.stride == 0) M->ser.due = t;
     if (M->nflt > 0) M->flt_mode = 3;
     return 0;
 }
@@ -1586,6 +1647,17 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
     if (tstp_first < 1 || nsteps < 0 || n_3d < 1) { m_err(errm, errm_len, "beom_multi_step: bad arguments"); return -3; }
     if (M->nb == 1 && !M->ring) return beom_step(M->eng[0], tstp_first, nsteps, tres, dtd8, dt_r, rsta, n_3d, errm, errm_len);
     if (M->nflt > 0 && !M->flt_ready) { m_err(errm, errm_len, "beom_multi_step: the handle's %lld floats have no positions yet (beom_multi_upload_floats)", M->nflt); return -3; }
+    if (M->ser.level > 0) {             // the recorder must hold every record of the call: refused before anything is launched
+        long long due = 0;
+        for (int t = tstp_first; t < tstp_first + nsteps; ++t) due += t % M->ser.stride == 0;
+        const long long held = (long long)M->ser.tstp.size();
+        if (held + due > M->ser.nrec) {
+            m_err(errm, errm_len, "beom_multi_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
+                  "empty it with beom_multi_download_series, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
+                  M->ser.stride, held, M->ser.nrec);
+            return -3;
+        }
+    }
     M->flt_mode = (M->nflt > 0 && nsteps > 0) ? 1 : 0;          // stage 1 alone in front of the call's first step
     for (int t = tstp_first; t < tstp_first + nsteps; ++t) {
         const int rc = multi_one_step(M, t, tres, dtd8, dt_r, rsta, n_3d, errm, errm_len);
@@ -1596,7 +1668,7 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
             return rc;
         }
     }
-    if (M->mom.due || M->tmom.due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
+    if (M->mom.due || M->tmom.due || M->ser.due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
         M_RC(multi_join_exchange(M, errm, errm_len));
         M_RC(multi_sample_due(M, errm, errm_len));
         if (M->flt_mode) {

@@ -458,6 +458,41 @@ int beom_integral_combine(const double *rows, int nrows_total, int count, double
 /* = beom_integral_rows(1..mm+1) + beom_integral_combine */
 int beom_integrals(beom_handle h, double *out, char *errm, int errm_len);
 
+/* ---- Series: a record of the row sums per sampled step, kept on the device (no reference routine).  What beom_integral_rows
+ * returns for one moment, recorded behind every stride-th step of the K-step loop without a host copy or a synchronisation:
+ * a time-latitude diagram of volume, energy, enstrophy and circulation and, at level 2, of the layer transports.
+ * One record is rows[(j-1)*cnt + k] for the handle's rows j = 1..M (M = mm+1), cnt = beom_series_count(nlay, level):
+ *   k = 0 .. 4*nlay        the quantities of beom_integral_rows in its layout: vol, ke, ens, circ per layer, then eta2
+ *   k = 4*nlay + 1 + (l-1) level 2: tu[l] = sum over i of h_u(i, j, l)
+ *   k = 5*nlay + 1 + (l-1) level 2: tv[l] = sum over i of h_v(i, j, l)
+ * h_u, h_v are the stored transport arrays (thickness * velocity through the W resp. S face of the cell, m^2/s; update_u,
+ * update_v, private_mod.f95:1492, 1578) as the step leaves them: with a rigid lid whatever the lid step rebuilt.  dl * tv[l]
+ * is the volume transport of layer l through the south faces of row j; accumulated over layers, the overturning
+ * streamfunction in layer coordinates.  Masking is the integrals' live rule: a position without a packed cell, the duplicated
+ * column lm+1 of a frame periodic in x and row mm+1 of one periodic in y contribute +0.0.
+ * Order of summation: the integrals' contract, unchanged.  Each row goes through the pairwise tree over the aligned column
+ * index, padded with +0.0 to a power of two.  A level-1 record equals beom_integral_rows(1..M) of that moment bit for bit,
+ * the first 4*nlay + 1 entries of a level-2 record likewise, and beom_integral_combine of a record equals beom_integrals.  The
+ * bits do not depend on the handle kind, the tile geometry or how the frame is cut into bands.
+ * A record is written behind every step with tstp % stride == 0, where the moments' sample sits (it reads the fields as
+ * beom_download_state would return them after that step), straight into slot `count` of a device buffer [nrec][M][cnt].  The
+ * host keeps the step numbers.  beom_step refuses with -3, before launching anything, a call whose steps would overflow the
+ * recorder.  beom_sample_series: one record by hand of the fields as they stand, under the number of the handle's last step;
+ * -3 on a full recorder or without a series.  beom_download_series copies the filled records (rows[n][M][cnt], oldest first)
+ * and their steps, then sets the count to 0; any of rows, tstp, count may be NULL; -3 without a series.  Uploads of state
+ * do not empty the recorder.  beom_set_series: level 0 frees (stride and nrec are then not looked at); other arguments
+ * reallocate and empty; between steps only; -3 for a level outside 0..2, stride < 1 or nrec < 1; -4 for rows too long for
+ * the integrals; a failed allocation leaves the handle without a series and returns the allocator's code with a message.
+ * Every single handle keeps a series: dense, embedded, the table path, variant = 1, rigid lid, svis > 0, open boundaries.
+ * beom_info: "series" (the level), "series_records" (records held).  beom_band_set_series is the band-side piece
+ * beom_multi_set_series is built from: the recorder covers local rows jlo..jlo+nrows-1 only and beom_step takes no record
+ * by itself; the caller places every record with beom_sample_series. */
+int beom_series_count(int nlay, int level);      /* level 1: 4*nlay + 1;  level 2: 6*nlay + 1 */
+int beom_set_series(beom_handle h, int level, int stride, int nrec, char *errm, int errm_len);
+int beom_sample_series(beom_handle h);
+int beom_download_series(beom_handle h, double *rows, int *tstp, int *count, char *errm, int errm_len);
+int beom_band_set_series(beom_handle h, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len);
+
 /* ---- Several GPUs: the frame cut into bands of rows (SURVEY §8b "Threading", §8e) -------------
  * No reference counterpart (the reference is OpenMP only).  The whole DENSE frame (ndeg = (lm+1)(mm+1))
  * is cut into bands of rows, one band per HIP device, each an ordinary slab handle with 4 ghost rows
@@ -686,6 +721,16 @@ int beom_multi_integrals(beom_multi_handle m, double *out, char *errm, int errm_
 /* one band per process: the row sums of this band's owned rows own0..own1 (rows[(j-own0)*count + k]); the caller gathers the
  * bands' rows in global row order (row mm+1 of a frame periodic in y: zeros) and combines with beom_integral_combine */
 int beom_multi_integral_rows_local(beom_multi_handle m, int *own0, int *own1, double *rows, char *errm, int errm_len);
+
+/* Series (see beom_set_series).  Global-array handles: every band records its OWNED rows; the record is taken on the band's
+ * main stream behind the wait for that step's ghost rows, where the tracer-moment sample sits, so the S neighbours of a
+ * band's first owned row are landed ghosts; cut steps stay cut.  beom_multi_step refuses with -3, before launching anything,
+ * a call whose steps would overflow the recorder.  beom_multi_download_series places the bands' rows at their global rows:
+ * rows[n][mm+1][cnt]; row mm+1 of a frame periodic in y is the duplicated row, all +0.0 (the companion frame is not asked).
+ * Chains with and without land, and rings.  -6 for handles that hold one band's window (beom_multi_create_local*): their
+ * rows are nowhere assembled.  One band that is the whole frame forwards to beom_set_series etc. */
+int beom_multi_set_series(beom_multi_handle m, int level, int stride, int nrec, char *errm, int errm_len);
+int beom_multi_download_series(beom_multi_handle m, double *rows, int *tstp, int *count, char *errm, int errm_len);
 
 #ifdef __cplusplus
 }

@@ -787,7 +787,9 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
         """beom_info: "stress_folded" (the last step formed its stress inside the momentum sweep: tt3d, tb3d, tu3d are
         then not kept current), "tile_rows", "biharm_tiled" (1: the handle's biharmonic viscosity, svis > 0, runs as the tiled
         sweep; 0 on the table path and with svis = 0), "uv_fused" (1: the last step's momentum ran as the fused u+v sweep),
-        "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did), "tracers", "tracer_scheme" (1 upstream, 2 limited), "floats",
+        "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did),
+        "vel_targets_zero" (1: the handle's velocity targets fnud[IX_U], fnud[IX_V] are +0 bit for bit, so the momentum sweeps
+        never fetch them for a lane whose velocity is an exact zero), "tracers", "tracer_scheme" (1 upstream, 2 limited), "floats",
         "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
         "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
         "tracer_moment_launches", "series" (the series' level), "series_records" (records its recorder holds)."""

@@ -8,6 +8,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/beom_hip.h"
@@ -244,6 +245,20 @@ inline std::vector<unsigned char> plan_nudging_tiles(const Layout &lay, int L, i
     //  beach 8192x1024x8 -2 % per step; a frame nudged over a third of its tiles goes without, wind case +1.5 % with it)
     if (3 * flagged > ngt.size()) ngt.clear();
     return ngt;
+}
+
+// Are the caller's velocity targets fnud(0:ndeg, nlay, ix_u | ix_v) +0 bit for bit: every layer, slots 0..ndeg, read as
+// 64-bit words?  (DevView::vel_targets_zero.)  A -0.0 target counts as not zero: (-0)*0 = -0 where uv_core would put +0;
+// so do a denormal and a NaN.  fnud(0:ndeg, nlay, 3): the two components are the last 2 * nlay * n1h words.
+inline int vel_targets_zero(const double *fnud, size_t n1h, size_t nlay) {
+    if (!fnud) return 0;
+    const double *p = fnud + nlay * n1h;
+    for (size_t k = 0; k < 2 * nlay * n1h; ++k) {
+        uint64_t w;
+        std::memcpy(&w, p + k, sizeof w);
+        if (w != 0) return 0;
+    }
+    return 1;
 }
 
 // The rigid lid's pressure sweep as a pipeline of wavefronts (k_rgld_gs_front) and the terms of its right-hand side

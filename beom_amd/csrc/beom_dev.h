@@ -85,6 +85,12 @@ struct DevView {
     double i_dl, i_gr, i_ns, i_r0, i_r1, i_rn[BEOM_MAX_LAYERS];
     // which optional terms are live (wave-uniform branches)
     int has_hdot, has_tide, has_bodf, has_nudg, has_stress, has_wind, has_hto;
+    // the velocity targets fnud(:, :, ix_u | ix_v) of the caller are +0 bit for bit in every slot (vel_targets_zero,
+    // beom_dense_host.h): lanes of uv_core whose new velocity is an exact zero then know their target without fetching it.
+    // uv_core reads the fact from fnud_vel = fnud(:, :, ix_u), null where the flag is set: the pointer takes the scalar
+    // registers that fnud held there, a flag next to fnud one more in kernels that spill scalars as they are
+    int vel_targets_zero;
+    const double *fnud_vel;
     // distribute_stress inside the fused momentum sweep (uv_core; set per launch by the engine: ocrp = 0, a stress refresh on
     // every step, steps > 3): the wind stress at real cells only (0 in the sentinel and in every slot that is no cell, as
     // tt3d is), bottom / top drag switched on, the densities of the top and the bottom layer

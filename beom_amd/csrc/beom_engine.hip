@@ -352,6 +352,7 @@ void fill_view(DevView &d, const beom_params &prm, const beom_statics &st) {
     d.has_bodf = any_nonzero(st.bodf, 2 * nl);
     d.has_nudg = any_nonzero(st.nudg, 3 * n1h);
     d.has_hto = any_nonzero(st.h_to, n1h);
+    d.vel_targets_zero = beom_dense::vel_targets_zero(st.fnud, n1h, nl);
     d.rho_top = prm.rhon[0]; d.rho_bot = prm.rhon[nl - 1];
 }
 
@@ -412,6 +413,7 @@ int upload_statics(beom_engine *E, const beom_dense::Layout &lay, const beom_den
     up(&d.fcor, st.fcor, 1); up(&d.h_th, st.h_th, 1); up(&d.h_to, st.h_to, 1);
     up(&d.nudg, st.nudg, 3); up(&d.fnud, st.fnud, 3 * nl); up(&d.hdot, st.hdot, nl);
     up(&d.tide, st.tide, 3, 2); up(&d.taus, st.taus, 2);
+    d.fnud_vel = (rc || d.vel_targets_zero) ? nullptr : d.fnud + d.n1 * (long long)d.nlay;
     // the wind stress as tt3d holds it: at real cells only (distribute_stress writes cells 1..ndeg, :1945-1966; index 0 and
     // every device slot that is no cell stay +0)
     std::vector<double> tc(2 * n1h, 0.0);
@@ -2072,6 +2074,7 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "uv_fused")) return E->last_uv_fused ? 1 : 0;
     if (!strcmp(what, "mont_history")) return E->last_mont_hist ? 1 : 0;
     if (!strcmp(what, "plain_sweeps")) return E->last_plain;
+    if (!strcmp(what, "vel_targets_zero")) return E->d.vel_targets_zero;
     if (!strcmp(what, "tracers")) return E->ntrc;
     if (!strcmp(what, "tracer_scheme")) return E->trc_scheme;
     if (!strcmp(what, "floats")) return (int)std::min<long long>(E->nflt, 2000000000ll);

@@ -13,6 +13,7 @@
 
 #define LL(a, ip, il) (a)[(long long)(ip) + d.n1 * (long long)((il) - 1)]
 #define FNUD_(ip, il, iv) d.fnud[(long long)(ip) + d.n1 * ((long long)((il) - 1) + (long long)d.nlay * ((iv) - 1))]
+#define FNUDV_(ip, il, iv) d.fnud_vel[(long long)(ip) + d.n1 * ((long long)((il) - 1) + (long long)d.nlay * ((iv) - 2))]   // iv = 2 (u), 3 (v)
 #define NUDG_(ip, iv) d.nudg[(long long)(ip) + d.n1 * ((iv) - 1)]
 #define TIDE_(m, ip, iv) d.tide[((m) - 1) + 2 * ((long long)(ip) + d.n1 * ((iv) - 1))]
 #define T3_(a, ip, id, il) (a)[(long long)(ip) + d.n1 * ((long long)((id) - 1) + 2 * (long long)((il) - 1))]
@@ -776,9 +777,15 @@ __device__ __forceinline__ double uv_core(const C &c, const DevView &d, int ilay
     vold = vold + rhsi * mask * d.dt;
     // Rate zero (or no nudging at all): the reference still evaluates vfor*0 + vold*(1-0) = (+-0) + vold, i.e. vold
     // unless vold is an exact zero, so only those (rare) lanes go through the full expression.
-    if ((!PLAIN && f_ng != 0.0) || vold == 0.0) {
+    // Those lanes are whole workgroups where a frame is still at rest (a third of the headline frame), and the target is a
+    // double per lane from a full-size array.  Where every velocity target is +0 bit for bit (DevView::vel_targets_zero:
+    // d.fnud_vel is null) the target is known without the fetch; in the plain form vfor then stays +0 through -+ (+0) and
+    // + (+0), and (+0)*0 + (+-0)*(1-0) = (+0) + (+-0) = +0 whatever the sign of vold was.
+    if (PLAIN && vold == 0.0 && !d.fnud_vel) {
+        vold = 0.0;
+    } else if ((!PLAIN && f_ng != 0.0) || vold == 0.0) {
         const double i__hh = 1.0 / (hcen + 1.0 - mask);
-        double vfor = FNUD_(ipnt, ilay, IV);
+        double vfor = d.fnud_vel ? FNUDV_(ipnt, ilay, IV) : 0.0;
         if (SF) {                              // tt3d = taus * fraction (1 in the top layer, 0 below), formed here (see above)
             const double lt = ilay == 1 ? 1.0 : 0.0;
             const double t0 = d.has_wind ? d.taus_cells[ipnt + d.n1 * (IO - 1)] * lt : 0.0, tb_ = d.has_wind ? d.taus_cells[cb + d.n1 * (IO - 1)] * lt : 0.0;

@@ -227,7 +227,9 @@ int beom_set_option(beom_handle h, const char *name, int value);
  * private_mod.f95:2508-2599) runs as the tiled sweep k_biharm_tiled (1: every dense or embedded handle with svis > 0) or
  * not (0: the table kernels of a packed handle, and every handle with svis = 0); "uv_fused" = the last step's update_u and
  * update_v ran as the fused sweep (1) or as two sweeps (0; 0 before the first step); "plain_sweeps" = which sweeps of the
- * last step ran their plain form: bit 0 (1) the fused update_u/update_v sweep, bit 1 (2) the fused Montgomery sweep. */
+ * last step ran their plain form: bit 0 (1) the fused update_u/update_v sweep, bit 1 (2) the fused Montgomery sweep;
+ * "vel_targets_zero" = the velocity targets fnud(0:ndeg, nlay, ix_u | ix_v) given to beom_create are +0 bit for bit in every
+ * slot (1: update_u / update_v never fetch the target of a point whose new velocity is an exact zero) or not (0). */
 int beom_info(beom_handle h, const char *what);
 
 /* Run all launches of this handle on the caller's HIP stream (e.g. the stream a

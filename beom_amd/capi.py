@@ -97,7 +97,7 @@ def source_hash() -> str:
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
     for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_dense_host.h",
-               "beom_bands_host.h", os.path.join("..", "..", "include", "beom_hip.h")):
+               "beom_bands_host.h", "beom_plan.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -24,6 +25,10 @@
 #include "beom_moments.h"
 #include "beom_tracer_moments.h"
 #include "beom_dense_host.h"
+#include "beom_plan.h"
+
+using beom_plan::StepFacts;
+using beom_plan::StepPlan;
 
 namespace {
 
@@ -146,7 +151,7 @@ struct beom_engine {
     int lid_last = 0;                  // sweeps the last solve kept
     int profile_stride = 1;            // option "profile_stride"
     bool profile_rotate = false;       // option "profile_rotate"
-    bool split_prod = false;           // split steps: part 1's Montgomery sweep left the viscous products for parts 2 and 3
+    StepPlan split{};                  // split steps: the plan part 1 made of its step (tstp 0: none yet); parts 2 and 3 run from it
     bool tile4 = false;                // the tiled sweeps run the 64 x 4 geometry (frames of one or two rounds of workgroups)
     // History from Montgomery (option "mont_history", default on): d.mont rotates through four buffers, once
     // per step (rotate_mont), and the fused u+v sweep re-forms dmx / dmy from the three kept levels instead of reading them.
@@ -157,7 +162,7 @@ struct beom_engine {
     bool last_mont_hist = false;       // the last step ran the new form (beom_info "mont_history")
     // Plain sweeps (option "plain_sweeps", default on): a launch of the fused u+v sweep resp. of the Montgomery
     // sweep whose handle has none of the optional forcing takes the instantiation with that forcing compiled out.  Decided
-    // per launch from the flags of the moment (keep_diag, uploaded stress and options change between steps).
+    // per step by plan_step (beom_plan.h) from the facts of the moment (keep_diag, uploaded stress and options change between steps).
     bool plain_sweeps = true;
     int last_plain = 0;                // bit 0: the last step's u+v sweep ran plain, bit 1: its Montgomery sweep (beom_info "plain_sweeps")
     // conservation integrals (beom_integral_rows): chunk sums and row sums of up to M rows, allocated on the first call; on
@@ -767,40 +772,48 @@ static int leave_mont_history(beom_engine *E) {
         else hipLaunchKernelGGL(KERNEL_G, CellGather::grid(E->d, (nz)), dim3(BEOM_BLOCK), 0, E->stream, __VA_ARGS__);         \
     } while (0)
 
+// Run-time values as template arguments: pick(f, a, b, ...) calls the generic lambda f with one std::bool_constant per
+// flag; pick_int<FROM, TO>(v, f) calls f with the std::integral_constant of v, trying FROM first and stepping towards TO
+// (a v outside the range counts as TO).  f names the kernel; what it discards with `if constexpr` is never instantiated.
+// The kernels come out in the order tried, true before false: the code object keeps the layout the ladders of old gave it.
+template <class F>
+static void pick(F &&f) { f(); }
+template <class F, class... R>
+static void pick(F &&f, bool b, R... rest) {
+    if (b) pick([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else pick([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <int FROM, int TO, class F>
+static void pick_int(int v, F &&f) {
+    if (FROM == TO || v == FROM) f(std::integral_constant<int, FROM>{});
+    else if constexpr (FROM != TO) pick_int<FROM + (TO > FROM ? 1 : -1), TO>(v, f);
+}
+
 static void launch_rebuild(beom_engine *E) {
     LAUNCH_CTX(k_rebuild_fluxes<CellGather>, k_rebuild_fluxes<CellDense>, E->d.nlay, E->d);
 }
+// FORCE of k_update_h and of the tracer sweeps: 0 = no relaxation, 1 = nudging, 2 = nudging and tide
+static int forcing(const DevView &d) { return d.has_nudg ? (d.has_tide ? 2 : 1) : 0; }
 static void launch_h(beom_engine *E, double gene, double ramp, double ctim, bool rotate = true) {
     // variant 1 couples layers inside a cell -> one thread walks nlay..1; variant 0: layer = blockIdx.y
     int nz = (E->d.variant == 1) ? 1 : E->d.nlay;
     // nudged frames: one thread walks the layers of its cell, so the cell's relaxation rate is read once instead of once per
     // layer (carrier beach 8192x1024x8: 802 -> 747 us per launch, sill 4096x512x4: 89 -> 83; same-box A/B, round 3)
     if (E->d.has_nudg) nz = 1;
-    if (E->d.has_nudg && E->d.has_tide) LAUNCH_CTX((k_update_h<CellGather, 2>), (k_update_h<CellDense, 2>), nz, E->d, gene, ramp, ctim, 0);
-    else if (E->d.has_nudg) LAUNCH_CTX((k_update_h<CellGather, 1>), (k_update_h<CellDense, 1>), nz, E->d, gene, ramp, ctim, 0);
-    else LAUNCH_CTX((k_update_h<CellGather, 0>), (k_update_h<CellDense, 0>), nz, E->d, gene, ramp, ctim, 0);
+    pick_int<2, 0>(forcing(E->d), [&](auto fo) { LAUNCH_CTX((k_update_h<CellGather, fo>), (k_update_h<CellDense, fo>), nz, E->d, gene, ramp, ctim, 0); });
     if (rotate) rot2(E->d.rs);
-}
-// scheme 2 (beom_tracers_lim.h): the tiled kernel in the handle's tile geometry, or the table path
-template <int FORCE>
-static void launch_tracers_lim(beom_engine *E, const TrcView &tv, double gene, double ramp, double ctim) {
-    if (!E->dense) hipLaunchKernelGGL((k_tracers_lim<CellGather, FORCE>), CellGather::grid(E->d, E->d.nlay), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
-    else if (E->tile4) hipLaunchKernelGGL((k_tracers_lim<TrcTiled<1>, FORCE>), tracers_lim_grid<1>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
-    else hipLaunchKernelGGL((k_tracers_lim<TrcTiled<2>, FORCE>), tracers_lim_grid<2>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
 }
 // the tracer sweep of a step (beom_tracers.h): all tracers in one launch, in front of the step's update_h
 static void launch_tracers(beom_engine *E, double gene, double ramp, double ctim) {
     TrcView tv{E->ntrc, E->trc_ctrg ? 1 : 0, E->trc_q, E->trc_q_alt, E->trc_rq[0], E->trc_rq[1], E->trc_ctrg};
     const int nz = E->d.nlay;
-    if (E->trc_scheme == 2) {
-        const int force = E->d.has_nudg ? (E->d.has_tide ? 2 : 1) : 0;
-        if (force == 2) launch_tracers_lim<2>(E, tv, gene, ramp, ctim);
-        else if (force == 1) launch_tracers_lim<1>(E, tv, gene, ramp, ctim);
-        else launch_tracers_lim<0>(E, tv, gene, ramp, ctim);
-    }
-    else if (E->d.has_nudg && E->d.has_tide) LAUNCH_CTX((k_tracers<CellGather, 2>), (k_tracers<CellDense, 2>), nz, E->d, tv, gene, ramp, ctim);
-    else if (E->d.has_nudg) LAUNCH_CTX((k_tracers<CellGather, 1>), (k_tracers<CellDense, 1>), nz, E->d, tv, gene, ramp, ctim);
-    else LAUNCH_CTX((k_tracers<CellGather, 0>), (k_tracers<CellDense, 0>), nz, E->d, tv, gene, ramp, ctim);
+    // scheme 2 (beom_tracers_lim.h): the tiled kernel in the handle's tile geometry, or the table path
+    if (E->trc_scheme == 2) pick_int<2, 0>(forcing(E->d), [&](auto fo) {
+        if (!E->dense) hipLaunchKernelGGL((k_tracers_lim<CellGather, fo>), CellGather::grid(E->d, nz), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
+        else if (E->tile4) hipLaunchKernelGGL((k_tracers_lim<TrcTiled<1>, fo>), tracers_lim_grid<1>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
+        else hipLaunchKernelGGL((k_tracers_lim<TrcTiled<2>, fo>), tracers_lim_grid<2>(E->d), dim3(BEOM_BLOCK), 0, E->stream, E->d, tv, gene, ramp, ctim);
+    });
+    else pick_int<2, 0>(forcing(E->d), [&](auto fo) { LAUNCH_CTX((k_tracers<CellGather, fo>), (k_tracers<CellDense, fo>), nz, E->d, tv, gene, ramp, ctim); });
     swp(E->trc_q, E->trc_q_alt);
     rot2(E->trc_rq);
 }
@@ -816,17 +829,15 @@ static void launch_floats(beom_engine *E, int mode, double *rec) {
     if (E->flt_band) {                 // a band: the frame's wraps and rows, not the window's
         f.fmm = E->flt_fmm; f.xper = E->flt_xper; f.yper = E->flt_yper; f.cellmap = nullptr;
         const dim3 g((unsigned)((E->nflt + BEOM_BLOCK - 1) / BEOM_BLOCK)), b(BEOM_BLOCK);
-        if (mode == 1) hipLaunchKernelGGL(k_floats_band<1>, g, b, 0, E->stream, d, f, E->flt_fb);
-        else if (mode == 2) hipLaunchKernelGGL(k_floats_band<2>, g, b, 0, E->stream, d, f, E->flt_fb);
-        else hipLaunchKernelGGL(k_floats_band<3>, g, b, 0, E->stream, d, f, E->flt_fb);
+        pick_int<1, 3>(mode, [&](auto m) { hipLaunchKernelGGL(k_floats_band<m>, g, b, 0, E->stream, d, f, E->flt_fb); });
         ++E->flt_launches;
         return;
     }
     const dim3 g((unsigned)((E->nflt + BEOM_BLOCK - 1) / BEOM_BLOCK)), b(BEOM_BLOCK);
-#define FLT_GO(m) do { if (E->dense) hipLaunchKernelGGL((k_floats<CellDense, m>), g, b, 0, E->stream, d, f); \
-                       else hipLaunchKernelGGL((k_floats<CellGather, m>), g, b, 0, E->stream, d, f); } while (0)
-    if (mode == 1) FLT_GO(1); else if (mode == 2) FLT_GO(2); else FLT_GO(3);
-#undef FLT_GO
+    pick_int<1, 3>(mode, [&](auto m) {
+        if (E->dense) hipLaunchKernelGGL((k_floats<CellDense, m>), g, b, 0, E->stream, d, f);
+        else hipLaunchKernelGGL((k_floats<CellGather, m>), g, b, 0, E->stream, d, f);
+    });
     ++E->flt_launches;
 }
 // stage 2 of step tstp (then stage 1 of the next step if `then_stage1`), with the step's record if it is due
@@ -846,11 +857,9 @@ static void launch_moments(beom_engine *E, int tstp) {
                        s[0], s[1], s[2], s[3], s[4], q[0], q[1], q[2], q[3], q[4]};
     const long long pairs = (m.n - 1) / 2;
     const dim3 g((unsigned)std::max<long long>(1, std::min<long long>((pairs + BEOM_BLOCK - 1) / BEOM_BLOCK, 2048))), b(BEOM_BLOCK);
-    const bool first = E->mom.count == 0;
-#define MOM_GO(lv) do { if (first) hipLaunchKernelGGL((k_moments<lv, true>), g, b, 0, E->stream, m); \
-                        else hipLaunchKernelGGL((k_moments<lv, false>), g, b, 0, E->stream, m); } while (0)
-    if (E->mom.level == 1) MOM_GO(1); else if (E->mom.level == 2) MOM_GO(2); else MOM_GO(3);
-#undef MOM_GO
+    pick_int<1, 3>(E->mom.level, [&](auto lv) {
+        pick([&](auto first) { hipLaunchKernelGGL((k_moments<lv, first>), g, b, 0, E->stream, m); }, E->mom.count == 0);
+    });
     accum_note_sample(E->mom, tstp);
 }
 // one sample of the tracer moments (beom_tracer_moments.h) of q, hlay, h_u, h_v as they stand, recorded under step tstp
@@ -858,11 +867,10 @@ static void launch_tracer_moments(beom_engine *E, int tstp) {
     double *const *r = E->tmom.ref, *const *s = E->tmom.sum;
     const TrcMomentView m{E->ntrc, E->trc_q, r[0], r[1], r[2], r[3], s[0], s[1], s[2], s[3], E->tmom.sq[0]};
     const int nz = E->d.nlay;
-    const bool first = E->tmom.count == 0;
-#define TMOM_GO(lv) do { if (first) LAUNCH_CTX((k_tracer_moments<CellGather, lv, true>), (k_tracer_moments<CellDense, lv, true>), nz, E->d, m); \
-                         else LAUNCH_CTX((k_tracer_moments<CellGather, lv, false>), (k_tracer_moments<CellDense, lv, false>), nz, E->d, m); } while (0)
-    if (E->tmom.level == 1) TMOM_GO(1); else if (E->tmom.level == 2) TMOM_GO(2); else TMOM_GO(3);
-#undef TMOM_GO
+    pick_int<1, 3>(E->tmom.level, [&](auto lv) {
+        pick([&](auto first) { LAUNCH_CTX((k_tracer_moments<CellGather, lv, first>), (k_tracer_moments<CellDense, lv, first>), nz, E->d, m); },
+             E->tmom.count == 0);
+    });
     accum_note_sample(E->tmom, tstp);
 }
 // one record of the series (beom_series.h) of the fields as they stand into the next free slot, under step tstp
@@ -878,29 +886,20 @@ static void launch_series(beom_engine *E, int tstp) {
     double *rec = E->ser_rec + E->ser_tstp.size() * (size_t)E->ser_rows * count;
     const dim3 g((unsigned)nch, (unsigned)((E->ser_rows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
     const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
-#define SER_GO(kern) do { if (E->dense) hipLaunchKernelGGL(kern<true>, g, b, 0, E->stream, d, E->ser_jlo, E->ser_rows, width, \
-                                                           E->integ_xper, E->integ_yper, map, E->integ_part); \
-                          else hipLaunchKernelGGL(kern<false>, g, b, 0, E->stream, d, E->ser_jlo, E->ser_rows, width, \
-                                                  E->integ_xper, E->integ_yper, map, E->integ_part); } while (0)
-    if (E->ser_level == 1) SER_GO(k_integral_rows); else SER_GO(k_series_rows);
-#undef SER_GO
+    // (the two kernels take the same arguments; named here and not through pick, which would move k_integral_rows behind
+    // its other user, beom_integral_rows, in the code object)
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, g, b, 0, E->stream, d, E->ser_jlo, E->ser_rows, width, E->integ_xper, E->integ_yper, map, E->integ_part); };
+    if (E->ser_level == 1) { if (E->dense) go(k_integral_rows<true>); else go(k_integral_rows<false>); }
+    else if (E->dense) go(k_series_rows<true>); else go(k_series_rows<false>);
     hipLaunchKernelGGL(k_integral_chunks, dim3((unsigned)E->ser_rows), dim3(64), 0, E->stream,
                        (const double *)E->integ_part, rec, count, nch, nchp2);
     E->ser_tstp.push_back(tstp);
 }
-template <class CTX>
-static bool launch_mont_all(beom_engine *E) {
-    const dim3 g = CTX::grid(E->d, 1), b(BEOM_BLOCK);
-    switch (E->d.nlay) {
-#define CASE_NL(n) case n: hipLaunchKernelGGL((k_update_mont_all<CTX, n>), g, b, 0, E->stream, E->d); return true;
-        CASE_NL(1) CASE_NL(2) CASE_NL(3) CASE_NL(4) CASE_NL(5) CASE_NL(6) CASE_NL(7) CASE_NL(8)
-#undef CASE_NL
-        default: return false;
-    }
-}
 static void launch_mont(beom_engine *E, int ilay) {
-    if (ilay == 0) {
-        if (E->dense ? launch_mont_all<CellDense>(E) : launch_mont_all<CellGather>(E)) return;
+    if (ilay == 0 && E->d.nlay <= 8) {         // all layers of a column in one thread: instantiated for 1..8 layers
+        if (E->dense) pick_int<1, 8>(E->d.nlay, [&](auto n) { hipLaunchKernelGGL((k_update_mont_all<CellDense, n>), CellDense::grid(E->d, 1), dim3(BEOM_BLOCK), 0, E->stream, E->d); });
+        else pick_int<1, 8>(E->d.nlay, [&](auto n) { hipLaunchKernelGGL((k_update_mont_all<CellGather, n>), CellGather::grid(E->d, 1), dim3(BEOM_BLOCK), 0, E->stream, E->d); });
+        return;
     }
     const int nz = ilay ? 1 : E->d.nlay;
     LAUNCH_CTX(k_update_mont<CellGather>, k_update_mont<CellDense>, nz, E->d, ilay);
@@ -929,54 +928,27 @@ static void launch_uv(beom_engine *E, int ilay, double gene, double ramp, double
 }
 // the tiled sweeps in the tile geometry Q (beom_kernels.h: TileGeom)
 template <int Q>
-static bool raw_mont_visc(beom_engine *E, bool leith, bool plain) {
+static void raw_mont_visc(beom_engine *E, const StepPlan &p) {
     const dim3 g = mont_visc_grid<Q>(E->d), b(BEOM_BLOCK);
-    switch (E->d.nlay) {
-#define MV_GO(n, le, pl) hipLaunchKernelGGL((k_mont_visc<Q, n, le, pl>), g, b, 0, E->stream, E->d)
-#define CASE_NL(n) case n: if (plain) { if (leith) MV_GO(n, true, true); else MV_GO(n, false, true); } \
-                           else if (leith) MV_GO(n, true, false); else MV_GO(n, false, false); return true;
-        CASE_NL(1) CASE_NL(2) CASE_NL(3) CASE_NL(4) CASE_NL(5) CASE_NL(6) CASE_NL(7) CASE_NL(8)
-#undef CASE_NL
-#undef MV_GO
-        default: return false;
-    }
+    pick_int<1, 8>(E->d.nlay, [&](auto n) {       // (p.mont.fused: nlay <= 8)
+        pick([&](auto pl, auto le) { hipLaunchKernelGGL((k_mont_visc<Q, n, le, pl>), g, b, 0, E->stream, E->d); }, p.mont.plain, p.leith);
+    });
 }
 template <int Q>
-static void raw_uv_fused(beom_engine *E, bool first_x, bool prod, bool zv, bool hm, bool plain, double gene, double ramp, double ctim) {
+static void raw_uv_fused(beom_engine *E, const StepPlan &p) {
     const dim3 g = uv_fused_grid<Q>(E->d), b(TileGeom<Q>::BLOCK);
-    DevView &d = E->d;
-#define UV_GO(kern, fx, pr, z) hipLaunchKernelGGL((kern<Q, fx, pr, z>), g, b, 0, E->stream, d, gene, ramp, ctim)
-#define UV_PLAIN(fx, z, h) hipLaunchKernelGGL((k_uv_fused<Q, fx, true, z, h, true>), g, b, 0, E->stream, d, gene, ramp, ctim)
-#define UV_PICK(fx) do { \
-        if (plain) { if (hm) { if (zv) UV_PLAIN(fx, true, true); else UV_PLAIN(fx, false, true); } \
-                     else { if (zv) UV_PLAIN(fx, true, false); else UV_PLAIN(fx, false, false); } } \
-        else if (hm) { if (zv) hipLaunchKernelGGL((k_uv_fused<Q, fx, true, true, true>), g, b, 0, E->stream, d, gene, ramp, ctim); \
-                       else hipLaunchKernelGGL((k_uv_fused<Q, fx, true, false, true>), g, b, 0, E->stream, d, gene, ramp, ctim); } \
-        else if (d.stress_fold) { if (zv) UV_GO(k_uv_fused_sf, fx, true, true); else if (prod) UV_GO(k_uv_fused_sf, fx, true, false); else UV_GO(k_uv_fused_sf, fx, false, false); } \
-        else { if (zv) UV_GO(k_uv_fused, fx, true, true); else if (prod) UV_GO(k_uv_fused, fx, true, false); else UV_GO(k_uv_fused, fx, false, false); } \
-    } while (0)
-    // (stress_fold: distribute_stress formed inside the sweep — its own instantiations, so that the unforced ones stay lean;
-    // hm: the history-from-Montgomery form, instantiated for the staged k_uv_fused only — mont_hist_step is its gate;
-    // plain: the staged forms with the optional forcing compiled out — launch_uv_fused is its gate)
-    if (first_x) UV_PICK(true); else UV_PICK(false);
-#undef UV_PICK
-#undef UV_PLAIN
-#undef UV_GO
+    // (sf: distribute_stress formed inside the sweep — its own instantiations, so that the unforced ones stay lean;
+    // hm: the history-from-Montgomery form, plain: the optional forcing compiled out — both instantiated for the staged
+    // k_uv_fused only.  beom_plan::uv_form_exists: the twelve forms a plan can name)
+    pick([&](auto fx, auto pl, auto hm, auto sf, auto zv, auto pr) {
+        if constexpr (!beom_plan::uv_form_exists(sf, pr, zv, hm, pl)) { fprintf(stderr, "beom: the plan names a form of the u+v sweep that does not exist\n"); std::abort(); }
+        else if constexpr (sf) hipLaunchKernelGGL((k_uv_fused_sf<Q, fx, pr, zv>), g, b, 0, E->stream, E->d, p.gene, p.ramp, p.ctim);
+        else hipLaunchKernelGGL((k_uv_fused<Q, fx, pr, zv, hm, pl>), g, b, 0, E->stream, E->d, p.gene, p.ramp, p.ctim);
+    }, p.uv.first_x, p.uv.plain, p.uv.hm, p.stress_fold, p.uv.zv, p.uv.prod);
 }
-// fused Montgomery + Leith sweep (dense frames); false if no instantiation for this nlay
-// leith: this step refreshes the Leith viscosity (:2188, :2268); else the sweep forms the products of the
-// standing v_cc, v_ll.  keep_visc: a refreshed viscosity has to stand for later steps (n_3d > 1).
-static bool launch_mont_visc(beom_engine *E, bool uv_fused_follows, bool leith, bool keep_visc) {
-    E->d.lean_d2h = uv_fused_follows && E->lean_d2h && !E->d.keep_diag;
-    E->d.keep_visc = keep_visc;
-    E->d.zero_visc = !leith && uv_fused_follows && E->lean_visc && E->visc_all_zero && E->P.dvis == 0.0 && E->P.bvis == 0.0 &&
-                     !E->d.keep_diag;
-    // plain: nothing of what PLAIN compiles out of body_mont_visc is asked for by this launch
-    const bool plain = E->plain_sweeps && E->d.ocrp == 0.0 && !(E->d.rgld >= 0.5) && !E->d.has_hto && !E->d.keep_diag && !E->d.keep_visc;
-    const bool ok = E->tile4 ? raw_mont_visc<1>(E, leith, plain) : raw_mont_visc<2>(E, leith, plain);
-    if (ok && plain) E->last_plain |= 2;
-    return ok;
-}
+// fused Montgomery + Leith sweep (dense frames): p.leith refreshes the Leith viscosity (:2188, :2268); else the sweep forms
+// the products of the standing v_cc, v_ll
+static void launch_mont_visc(beom_engine *E, const StepPlan &p) { if (E->tile4) raw_mont_visc<1>(E, p); else raw_mont_visc<2>(E, p); }
 // fused U+V sweep (dense frames): first_x = update_u first (even tstp)
 static void uv_fused_swap(beom_engine *E, bool first_x, bool hm = false) {
     DevView &d = E->d;
@@ -986,28 +958,9 @@ static void uv_fused_swap(beom_engine *E, bool first_x, bool hm = false) {
     if (first_x) { rot4(d.dmx); rot3(d.dmy); }
     else         { rot4(d.dmy); rot3(d.dmx); }
 }
-// hm: the history-from-Montgomery form (needs prod; the caller has checked mont_hist_step)
-static void launch_uv_fused(beom_engine *E, bool first_x, bool prod, double gene, double ramp, double ctim,
-                            bool swap = true, bool hm = false) {
-    const bool zv = prod && E->d.zero_visc;       // set by launch_mont_visc of this step
-    // plain: a staged sweep (not the _sf kernel) of a handle with nothing of what PLAIN compiles out of uv_core
-    const DevView &d = E->d;
-    const bool plain = E->plain_sweeps && prod && !d.stress_fold && !d.has_nudg && !d.has_tide && !d.has_stress && !d.has_bodf &&
-                       !(d.rgld >= 0.5) && d.svis == 0.0;
-    if (plain) E->last_plain |= 1;
-    if (E->tile4) raw_uv_fused<1>(E, first_x, prod, zv, hm, plain, gene, ramp, ctim);
-    else raw_uv_fused<2>(E, first_x, prod, zv, hm, plain, gene, ramp, ctim);
-    if (swap) uv_fused_swap(E, first_x, hm);
-}
-static bool can_fuse(const beom_engine *E, int n_3d, bool first3) {
-    // either every step refreshes the viscosity (dvis > 1e-3 and n_3d = 1, :2268) — Montgomery + Leith
-    // in one sweep — or no step after the third ever does (dvis <= 1e-3, svis = 0): v_cc, v_ll stand
-    // and the sweep forms their products with this step's dive, rvor
-    const int nl = E->d.nlay;
-    if (!(E->dense && E->fuse && nl <= 8) || E->P.svis > 0.0) return false;
-    (void)n_3d;
-    if (E->P.dvis > 1.e-3) return true;           // refresh steps: Leith in the sweep; others: standing v_cc, v_ll
-    return !first3;                               // steps 1-3 call update_viscosity unconditionally (:2188)
+static void launch_uv_fused(beom_engine *E, const StepPlan &p, bool swap = true) {
+    if (E->tile4) raw_uv_fused<1>(E, p); else raw_uv_fused<2>(E, p);
+    if (swap) uv_fused_swap(E, p.uv.first_x, p.uv.hm);
 }
 // rigid lid: rebuild the transports from the new h and velocities (steps 1-3: centred, :2166-2177; later: upstream with the
 // curvatures of the last layer, :2237-2257), then the pressure solve and the velocity correction (surf_pressure, :1705-1838)
@@ -1087,46 +1040,34 @@ int beom_distribute_stress(beom_handle E) { NEED_ARRAYS(E); launch_stress(E); re
 
 }  // extern "C"
 
-// Per-step scalars of integrate_time (private_mod.f95:1858-1901).
-struct StepScalars { double ctim, ramp, gene; bool first3, upst, stress, fused, fused_uv; int n_3d; };
-static StepScalars step_scalars(const beom_engine *E, int tstp, double tres, double dtd8, double dt_r,
-                                double rsta, int n_3d) {
-    StepScalars s;
-    s.ctim = tres + dtd8 * (double)tstp;                           // :1862,1887
-    s.first3 = tstp <= 3;
-    s.ramp = 1.0;
-    if (s.first3) {
-        const double c1 = tres + dtd8 * 1.0;                       // ramp is set once, at tstp = 1 (:1864-1866)
-        if (rsta < 0.5 && c1 < dt_r) s.ramp = c1 / dt_r;
-        s.upst = true;                                             // update_viscosity is unconditional (:2188)
-        s.stress = tstp == 1;                                      // :1863
-    } else {
-        if (rsta < 0.5 && s.ctim < dt_r) s.ramp = s.ctim / dt_r;   // :1898-1901
-        s.upst = (tstp % n_3d) == 0;                               // :1889-1892
-        s.stress = s.upst;                                         // :1894-1896
-    }
-    s.gene = (s.first3 || (E->lid && E->P.g_fb > 0.5)) ? 0.0 : E->P.g_fb;      // :1859,1877; :1880-1884: no multistep with a lid
-    s.n_3d = n_3d;
-    s.fused = can_fuse(E, n_3d, s.first3);
-    s.fused_uv = E->dense && E->fuse_uv;           // (svis > 0: the v_cc / v_ll form, uu4 and vv4 read through L2)
-    return s;
+// ---- the step driver: plan_step (beom_plan.h) decides the form of a step, the functions below execute it ---------------
+static StepFacts facts_of(const beom_engine *E) {
+    const DevView &d = E->d;
+    StepFacts f;
+    f.dense = E->dense; f.nlay = d.nlay; f.lid = E->lid;
+    f.svis = E->P.svis; f.dvis = E->P.dvis; f.bvis = E->P.bvis; f.g_fb = E->P.g_fb; f.ocrp = d.ocrp;
+    f.has_nudg = d.has_nudg; f.has_tide = d.has_tide; f.has_stress = d.has_stress; f.has_bodf = d.has_bodf; f.has_hto = d.has_hto;
+    f.wind = E->wind; f.bot = E->bot; f.top = E->top; f.up_tt = E->up_tt; f.up_tb = E->up_tb; f.up_tu = E->up_tu;
+    f.fold_static_ok = E->fold_static_ok; f.visc_all_zero = E->visc_all_zero; f.mont_keep = E->mont_keep;
+    f.fuse = E->fuse; f.fuse_uv = E->fuse_uv; f.fold_stress = E->fold_stress; f.lean_d2h = E->lean_d2h; f.lean_visc = E->lean_visc;
+    f.mont_history = E->mont_history; f.plain_sweeps = E->plain_sweeps; f.keep_diag = d.keep_diag != 0;
+    f.mont_levels_valid = E->mont_levels_valid;
+    return f;
+}
+// The one place that writes the per-launch fields of the view and what beom_info reports of the last step.
+static void apply_plan(beom_engine *E, const StepPlan &p) {
+    DevView &d = E->d;
+    d.lean_d2h = p.mont.lean_d2h; d.keep_visc = p.mont.keep_visc; d.zero_visc = p.mont.zero_visc; d.stress_fold = p.stress_fold;
+    E->last_folded = p.stress_fold;
+    E->last_uv_fused = p.uv.fused_uv;
+    E->last_mont_hist = p.uv.hm;
+    E->last_plain = (p.uv.plain ? 1 : 0) | (p.mont.plain ? 2 : 0);
 }
 
-// distribute_stress of this step inside its fused momentum sweep (uv_core): the fractions are constants (ocrp = 0), every
-// step refreshes the stress (so tt3d, tb3d, tu3d are never read back; steps 2 and 3 reuse step 1's, :1863), and an array
-// the engine does not refresh holds nothing but zeros.  The three arrays then keep their values of step 3 ("keep_diag" = 1
-// keeps them current).
-static bool stress_folds(const beom_engine *E, const StepScalars &s) {
-    return E->fold_stress && E->fold_static_ok && s.fused_uv && s.stress && !s.first3 && s.n_3d == 1 && !E->d.keep_diag &&
-           (E->wind || !E->up_tt) && (E->bot || !E->up_tb) && (E->top || !E->up_tu);
-}
-
-// the start of a step, and of each part of a split step: its timer if the step is sampled, whether its stress folds
-static StepTimer *begin_step(beom_engine *E, int tstp, const StepScalars &s) {
+// the timer of a step, and of each part of a split step, if the step is sampled
+static StepTimer *step_timer(beom_engine *E, int tstp) {
     StepTimer *T = (E->timer && tstp % E->timer->stride == 0) ? E->timer : nullptr;
     if (T) { T->st = E->stream; T->step(tstp); }
-    E->d.stress_fold = stress_folds(E, s) ? 1 : 0;
-    E->last_folded = E->d.stress_fold != 0;
     return T;
 }
 // launches f, bracketed as kernel class c when the step is sampled
@@ -1137,67 +1078,50 @@ static void timed(StepTimer *T, int c, F &&f) {
     if (T) T->end();
 }
 
-// The step up to the momentum sweeps: stress, the rebuild of steps 1-3, update_h, Montgomery + Leith.  Returns prod: the
-// Montgomery sweep formed the viscous products for the fused u+v sweep (s.fused_uv) that follows.
-static bool step_front(beom_engine *E, const StepScalars &s, StepTimer *T) {
-    if (s.stress && !E->d.stress_fold) launch_stress(E);
-    if (E->lid) launch_lid_fluxes(E, s.first3);
-    else if (s.first3) launch_rebuild(E);                          // :2166-2177
-    if (E->ntrc > 0) timed(T, 7, [&] { launch_tracers(E, s.gene, s.ramp, s.ctim); });      // reads hlay, h_u, h_v as update_h is about to
+// The step up to the momentum sweeps: stress, the rebuild of steps 1-3, update_h, Montgomery + Leith.
+static void step_front(beom_engine *E, const StepPlan &p, StepTimer *T) {
+    if (p.launch_stress) launch_stress(E);
+    if (E->lid) launch_lid_fluxes(E, p.first3);
+    else if (p.rebuild) launch_rebuild(E);                         // :2166-2177
+    if (E->ntrc > 0) timed(T, 7, [&] { launch_tracers(E, p.gene, p.ramp, p.ctim); });      // reads hlay, h_u, h_v as update_h is about to
     timed(T, 0, [&] {
-        launch_h(E, s.gene, s.ramp, s.ctim);                       // :2181,2259
+        launch_h(E, p.gene, p.ramp, p.ctim);                       // :2181,2259
         if (E->lid) launch_lid_h_epilogue(E);                      // :1648-1700
     });
-    const bool leith = E->P.dvis > 1.e-3 && s.upst;
-    bool prod = false;
-    timed(T, s.fused ? 5 : 1, [&] {
-        prod = s.fused && launch_mont_visc(E, s.fused_uv, leith, leith && s.n_3d > 1);     // :2187-2188, 2266-2269 in one sweep
-        if (!prod) launch_mont(E, 0);
+    timed(T, p.mont.fused ? 5 : 1, [&] {
+        if (p.mont.fused) launch_mont_visc(E, p);                  // :2187-2188, 2266-2269 in one sweep
+        else launch_mont(E, 0);
     });
-    if (!prod && (s.first3 || leith || E->P.svis > 0.0)) timed(T, 2, [&] { launch_visc(E, 0); });     // :2188,2268
-    return prod;
-}
-
-// Does this step run the history-from-Montgomery form of the fused u+v sweep?  The option is on; the handle keeps the
-// levels (a whole dense frame, no lid); the step takes launch_uv_fused with the products staged (s.fused: k_mont_visc runs
-// for every nlay <= 8, which mont_keep implies) and the multistep term live; its stress does not fold (k_uv_fused_sf stays
-// on the arrays); and the buffers hold the three steps before this one.
-static bool mont_hist_step(const beom_engine *E, const StepScalars &s) {
-    return E->mont_history && E->mont_keep && s.fused && s.fused_uv && s.gene != 0.0 && !stress_folds(E, s) &&
-           E->mont_levels_valid >= 3;
+    if (p.launch_visc) timed(T, 2, [&] { launch_visc(E, 0); });    // :2188,2268
 }
 
 // flt: -1 = the handle carries no floats; else bit 0 = the first step of its beom_step call, bit 1 = the last.  The float
 // launches sit at the top and at the very end: stage 1 alone in front of the call's first step, stage 2 (+ the next step's
 // stage 1, on the same velocities) behind every step.
-static void one_step(beom_engine *E, int tstp, const StepScalars &s, int flt = -1) {
+static void one_step(beom_engine *E, const StepPlan &p, int flt = -1) {
+    const int tstp = p.tstp;
     if (flt >= 0 && (flt & 1)) launch_floats(E, 1, nullptr);
-    const bool hm = mont_hist_step(E, s);
-    if (!hm) (void)hist_sync(E);                                   // a step on the arrays: bring them up to date first
+    if (p.needs_arrays) (void)hist_sync(E);                        // a step on the arrays: bring them up to date first
     rotate_mont(E);                                                // the one place d.mont moves to its next buffer
-    StepTimer *T = begin_step(E, tstp, s);
-    E->last_plain = 0;
-    const bool prod = step_front(E, s, T);
-    const bool u_first = tstp % 2 == 0;                            // :2193-2199,2276-2282
-    E->last_uv_fused = s.fused_uv;
-    E->last_mont_hist = hm;
+    StepTimer *T = step_timer(E, tstp);
+    apply_plan(E, p);
+    step_front(E, p, T);
     if (E->mont_keep) E->mont_levels_valid = std::min(E->mont_levels_valid + 1, 3);      // this step's mont is in its buffer
-    if (s.fused_uv) timed(T, 6, [&] { launch_uv_fused(E, u_first, prod, s.gene, s.ramp, s.ctim, true, hm && prod); });
+    if (p.uv.fused_uv) timed(T, 6, [&] { launch_uv_fused(E, p); });
     else
-        for (const bool x : {u_first, !u_first})
+        for (const bool x : {p.uv.first_x, !p.uv.first_x})
             timed(T, x ? 3 : 4, [&] {
-                if (x) launch_uv<true>(E, 0, s.gene, s.ramp, s.ctim, prod);
-                else launch_uv<false>(E, 0, s.gene, s.ramp, s.ctim, prod);
+                if (x) launch_uv<true>(E, 0, p.gene, p.ramp, p.ctim, p.uv.prod);
+                else launch_uv<false>(E, 0, p.gene, p.ramp, p.ctim, p.uv.prod);
             });
     if (E->obc) {                                                  // :2201-2204, 2285-2288
         const dim3 g((unsigned)((E->d.nseg + BEOM_BLOCK - 1) / BEOM_BLOCK), (unsigned)E->d.nlay, 1);
         hipLaunchKernelGGL(k_no_gradient_obc, g, dim3(BEOM_BLOCK), 0, E->stream, E->d, 0);
         hipLaunchKernelGGL(k_no_gradient_obc, g, dim3(BEOM_BLOCK), 0, E->stream, E->d, 1);
     }
-    if (E->lid) { launch_lid_fluxes(E, s.first3); launch_lid_pressure(E); }       // :2206-2222, 2290-2316
-    E->d.stress_fold = 0;
+    if (E->lid) { launch_lid_fluxes(E, p.first3); launch_lid_pressure(E); }      // :2206-2222, 2290-2316
     if (flt >= 0) launch_floats_after(E, tstp, !(flt & 2));
-    E->last_tstp = tstp;
+    E->last_tstp = tstp; E->split.tstp = 0;      // (a whole step: no part 1 is pending)
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
     if (!E->ser_by_caller && series_due(E, tstp)) launch_series(E, tstp);
@@ -1220,6 +1144,15 @@ static int rows_copy(beom_handle E, int jlo, int nrows, void *dbuf, int jlo2, vo
     }
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
+// Can a recorder of nrec records, `held` of them taken, hold those due in steps tstp_first .. tstp_first+nsteps-1?  If not,
+// the refusal goes to errm in the words of fmt (first step, last step, records due, stride, held, nrec).
+static bool recorder_holds(int tstp_first, int nsteps, int stride, size_t held, int nrec, char *errm, int errm_len, const char *fmt) {
+    long long due = 0;
+    for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp) due += tstp % stride == 0;
+    if ((long long)held + due <= nrec) return true;
+    set_err(errm, errm_len, fmt, tstp_first, tstp_first + nsteps - 1, due, stride, (long long)held, nrec);
+    return false;
+}
 extern "C" {
 
 int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd8, double dt_r,
@@ -1230,31 +1163,18 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
     if (E->lid && !E->lid_ready) { set_err(errm, errm_len, "beom_step: rgld = 1 needs beom_set_rigid_lid (the Poisson operators Ow, Os, Osum_ and the lid pressure, private_mod.f95:505-563)"); return -6; }
     const bool flt = E->nflt > 0 && !E->flt_band;      // (a band's floats are launched by beom_multi_step, around the exchange)
     if (flt && !E->flt_ready) { set_err(errm, errm_len, "beom_step: the handle's %lld floats have no positions yet (beom_upload_floats)", E->nflt); return -3; }
-    if (flt && E->flt_nrec > 0) {          // the recorder must hold every record of the call: refused before anything is launched
-        long long due = 0;
-        for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp) due += tstp % E->flt_stride == 0;
-        const long long held = (long long)E->flt_rec_tstp.size();
-        if (held + due > E->flt_nrec) {
-            set_err(errm, errm_len, "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
-                    "empty it with beom_download_float_track, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
-                    E->flt_stride, held, E->flt_nrec);
-            return -3;
-        }
-    }
-    if (E->ser_level > 0 && !E->ser_by_caller) {      // the series' recorder likewise
-        long long due = 0;
-        for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp) due += tstp % E->ser_stride == 0;
-        const long long held = (long long)E->ser_tstp.size();
-        if (held + due > E->ser_nrec) {
-            set_err(errm, errm_len, "beom_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
-                    "empty it with beom_download_series, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
-                    E->ser_stride, held, E->ser_nrec);
-            return -3;
-        }
-    }
+    // a recorder must hold every record of the call: refused before anything is launched
+    if (flt && E->flt_nrec > 0 &&
+        !recorder_holds(tstp_first, nsteps, E->flt_stride, E->flt_rec_tstp.size(), E->flt_nrec, errm, errm_len,
+                        "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
+                        "empty it with beom_download_float_track, or take fewer steps per call")) return -3;
+    if (E->ser_level > 0 && !E->ser_by_caller &&
+        !recorder_holds(tstp_first, nsteps, E->ser_stride, E->ser_tstp.size(), E->ser_nrec, errm, errm_len,
+                        "beom_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
+                        "empty it with beom_download_series, or take fewer steps per call")) return -3;
     HIP_TRY(hipSetDevice(E->device));
-    for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp)
-        one_step(E, tstp, step_scalars(E, tstp, tres, dtd8, dt_r, rsta, n_3d),
+    for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp)      // (the facts move with the steps: mont_levels_valid)
+        one_step(E, beom_plan::plan_step(facts_of(E), tstp, tres, dtd8, dt_r, rsta, n_3d),
                  flt ? (tstp == tstp_first ? 1 : 0) | (tstp == tstp_first + nsteps - 1 ? 2 : 0) : -1);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1323,35 +1243,36 @@ int beom_step_phase(beom_handle E, int tstp, double tres, double dtd8, double dt
     HIP_TRY(hipSetDevice(E->device));
     DevView &d = E->d;
     if (E->P.flag_nudging && E->P.mcbc < 0.5 && !E->obc && !E->obc_set) { set_err(errm, errm_len, "beom_step_phase: mcbc = 0 with nudging needs beom_set_open_boundaries (no_gradient_obc, private_mod.f95:2613-2679)"); return -6; }
-    const StepScalars s = step_scalars(E, tstp, tres, dtd8, dt_r, rsta, n_3d);
     const bool south = d.slab && d.joff > 0, north = d.slab && d.joff + d.M < d.Mg;
     // (svis > 0: a band's step stays whole)
-    if (!s.fused_uv || !(south || north) || d.M < 4 * kEdgeRows || phase < 1 || phase > 3 || E->obc || E->lid || E->P.svis > 0.0) {
+    if (!beom_plan::fuses_uv(facts_of(E)) || !(south || north) || d.M < 4 * kEdgeRows || phase < 1 || phase > 3 || E->obc || E->lid || E->P.svis > 0.0) {
         set_err(errm, errm_len, "beom_step_phase: split step not available for this step/configuration");
         return -20;
     }
+    const StepPlan &p = E->split;          // part 1 plans the step, parts 2 and 3 run from what it kept
+    if (phase > 1 && (tstp < 1 || p.tstp != tstp)) {      // (the step's number is all that is matched; 0: no part 1 pending)
+        set_err(errm, errm_len, "beom_step_phase: part %d of step %d, but part 1 prepared step %d", phase, tstp, p.tstp);
+        return -3;
+    }
     const int M = d.M;
-    const bool u_first = tstp % 2 == 0;
     if (leave_mont_history(E)) { set_err(errm, errm_len, "beom_step_phase: the history arrays could not be brought up to date"); return -10; }
-    StepTimer *T = begin_step(E, tstp, s);
-    E->last_uv_fused = true;
-    E->last_mont_hist = false;
+    if (phase == 1) E->split = beom_plan::plan_step(facts_of(E), tstp, tres, dtd8, dt_r, rsta, n_3d);      // (no levels kept: never hm)
+    StepTimer *T = step_timer(E, tstp);
     if (phase == 1) {
-        E->last_plain = 0;
-        E->split_prod = step_front(E, s, T);      // (s.fused_uv holds: parts 2 and 3 are the fused u+v sweep it prepares)
+        apply_plan(E, p);
+        step_front(E, p, T);               // (p.uv.fused_uv holds: parts 2 and 3 are the fused u+v sweep it prepares)
     } else if (phase == 2) {
         // a side without a neighbour has no strip (its rows belong to part 3)
         if (south && north) set_rows(d, 2, 1, kEdgeRows, M - kEdgeRows + 1, M);
         else if (south) set_rows(d, 1, 1, kEdgeRows);
         else set_rows(d, 1, M - kEdgeRows + 1, M);
-        timed(T, 6, [&] { launch_uv_fused(E, u_first, E->split_prod, s.gene, s.ramp, s.ctim, false); });
+        timed(T, 6, [&] { launch_uv_fused(E, p, false); });
     } else {
         set_rows(d, 1, south ? kEdgeRows + 1 : 1, north ? M - kEdgeRows : M);
-        timed(T, 6, [&] { launch_uv_fused(E, u_first, E->split_prod, s.gene, s.ramp, s.ctim, true); });
+        timed(T, 6, [&] { launch_uv_fused(E, p, true); });
     }
     set_rows(d, 1, 1, M);
-    d.stress_fold = 0;
-    E->last_tstp = tstp;
+    E->last_tstp = tstp; if (phase == 3) E->split.tstp = 0;
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1337,7 +1337,11 @@ int beom_download_outputs(beom_handle E, const float *h0r4, float *eta, float *u
 }
 
 // The three `diag` records of write_array (private_mod.f95:2884-2974) formed on the device: only real*4 crosses PCIe.
-// Between time steps only (the work arrays are the step's d2hx / d2hy scratch).
+// Between time steps only: the work arrays are the step's d2hx / d2hy scratch (pcd / qlr with a lid), dead between the steps
+// of every form test_gpu_outputs.py runs a download in front of and names by an assertion — the fused pair with the history
+// kept in arrays or rebuilt from the Montgomery levels, keep_diag = 1, the folded stress, tiled biharmonic viscosity,
+// dt3d > 0, 12 layers, the rectangle with land, the table path, the lid (state and scratch of the next step bit for bit),
+// bands and a ring (state).
 int beom_download_diag(beom_handle E, float *pvor4, float *mont4, float *vcc4, char *errm, int errm_len) {
     if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
     HIP_TRY(hipSetDevice(E->device));

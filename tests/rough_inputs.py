@@ -348,7 +348,10 @@ GATE_CONFIGS = {
     "closed_wind_only_2l": (lambda lm, mm: (lambda pf: (pf[0].replace(tauw=["0.05", "0.02"]), pf[1]))(I.case_headline(lm, mm, 2)), {}, False),
     "closed_drag_only_2l": (lambda lm, mm: (lambda pf: (pf[0].replace(bdrg="1.e-3"), pf[1]))(I.case_headline(lm, mm, 2)), {}, False),
 }
-FRAMES = {"130x18": (130, 18), "321x50": (321, 50), "130x99": (130, 99), "4200x9": (4200, 9)}
+FRAMES = {"130x18": (130, 18), "321x50": (321, 50), "130x99": (130, 99), "4200x9": (4200, 9),
+          # for the output records: one tile, 512 cell slots in three workgroups of the scan (the last holds cell ndeg alone);
+          # lm + 1 = 193 = 1 mod 64, a row pitch padded by 15
+          "63x7": (63, 7), "192x30": (192, 30)}
 _BASE = {}
 
 

@@ -544,6 +544,14 @@ void oracle_rgld_upstream_fluxes(const beom_params *P, oracle_state *S) {
         }
 }
 
+/* Gauss-Seidel sweeps of the last oracle_surf_pressure, and sweeps and solves of all of them since the library was
+ * loaded: what the tests hold the engine's "lid_sweeps" / "lid_solves" to.  Not part of the arithmetic. */
+static int lid_sweeps_last = 0;
+static long long lid_sweeps_total = 0, lid_solves_total = 0;
+int oracle_lid_sweeps_last(void) { return lid_sweeps_last; }
+long long oracle_lid_sweeps_total(void) { return lid_sweeps_total; }
+long long oracle_lid_solves_total(void) { return lid_solves_total; }
+
 /* surf_pressure, private_mod.f95:1705-1838: Poisson equation for the lid pressure by Gauss-Seidel
  * sweeps in packed order (rp = 1), then the velocity correction */
 void oracle_surf_pressure(const beom_params *P, oracle_state *S) {
@@ -586,6 +594,7 @@ void oracle_surf_pressure(const beom_params *P, oracle_state *S) {
         }
         iters = iters + 1;
     }
+    lid_sweeps_last = iters; lid_sweeps_total += iters; ++lid_solves_total;
     for (int ilay = 1; ilay <= P->nlay; ++ilay)                                          /* :1806-1819 */
         for (int ipnt = 1; ipnt <= nd; ++ipnt)
             if (S->subc[ipnt] > 1 && S->subc[ipnt] < lm + 1) {

@@ -75,6 +75,9 @@ def load():
             getattr(_lib, nm).argtypes = [PP, SP]
         _lib.oracle_step.argtypes = [PP, SP, ci, ci, cd, cd, cd, cd, ci]
         _lib.oracle_step.restype = ci
+        _lib.oracle_lid_sweeps_last.restype = ci
+        _lib.oracle_lid_sweeps_total.restype = C.c_longlong
+        _lib.oracle_lid_solves_total.restype = C.c_longlong
         assert _lib.oracle_sizeof_params() == C.sizeof(BeomParams)
         assert _lib.oracle_sizeof_state() == C.sizeof(OracleState)
     return _lib
@@ -138,6 +141,12 @@ class Oracle:
     def rgld_upstream_fluxes(self): self.lib.oracle_rgld_upstream_fluxes(C.byref(self.prm), C.byref(self.st))
     def surf_pressure(self): self.lib.oracle_surf_pressure(C.byref(self.prm), C.byref(self.st))
     def distribute_stress(self): self.lib.oracle_distribute_stress(C.byref(self.prm), C.byref(self.st))
+
+    def lid_sweeps(self) -> dict:
+        """Gauss-Seidel sweeps of surf_pressure: {"last": of the last solve, "sweeps", "solves": running totals of the
+        library, every Oracle object together — callers compare the increase over their own calls}."""
+        return {"last": int(self.lib.oracle_lid_sweeps_last()), "sweeps": int(self.lib.oracle_lid_sweeps_total()),
+                "solves": int(self.lib.oracle_lid_solves_total())}
 
     def state(self) -> dict:
         return {k: self.a[k] for k in STATE_NAMES}

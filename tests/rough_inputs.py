@@ -24,6 +24,8 @@ Amplitudes (all configurations; dt, dl, hsal the case's own):
   nudg          x [0.5, 1] inside the sponge (exact 0 kept elsewhere);  fnud  thickness +-2 cm, velocities +-U there
   hdot          +-max|hdot| per cell and layer where the case has it;  tide  amplitude x [0.5, 1.5], phase +-1 rad
   bodf          +-(0.5-1) x 0.02 U / dt, distinct per layer and direction
+  pi_s          with a rigid lid only: uniform in +-10 at wet cells, 0 elsewhere (the oracle's pressure on these states
+                reaches 30-50 after its 1000 sweeps): a starting pressure that is no earlier solve's result
 
 Growth: max(|u|, |v|) / U of the oracle after step plan B (steps 7-12 from the rough state), frame 130 x 18, seed 1 —
 measured on the CPU oracle; the bound of the tests is 20:
@@ -32,6 +34,12 @@ measured on the CPU oracle; the bound of the tests is 20:
   closed_12l_hdot 1.6   zero_visc_2l 1.6
 (the jet's random divergence on a 5 m column radiates gravity waves of several U within a step; the sill's comes from the
 cell-layers placed at 1-3 hsal).
+The lid, outcropping-stress and private_mod3d configurations, plan A / plan B on 130 x 18, then on 321 x 50:
+  lid_wind_drag_2l 8.5 / 9.8, 9.5 / 11.2   lid_coast_3l 8.2 / 10.2, 9.1 / 11.9   sill_ocrp_stress_3l 8.3 / 8.4, 8.8 / 8.9
+  variant3d_sponge_3l 6.7 / 8.7, 7.0 / 8.6
+(on the rough lid states every solve of both plans stops at surf_pressure's cap of 1000 sweeps, from the rough and from a
+zero starting pressure; variant3d_sponge_3l: layer 3 of the eastern sponge's cells lies below / above 20 hsal in 54 / 46 %
+at 130 x 18 and 50 / 50 % at 321 x 50, and variant 1 differs from variant 0 in 15 % and 6 % of the cell-layers after plan B).
 """
 import copy
 import zlib
@@ -40,18 +48,25 @@ import numpy as np
 
 from beom_amd import inputs as I
 from beom_amd.grid import read_input_data
+from beom_amd.params import make_params
 from helpers import land_mask
 
 U0 = 0.05
 STATIC_INPUTS = ("fcor", "h_to", "h_th", "taus:0", "taus:1", "nudg", "fnud", "hdot", "tide", "bodf")
 STATE_INPUTS = ("hlay", "u", "v", "h_u", "h_v", "rs_h:0", "rs_h:1", "dmdx:0", "dmdx:1", "dmdx:2", "dmdy:0", "dmdy:1", "dmdy:2",
-                "v_cc", "v_ll", "tt3d", "tb3d", "tu3d")
+                "v_cc", "v_ll", "tt3d", "tb3d", "tu3d", "pi_s")
 INPUTS = STATIC_INPUTS + STATE_INPUTS
 # array name: (axis of the packed cells, axis of the layers, axis of the levels / components); None = no such axis
 AXES = {"fcor": (0, None, None), "h_to": (0, None, None), "h_th": (0, None, None), "taus": (1, None, 0), "nudg": (1, None, 0),
         "fnud": (2, 1, 0), "hdot": (1, 0, None), "tide": (1, None, 0), "hlay": (1, 0, None), "u": (1, 0, None),
         "v": (1, 0, None), "h_u": (1, 0, None), "h_v": (1, 0, None), "rs_h": (1, 0, 2), "dmdx": (1, 0, 2), "dmdy": (1, 0, 2),
-        "v_cc": (1, 0, None), "v_ll": (1, 0, None), "tt3d": (2, 0, 1), "tb3d": (2, 0, 1), "tu3d": (2, 0, 1)}
+        "v_cc": (1, 0, None), "v_ll": (1, 0, None), "tt3d": (2, 0, 1), "tb3d": (2, 0, 1), "tu3d": (2, 0, 1),
+        "pi_s": (0, None, None)}                       # (None on a case without a lid: present() leaves it out)
+
+
+def present(f):
+    """The arrays of AXES the Fields object f has (pi_s: with a rigid lid only)."""
+    return [k for k in AXES if getattr(f, k, None) is not None]
 
 
 def _rng(seed, reseed, name):
@@ -190,6 +205,9 @@ def rough_fields(f, seed, U=U0, reseed=(), visc="rough", zero=()):
         a[:, 1] = np.where(opv[None], _pm(r, (nlay, n1)) * amp * hcv, 0.0)
         setattr(g, k, a)
         sup[k] = np.stack([np.broadcast_to(opu[None], (nlay, n1)), np.broadcast_to(opv[None], (nlay, n1))], axis=1)
+    if float(p.rgld) > 0.5:                                          # a starting pressure that is no solve's result
+        g.pi_s = np.where(wet, _pm(R("pi_s"), n1) * 10.0, 0.0)
+        sup["pi_s"] = wet.copy()
     for k in zero:
         setattr(g, k, np.zeros_like(getattr(g, k)))
         sup[k] = np.zeros(sup[k].shape, bool)
@@ -319,6 +337,58 @@ def _dt3d_forced(lm, mm):
                      tauw=["0.05", "0.02"]), files
 
 
+def _lid(nlay, coast=False, tauw=("0.05", "0.02")):
+    """The rigid lid (rgld = 1; its operators need ocrp = 1) on the headline basin with wind and bottom drag, no multistep
+    term.  coast: land north of row 0.8 mm — a straight coast (at a cell with four dry faces, as a ragged coast has them,
+    the reference's operators are 1/0 and the oracle gives NaN from step 1)."""
+    def make(lm, mm):
+        p, files = I.case_headline(lm, mm, nlay)
+        p = p.replace(rgld="1.", ocrp="1.", g_fb="0.", bdrg="2.e-4", tauw=list(tauw))
+        if coast:
+            files = {k: np.array(v, dtype=np.float64) for k, v in files.items()}
+            files["h_bo"][:, int(0.8 * p.mm) + 1:] = 0.0
+            p = p.replace(ndeg=I.get_nbr_deg_freedom(files["h_bo"]))
+        return p, files
+    return make
+
+
+LID_REST_WINDS = {"strong": ("5.", "2."), "mild": ("0.5", "0.2")}
+
+
+def lid_from_rest(tauw, frame="130x18"):
+    """Fields of the 2-layer lid case started from rest under the wind tauw (two literals): the solves converge, in a
+    number of sweeps that depends on the wind."""
+    p, files = _lid(2, tauw=tauw)(*FRAMES[frame])
+    return read_input_data(p, files=files)
+
+
+def _sill_stress(lm, mm):
+    p, files = CONFIGS["sill_ocrp_sponge_3l"][0](lm, mm)
+    return p.replace(bdrg="1.e-3", tdrg="5.e-4", qdrg="0.5", tauw=["0.05", "0.02"]), files
+
+
+def _variant3d_sponge(lm, mm):
+    """case_3d_variant of tests/golden/make_golden.py (the update_h epilogue of private_mod3d.f95, :1635-1683) on any frame,
+    with layer 3 at 200 m = 20 hsal in the east before roughening, and sponges on eta 12 columns wide at both ends at a
+    tenth of the golden's rates (with the golden's own the oracle's growth on the rough state is 22-37 U)."""
+    nlay = 3
+    h_bo = np.zeros((lm + 2, mm + 2)); h_bo[1:-1, 1:-1] = 900.0
+    nudg = np.zeros((lm + 2, mm + 2, 3))
+    for i in range(1, 13):
+        nudg[i, :, 0] = 0.1 * 0.25 * (13 - i) / 12.0
+        nudg[lm + 1 - i, :, 0] = 0.1 * 0.20 * (13 - i) / 12.0
+    nudg[0:3, :, 1] = 0.02                           # a nudged western segment must exist (:1226-1231)
+    init = np.zeros((lm + 2, mm + 2, nlay, 3))
+    x = (np.arange(lm + 2) - lm // 2)[:, None] * np.ones((1, mm + 2))
+    init[:, :, 1, 0] = 20.0 * np.tanh(x / 4.0)
+    init[:, :, 2, 0] = 20.0 * (x > 3)
+    cext = np.sqrt(9.8 * 900.0); dl = 1.0e3; dt = 0.5 * dl / cext
+    p = make_params(lm, mm, nlay, I.get_nbr_deg_freedom(h_bo), dl, cext, 1.0e-4, [1026.0, 1027.0, 1028.0], [0.0, 0.3, 0.8],
+                    12 * dt / 86400.0, 1.0, 0.0, 0.0, 0.0, 0.2, 0.0, 1.0, 10.0, 10.0, 1.0, 1.0,
+                    0.0, 0.0, 0.0, 0.0, 0.0, 0.0, desc="rough inputs: private_mod3d update_h epilogue")
+    return p, {"h_bo": h_bo, "nudg": nudg, "init": init}
+
+
 def _closed_12l(lm, mm):
     p, files = I.case_headline(lm, mm, 12)
     hdot = np.zeros((lm + 2, mm + 2, 12))
@@ -342,7 +412,19 @@ CONFIGS = {
     "tide_sponge_2l": (_tide_sponge, {}, False),
     "closed_12l_hdot": (_closed_12l, {}, False),
     "zero_visc_2l": (lambda lm, mm: I.case_headline(lm, mm, 2, dvis=0.0), {}, False),
+    "lid_wind_drag_2l": (_lid(2), {}, False),
+    "lid_coast_3l": (_lid(3, coast=True), {}, True),
+    "sill_ocrp_stress_3l": (_sill_stress, {}, False),
+    "variant3d_sponge_3l": (_variant3d_sponge, {}, False),
 }
+# the `variant` of the oracle and of the engine (1: the update_h epilogue of private_mod3d.f95); 0 where not listed
+ENGINE_VARIANT = {"variant3d_sponge_3l": 1}
+
+
+def variant_of(config):
+    return ENGINE_VARIANT.get(config, 0)
+
+
 # handles with one forcing only, for the gates of the folded stress (not part of the sweep over CONFIGS)
 GATE_CONFIGS = {
     "closed_wind_only_2l": (lambda lm, mm: (lambda pf: (pf[0].replace(tauw=["0.05", "0.02"]), pf[1]))(I.case_headline(lm, mm, 2)), {}, False),
@@ -360,8 +442,8 @@ def base_fields(config, frame):
     key = (config, frame)
     if key not in _BASE:
         p, files = dict(CONFIGS, **GATE_CONFIGS)[config][0](*FRAMES[frame])
-        if float(p.g_fb) == 0.0:
-            p = p.replace(g_fb="1.")                   # (the multistep terms are what the history levels are for)
+        if float(p.g_fb) == 0.0 and float(p.rgld) < 0.5:
+            p = p.replace(g_fb="1.")                   # (the multistep terms are what the history levels are for; a lid has none)
         _BASE[key] = read_input_data(p, files=files)
     return copy.copy(_BASE[key])
 
@@ -386,4 +468,11 @@ def switched_off(p, f):
         off.add("hdot")
     if not (f.has.get("tide", False) and np.any(f.tide != 0.0)):
         off.add("tide")
+    if float(p.rgld) > 0.5:
+        # no multistep with a lid (gene = 0 on every step, private_mod.f95:1880-1884): the history levels of update_h and of
+        # update_u / update_v are multiplied by 0; and from step 4 on the transports are rebuilt from u and hlay before
+        # update_h reads them (:2237-2257), so the uploaded ones are never read
+        off |= {"rs_h:0", "rs_h:1", "dmdx:0", "dmdx:1", "dmdx:2", "dmdy:0", "dmdy:1", "dmdy:2", "h_u", "h_v"}
+    else:
+        off.add("pi_s")
     return off

@@ -5,7 +5,10 @@ the keys the handle's form keeps (test_gpu_parity._live / _fuses), the one tidal
 Plan A: create from the rough fields, step(1, 5) — steps 1-3 rebuild the transports from rough u and hlay, then steps 4-5.
 Plan B: step(7, ...) in calls of 2, 1 and 3 with a download after each — three steps on the uploaded history, viscosity and
 stress arrays, then (on eligible handles) the history-from-Montgomery form.  The oracle's results are computed once per
-configuration and frame and shared by both tile geometries."""
+configuration and frame and shared by both tile geometries.
+
+The two rigid-lid configurations have a test of their own (test_rigid_lid_on_rough_states): the same plans, with the lid
+pressure and the handle's counts of Gauss-Seidel sweeps and solves held to the oracle's after every call."""
 import copy
 import os
 
@@ -23,8 +26,9 @@ from test_gpu_parity import COS_TOL, MODES, PROGNOSTIC, _fuses, _live
 pytestmark = pytest.mark.gpu
 CALLS_B = (2, 1, 3)
 
+LIDS = ("lid_wind_drag_2l", "lid_coast_3l")      # (their own test further down: the pressure and the counts of sweeps)
 # name: (configuration, arguments of rough_fields, dense_hint, stress folded from step 4 on?)
-VARIANTS = {c: (c, {}, 1, False) for c in RI.CONFIGS}
+VARIANTS = {c: (c, {}, 1, False) for c in RI.CONFIGS if c not in LIDS}
 VARIANTS.update({
     # the fold needs every uploaded stress array to have its forcing: no top drag here, so tu3d stays +0
     "stommel_wind_drag": ("stommel_wind_drag", {"zero": ("tu3d",)}, 1, True),
@@ -46,7 +50,7 @@ def _no_geometry_leak():
 def _rough(variant, frame):
     key = (variant, frame)
     if key not in _ROUGH:
-        config, kw, _, _ = VARIANTS[variant]
+        config, kw = VARIANTS[variant][:2] if variant in VARIANTS else (variant, {})      # (a lid: the configuration itself)
         _ROUGH[key] = RI.rough_fields(RI.base_fields(config, frame), 1, **kw)
     return _ROUGH[key]
 
@@ -60,10 +64,11 @@ def _oracle(variant, frame):
     key = (variant, frame)
     if key not in _ORACLE:
         g = _rough(variant, frame)
-        o = oracle_lib.Oracle(g)
+        ev = RI.variant_of(VARIANTS[variant][0])
+        o = oracle_lib.Oracle(g, variant=ev)
         o.step(1, 5)
         res = {"A": _snap(o), "B": []}
-        o = oracle_lib.Oracle(g)
+        o = oracle_lib.Oracle(g, variant=ev)
         t = 7
         for n in CALLS_B:
             o.step(t, n)
@@ -77,6 +82,7 @@ def _oracle(variant, frame):
 def _engine(g, variant, rows=None, **kw):
     config, _, dense_hint, _ = VARIANTS[variant]
     opts = dict(RI.CONFIGS, **RI.GATE_CONFIGS)[config][1]
+    kw = dict(kw, variant=RI.variant_of(config))
     if rows is None:
         e = capi.Engine(g, dense_hint=dense_hint, **kw)
     else:
@@ -144,14 +150,15 @@ def test_plans_a_and_b_against_the_oracle(variant, frame, rows):
 
 
 @pytest.mark.parametrize("mode", [m for m in MODES if m != "dense_fused"])
-@pytest.mark.parametrize("config", ["closed_leith_3l", "sill_ocrp_sponge_3l", "zero_visc_2l", "closed_dt3d_forced_3l"])
+@pytest.mark.parametrize("config", ["closed_leith_3l", "sill_ocrp_sponge_3l", "zero_visc_2l", "closed_dt3d_forced_3l",
+                                    "sill_ocrp_stress_3l", "variant3d_sponge_3l"])
 def test_other_engine_modes_on_plan_b(config, mode):
     """The table path, the separate sweeps, one fused sweep without the other, and the fused pair that keeps its diagnostics:
     the forms the production default does not launch read the same rough arrays through other kernels."""
     g = _rough(config, "130x18")
     p = g.p
     dh, fmv, fuv, keep = MODES[mode]
-    e = capi.Engine(g, dense_hint=dh)
+    e = capi.Engine(g, dense_hint=dh, variant=RI.variant_of(config))
     for k, v in (("fuse_mont_visc", fmv), ("fuse_uv", fuv), ("keep_diag", keep)):
         e.set_option(k, v)
     t = 7
@@ -167,6 +174,112 @@ def test_other_engine_modes_on_plan_b(config, mode):
                 assert same(st[k], want[k]), (config, mode, t - 1, k)
         for k in (SCRATCH if not lossy else ("mont", "pvor", "d2hx", "d2hy")):
             assert same(sc[k][p.nlay - 1], scr[k]), (config, mode, t - 1, k, maxrel(sc[k][p.nlay - 1], scr[k]))
+    e.close()
+
+
+# ---- the rigid lid ------------------------------------------------------------------------------------------------------------
+_LID_ORACLE = {}
+
+
+def _lid_counts(x):
+    """(sweeps, solves) so far: of a handle, or of the oracle library."""
+    if isinstance(x, oracle_lib.Oracle):
+        c = x.lid_sweeps()
+        return c["sweeps"], c["solves"]
+    return x.info("lid_sweeps"), x.info("lid_solves")
+
+
+def _lid_oracle_call(o, t, n):
+    """Steps t..t+n-1 on the oracle: (state, pressure, sweeps, solves of this call)."""
+    s0, n0 = _lid_counts(o)
+    o.step(t, n)
+    s1, n1 = _lid_counts(o)
+    return _snap(o), o.rgld["pi_s"].copy(), s1 - s0, n1 - n0
+
+
+def _lid_oracle(config, frame):
+    """{"A": [result of step(1, 5)], "B": [results of the calls of plan B]} on the rough state, computed once."""
+    key = (config, frame)
+    if key not in _LID_ORACLE:
+        g = _rough(config, frame)
+        res = {"A": [_lid_oracle_call(oracle_lib.Oracle(g), 1, 5)], "B": []}
+        o = oracle_lib.Oracle(g)
+        t = 7
+        for n in CALLS_B:
+            res["B"].append(_lid_oracle_call(o, t, n))
+            t += n
+        RI.bounded(g, res["A"][-1][0]); RI.bounded(g, res["B"][-1][0])
+        _LID_ORACLE[key] = res
+    return _LID_ORACLE[key]
+
+
+def _lid_engine_call(e, t, n, want, what):
+    """Steps t..t+n-1 on the handle against the oracle's result of the same call: the fields that carry on and the pressure
+    bit for bit, the other arrays as numbers, and the sweeps and solves the handle counts."""
+    state, pi_s, sweeps, solves = want
+    s0, n0 = _lid_counts(e)
+    e.step(t, n)
+    s1, n1 = _lid_counts(e)
+    assert e.info("stress_folded") == 0, what
+    st = e.download()
+    for k in ("hlay", "u", "v", "h_u", "h_v"):
+        assert same_bits(st[k], state[k]), what + (k, float(np.nanmax(np.abs(st[k] - state[k]))))
+    got = e.download_pressure()
+    assert same_bits(got, pi_s), what + ("pi_s", float(np.nanmax(np.abs(got - pi_s))))
+    for k in PROGNOSTIC:
+        assert same(st[k], state[k]), what + (k, maxrel(st[k], state[k]))
+    assert (s1 - s0, n1 - n0) == (sweeps, solves) and solves == n, what + ("sweeps, solves", (s1 - s0, n1 - n0), (sweeps, solves))
+
+
+@pytest.mark.parametrize("frame", ["130x18", "321x50"])
+@pytest.mark.parametrize("config,dense_hint", [("lid_wind_drag_2l", 1), ("lid_coast_3l", 1), ("lid_coast_3l", 0)])
+def test_rigid_lid_on_rough_states(config, dense_hint, frame):
+    """rgld = 1 from a rough state and a rough starting pressure that is no solve's result: every solve runs into
+    surf_pressure's 1000 sweeps (test_rough_inputs_cpu holds the oracle to that), the last batch of the pipeline is a short
+    one and the ring of pressure copies wraps three times per solve.  Plan A creates the handle with the rough pressure,
+    plan B uploads it afterwards, and scatters state and pressure once more between its second and third call."""
+    g = _rough(config, frame)
+    ref = _lid_oracle(config, frame)
+    what = (config, dense_hint, frame)
+    e = capi.Engine(g, dense_hint=dense_hint)
+    assert bool(e.is_dense) == bool(dense_hint) and bool(e.is_embedded) == (bool(dense_hint) and RI.CONFIGS[config][2])
+    _lid_engine_call(e, 1, 5, ref["A"][0], what + ("plan A",))
+    assert ref["A"][0][2] == 5 * 1000, what
+    e.close()
+    own = copy.copy(g)
+    own.pi_s = RI.base_fields(config, frame).pi_s              # the case's own starting pressure at creation
+    assert not same(own.pi_s, g.pi_s)
+    e = capi.Engine(own, dense_hint=dense_hint)
+    e.upload_pressure(g.pi_s)
+    assert same_bits(e.download_pressure(), g.pi_s), what
+    t = 7
+    for i, (n, want) in enumerate(zip(CALLS_B, ref["B"])):
+        if i == 2:
+            e.upload(**e.download()); e.upload_pressure(e.download_pressure())
+        _lid_engine_call(e, t, n, want, what + ("plan B", t + n - 1))
+        assert want[2] == n * 1000, what
+        t += n
+    e.close()
+
+
+@pytest.mark.parametrize("wind", list(RI.LID_REST_WINDS))
+def test_rigid_lid_from_rest_sweep_counts_per_step(wind):
+    """The lid started from rest, one step per call, the handle's count of sweeps against the oracle's on every step.
+    strong: solves at the cap followed by one that converges within the first batch, which the solve before sized at its
+    largest.  mild: solves that converge in a later batch, after the ring of 257 copies has wrapped."""
+    g = RI.lid_from_rest(RI.LID_REST_WINDS[wind])
+    e, o = capi.Engine(g), oracle_lib.Oracle(g)
+    assert e.is_dense and not e.is_embedded
+    counts = []
+    for t in range(1, 9):
+        want = _lid_oracle_call(o, t, 1)
+        _lid_engine_call(e, t, 1, want, ("from rest", wind, t))
+        counts.append(want[2])
+    print("lid from rest, %s wind: sweeps per step %s" % (wind, counts))
+    if wind == "strong":
+        assert any(a == 1000 and b <= 16 for a, b in zip(counts, counts[1:])), counts
+    else:
+        assert any(257 <= c <= 999 for c in counts) and all(c < 1000 for c in counts), counts
     e.close()
 
 
@@ -210,7 +323,7 @@ def test_body_force_of_minus_zero_keeps_the_fold_off():
 
 # ---- bands ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("config,nband", [("closed_leith_3l", 2), ("closed_leith_3l", 3), ("jet_xyper_2l", 2),
-                                          ("island_ragged_3l", 2)])
+                                          ("island_ragged_3l", 2), ("sill_ocrp_stress_3l", 2)])
 def test_bands_against_the_oracle(config, nband):
     g = _rough(config, "130x99")
     p = g.p

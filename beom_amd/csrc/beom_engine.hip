@@ -21,6 +21,7 @@
 #include "beom_series.h"
 #include "beom_tracers.h"
 #include "beom_tracers_lim.h"
+#include "beom_tracer_mix.h"
 #include "beom_floats.h"
 #include "beom_moments.h"
 #include "beom_tracer_moments.h"
@@ -177,6 +178,11 @@ struct beom_engine {
     int trc_scheme = 1;                // 1 = upstream (k_tracers), 2 = flux-limited (k_tracers_lim); beom_set_tracer_scheme
     double *trc_q = nullptr, *trc_q_alt = nullptr, *trc_rq[2] = {nullptr, nullptr}, *trc_ctrg = nullptr;
     std::vector<void *> trc_allocs;
+    // lateral diffusion, decay and sources of the tracers (beom_set_tracer_mixing; beom_tracer_mix.h): the coefficients
+    // [3][ntrc][nlay] on the device, null while mixing is off; the launches so far
+    double *trc_mix = nullptr;
+    std::vector<void *> trc_mix_allocs;
+    long long trc_mix_launches = 0;
     // Lagrangian floats (beom_set_floats; beom_floats.h): positions, layers, rejected steps, stage 1's increment and
     // provisional position; the track recorder [record][3][float] with the step of every held record
     long long nflt = 0;
@@ -546,7 +552,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -803,8 +809,17 @@ static void launch_h(beom_engine *E, double gene, double ramp, double ctim, bool
     pick_int<2, 0>(forcing(E->d), [&](auto fo) { LAUNCH_CTX((k_update_h<CellGather, fo>), (k_update_h<CellDense, fo>), nz, E->d, gene, ramp, ctim, 0); });
     if (rotate) rot2(E->d.rs);
 }
-// the tracer sweep of a step (beom_tracers.h): all tracers in one launch, in front of the step's update_h
-static void launch_tracers(beom_engine *E, double gene, double ramp, double ctim) {
+// diffusion, decay and sources of the tracers (beom_tracer_mix.h): all tracers in one launch, q -> q_alt
+static void launch_tracer_mix(beom_engine *E) {
+    const TrcMixView m{E->ntrc, E->trc_q, E->trc_q_alt, E->trc_mix};
+    LAUNCH_CTX(k_tracer_mix<CellGather>, k_tracer_mix<CellDense>, E->d.nlay, E->d, m);
+    swp(E->trc_q, E->trc_q_alt);
+    ++E->trc_mix_launches;
+}
+// the tracer sweep of a step (beom_tracers.h): all tracers in one launch, in front of the step's update_h; a step of a
+// handle with mixing runs the mixing launch first, on the q and hlay of the same time level
+static void launch_tracers(beom_engine *E, double gene, double ramp, double ctim, bool mix = true) {
+    if (mix && E->trc_mix) launch_tracer_mix(E);
     TrcView tv{E->ntrc, E->trc_ctrg ? 1 : 0, E->trc_q, E->trc_q_alt, E->trc_rq[0], E->trc_rq[1], E->trc_ctrg};
     const int nz = E->d.nlay;
     // scheme 2 (beom_tracers_lim.h): the tiled kernel in the handle's tile geometry, or the table path
@@ -1028,7 +1043,8 @@ extern "C" {
 // (a sweep called on its own works on the history arrays and breaks the sequence of kept Montgomery levels: NEED_ARRAYS)
 #define NEED_ARRAYS(E) do { NEED(E); if (leave_mont_history(E)) return -10; } while (0)
 int beom_update_h(beom_handle E, double gene, double ramp, double ctim) { NEED_ARRAYS(E); launch_h(E, gene, ramp, ctim); return LAUNCHED(); }
-int beom_update_tracers(beom_handle E, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (E->ntrc < 1) return -3; launch_tracers(E, gene, ramp, ctim); return LAUNCHED(); }
+int beom_update_tracers(beom_handle E, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (E->ntrc < 1) return -3; launch_tracers(E, gene, ramp, ctim, false); return LAUNCHED(); }
+int beom_update_tracer_mixing(beom_handle E) { NEED_ARRAYS(E); if (E->ntrc < 1 || !E->trc_mix) return -3; launch_tracer_mix(E); return LAUNCHED(); }
 int beom_update_mont_rvor_pvor_dive_kine(beom_handle E, int ilay) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_mont(E, ilay); return LAUNCHED(); }
 int beom_update_viscosity(beom_handle E, int ilay) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_visc(E, ilay); return LAUNCHED(); }
 int beom_update_u(beom_handle E, int ilay, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_uv<true>(E, ilay, gene, ramp, ctim); return LAUNCHED(); }
@@ -1531,6 +1547,10 @@ int beom_download_series(beom_handle E, double *rows, int *tstp, int *count, cha
 
 // ---- passive tracers (beom_tracers.h) -----------------------------------------------------------------------------------
 static void accum_free(Accum &A);
+static void free_tracer_mixing(beom_engine *E) {
+    free_list(E->trc_mix_allocs);
+    E->trc_mix = nullptr;
+}
 static void free_tracers(beom_engine *E) {
     free_list(E->trc_allocs);
     E->ntrc = 0;
@@ -1543,7 +1563,7 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    if (ntrc != E->ntrc) accum_free(E->tmom);         // (their arrays have the tracers' shape)
+    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); }        // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
@@ -1559,6 +1579,39 @@ int beom_set_tracer_scheme(beom_handle E, int scheme, char *errm, int errm_len) 
     if (scheme != 1 && scheme != 2) { set_err(errm, errm_len, "beom_set_tracer_scheme: scheme %d (1 = upstream, 2 = limited)", scheme); return -3; }
     if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
     E->trc_scheme = scheme;
+    return 0;
+}
+
+// Diffusion, decay and sources (beom_tracer_mix.h).  Everything is looked at before anything is touched; all null or all
+// zero switches the mixing off and frees the coefficients.
+int beom_set_tracer_mixing(beom_handle E, const double *kappa, const double *decay, const double *source, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->ntrc < 1) { set_err(errm, errm_len, "beom_set_tracer_mixing: the handle carries no tracer (beom_set_tracers comes first)"); return -3; }
+    const int per = E->ntrc * E->d.nlay;
+    // (the caps allow for the roundings of a coefficient that was itself computed as 0.25*dl*dl/dt or 1/dt)
+    const double dt = E->d.dt, cfl = dt / (E->d.dl * E->d.dl), slack = 1.0 + 8.0 * 2.220446049250313e-16;
+    std::vector<double> co(3 * (size_t)per, 0.0);
+    const double *src[3] = {kappa, decay, source};
+    const char *nm[3] = {"kappa", "decay", "source"};
+    bool any = false;
+    for (int k = 0; k < 3; ++k)
+        for (int i = 0; src[k] && i < per; ++i) {
+            const double v = src[k][i];
+            const int t = i / E->d.nlay + 1, l = i % E->d.nlay + 1;
+            if (!std::isfinite(v)) { set_err(errm, errm_len, "beom_set_tracer_mixing: %s of tracer %d, layer %d is not finite", nm[k], t, l); return -3; }
+            if (k < 2 && v < 0.0) { set_err(errm, errm_len, "beom_set_tracer_mixing: %s of tracer %d, layer %d is negative (%g)", nm[k], t, l, v); return -3; }
+            if (k == 0 && v * cfl > 0.25 * slack) { set_err(errm, errm_len, "beom_set_tracer_mixing: kappa of tracer %d, layer %d: kappa*dt/dl^2 = %g exceeds 0.25 (the forward step's maximum principle)", t, l, v * cfl); return -3; }
+            if (k == 1 && v * dt > slack) { set_err(errm, errm_len, "beom_set_tracer_mixing: decay of tracer %d, layer %d: decay*dt = %g exceeds 1 (the forward step would change the sign)", t, l, v * dt); return -3; }
+            co[(size_t)k * per + i] = v == 0.0 ? 0.0 : v;       // (-0 counts as +0)
+            any = any || v != 0.0;
+        }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    if (!any) { free_tracer_mixing(E); return 0; }
+    int rc;
+    if (!E->trc_mix && (rc = alloc_plain(E, E->trc_mix_allocs, &E->trc_mix, co.size(), errm, errm_len))) { free_tracer_mixing(E); return rc; }
+    HIP_TRY(hipMemcpyAsync(E->trc_mix, co.data(), co.size() * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
     return 0;
 }
 
@@ -2002,6 +2055,8 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "vel_targets_zero")) return E->d.vel_targets_zero;
     if (!strcmp(what, "tracers")) return E->ntrc;
     if (!strcmp(what, "tracer_scheme")) return E->trc_scheme;
+    if (!strcmp(what, "tracer_mixing")) return E->trc_mix ? 1 : 0;
+    if (!strcmp(what, "tracer_mix_launches")) return (int)std::min<long long>(E->trc_mix_launches, 2000000000ll);      // all calls so far
     if (!strcmp(what, "floats")) return (int)std::min<long long>(E->nflt, 2000000000ll);
     if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
     if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far

@@ -877,6 +877,17 @@ int beom_multi_set_tracer_scheme(beom_multi_handle M, int scheme, char *errm, in
     return 0;
 }
 
+// beom_set_tracer_mixing on every band: the same coefficients, looked at by band 0 before any band is touched
+int beom_multi_set_tracer_mixing(beom_multi_handle M, const double *kappa, const double *decay, const double *source, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracer_mixing: an earlier step failed half way; destroy the handle"); return -30; }
+    M_RC(tracers_refused(M, "beom_multi_set_tracer_mixing", errm, errm_len));
+    if (M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_mixing: the handle carries no tracer (beom_multi_set_tracers comes first)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    for (int k = 0; k < M->n; ++k) M_RC(beom_set_tracer_mixing(M->eng[k], kappa, decay, source, errm, errm_len));
+    return 0;
+}
+
 int beom_multi_upload_tracers(beom_multi_handle M, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
     M_RC(tracers_refused(M, "beom_multi_upload_tracers", errm, errm_len));

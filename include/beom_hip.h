@@ -324,6 +324,38 @@ int beom_update_tracers(beom_handle h, double gene, double ramp, double ctim);
  * between steps of a run; rq then holds the other scheme's tendencies, as after a restart from another scheme's files.
  * beom_info(h, "tracer_scheme") returns it. */
 int beom_set_tracer_scheme(beom_handle h, int scheme, char *errm, int errm_len);
+/* Lateral diffusion, decay and sources of the tracers (no reference routine; DESIGN.md f-N11): an operator-split
+ * forward-Euler update of q in a launch of its own in front of the tracer sweep of either scheme, while q and hlay still
+ * belong to the same time level.  Per tracer t, layer l and cell p (E, N, W, S = neig(1|3|5|7, p)), all FP64, no
+ * contraction, in this order:
+ *   c(x)     = hlay(x,l) > 0 ? q(x,l) / hlay(x,l) : +0.0
+ *   kd       = kappa(t,l) * i_dl
+ *   G(b, x)  = hf > 0 ? (kd * hf) * (c(b) - c(x)) : +0.0,   hf = fmin(hlay(b,l), hlay(x,l))
+ *   Gu(p) = G(W(p), p)    Gu(E) = G(W(E), E)    Gv(p) = G(S(p), p)    Gv(N) = G(S(N), N)
+ *   div      = ((Gu(p) - Gu(E)) + (Gv(p) - Gv(N))) * i_dl
+ *   r        = ((div + source(t,l) * hlay(p,l)) - decay(t,l) * q(p,l)) * mk_n(p)
+ *   q_mix    = hlay(p,l) > 0 ? q(p,l) + dt * r : q(p,l)
+ *  - W(E) and S(N) are cell E's and N's own back links, as for Fu(E), Fv(N) above: the sentinel's links are 0.
+ *  - G(b, x) is the diffusive flux of content into x through the face it shares with b: div(kappa h grad c) in flux form.
+ *    The face is as thick as the thinner of its two cells.  A face next to land, a dry cell, the frame's edge or an open
+ *    boundary carries nothing, because hlay(0) = 0.  Every weight hf / hlay(p) is at most 1, so kappa*dt/dl^2 <= 1/4 makes
+ *    the new concentration a convex combination of the five old ones: a maximum principle, whatever the thickness contrast.
+ *  - decay is a rate in 1/s, source adds concentration per second.  source = 1 in the interior layers with a large decay in
+ *    layer 1 gives a ventilation age in seconds; decay alone a radioactive tracer.
+ *  - dt is the handle's dt, in steps 1-3 too.  rq is not touched: the multistep history stays the advective tendency.
+ *  - With q = hlay, decay = source = +0 and any kappa every c is exactly 1, every G is +0, r = +0 and q_mix = q: the
+ *    identity with hlay holds with diffusion on, under both schemes.
+ *  - The tracer moments' fu, fv remain the advective faces: the diffusive flux is not in their mean budget.
+ * beom_set_tracer_mixing: kappa (m2/s), decay, source are [ntrc][nlay] each (x[(l-1) + nlay*(t-1)]); NULL = all +0.  All
+ * NULL or all zero switches the mixing off: its array is freed and no launch follows, the step is what it was.  Between
+ * steps only, after beom_set_tracers (-3 otherwise).  Refused with -3 and a message, nothing touched: a value that is not
+ * finite, kappa < 0, kappa*dt/dl^2 > 0.25, decay < 0, decay*dt > 1 (the two caps are held to a few units of rounding, so
+ * that kappa = 0.25*dl*dl/dt passes).  beom_set_tracers with another count drops the mixing, the same count keeps it;
+ * uploads leave it alone.  beom_step and beom_step_phase (phase 1) then run the launch in front of the tracer sweep;
+ * beom_update_tracer_mixing is the launch on its own (-3 without mixing), and beom_update_tracers stays the advective sweep
+ * alone.  beom_info: "tracer_mixing" (0 | 1), "tracer_mix_launches" (all calls so far). */
+int beom_set_tracer_mixing(beom_handle h, const double *kappa, const double *decay, const double *source, char *errm, int errm_len);
+int beom_update_tracer_mixing(beom_handle h);
 
 /* ---- Lagrangian (isopycnal) floats carried by the layer velocities (no reference routine; DESIGN.md f-N7).  A float has a
  * position (x, y) in FP64 grid units and a fixed layer l.  Cell (i, j) spans [i-1, i] x [j-1, j]; u(p) sits on the cell's west
@@ -636,6 +668,10 @@ int beom_multi_set_tracers(beom_multi_handle m, int ntrc, char *errm, int errm_l
 /* beom_set_tracer_scheme on every band.  Scheme 2 reaches two rows; the four ghost rows and the exchange of q suffice, so
  * cut steps stay cut and no buffer changes.  (beom_multi_set_tracers refuses rings and rank-local handles as before.) */
 int beom_multi_set_tracer_scheme(beom_multi_handle m, int scheme, char *errm, int errm_len);
+/* beom_set_tracer_mixing with the same coefficients on every band.  The mixing reaches one row, in front of a sweep that
+ * reaches one or two: the four ghost rows still suffice, cut steps stay cut and no buffer changes.  Rings and rank-local
+ * handles are refused with -6, as by beom_multi_set_tracers. */
+int beom_multi_set_tracer_mixing(beom_multi_handle m, const double *kappa, const double *decay, const double *source, char *errm, int errm_len);
 int beom_multi_upload_tracers(beom_multi_handle m, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len);
 int beom_multi_download_tracers(beom_multi_handle m, double *q, double *rq, char *errm, int errm_len);
 

@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_dense_host.h",
                "beom_bands_host.h", "beom_plan.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -228,6 +228,12 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.beom_update_tracer_mixing.argtypes = [H]
         for name in TRACER_MIX_EXPORTS:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_tracer_vmixing"):  # (likewise: an older build has no vertical tracer mixing)
+        lib.beom_set_tracer_vmixing.argtypes = [H, dpp, cp, ci]
+        lib.beom_multi_set_tracer_vmixing.argtypes = [MH, dpp, cp, ci]
+        lib.beom_update_tracer_vmixing.argtypes = [H]
+        for name in TRACER_VMIX_EXPORTS:
+            getattr(lib, name).restype = ci
     if hasattr(lib, "beom_set_floats"):          # (likewise: an older build has no floats)
         lib.beom_set_floats.argtypes = [H, C.c_int64, ci, ci, cp, ci]
         lib.beom_upload_floats.argtypes = [H, dpp, dpp, ipp, cp, ci]
@@ -306,6 +312,7 @@ TRACER_MOMENT_EXPORTS = ("beom_set_tracer_moments", "beom_reset_tracer_moments",
                          "beom_download_tracer_moments", "beom_multi_set_tracer_moments", "beom_multi_reset_tracer_moments",
                          "beom_multi_download_tracer_moments")
 TRACER_MIX_EXPORTS = ("beom_set_tracer_mixing", "beom_update_tracer_mixing", "beom_multi_set_tracer_mixing")
+TRACER_VMIX_EXPORTS = ("beom_set_tracer_vmixing", "beom_update_tracer_vmixing", "beom_multi_set_tracer_vmixing")
 SERIES_EXPORTS = ("beom_series_count", "beom_set_series", "beom_sample_series", "beom_download_series", "beom_band_set_series",
                   "beom_multi_set_series", "beom_multi_download_series")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
@@ -331,7 +338,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -416,6 +423,24 @@ class _Tracers:
                 a = np.ascontiguousarray(np.broadcast_to(a[:, None] if a.ndim == 1 else a, want))
             co.append(a)
         self._check(self._trc("set_tracer_mixing")(self.h, _dp(co[0]), _dp(co[1]), _dp(co[2]), self._err, ERRLEN))
+
+    def set_tracer_vertical_mixing(self, kappa_v=None):
+        """Vertical (diapycnal) diffusion kappa_v (m2/s) of the tracers through the nlay - 1 interfaces of every water column,
+        implicit in the column, in a launch of its own between the lateral mixing and the tracer sweep
+        (beom_set_tracer_vmixing).  A scalar, [nlay-1] or [ntrc, nlay-1], broadcast to [ntrc, nlay-1]; there is no cap.  None
+        or all zero switches it off.  Between steps only, after set_tracers."""
+        if not hasattr(self.lib, "beom_set_tracer_vmixing"):
+            raise BeomError("this libbeom_hip.so has no vertical tracer mixing (beom_set_tracer_vmixing)")
+        a = kappa_v
+        if a is not None:
+            want = (self.ntrc, self.p.nlay - 1)
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim > 2 or (a.ndim == 1 and a.shape != want[1:]) or (a.ndim == 2 and a.shape != want):
+                raise BeomError("kappa_v of shape %s: a scalar, %s or %s expected" % (a.shape, want[1:], want))
+            a = np.ascontiguousarray(np.broadcast_to(a, want))
+            if a.size == 0:         # (no tracer or one layer: the library refuses in its own words, and reads no value)
+                a = np.zeros(1)
+        self._check(self._trc("set_tracer_vmixing")(self.h, _dp(a), self._err, ERRLEN))
 
     def _trc_array(self, a, tail=()):
         if a is None:
@@ -815,7 +840,8 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
         "plain_sweeps" (bit 0: the last step's u+v sweep ran its plain form, bit 1: its Montgomery sweep did),
         "vel_targets_zero" (1: the handle's velocity targets fnud[IX_U], fnud[IX_V] are +0 bit for bit, so the momentum sweeps
         never fetch them for a lane whose velocity is an exact zero), "tracers", "tracer_scheme" (1 upstream, 2 limited),
-        "tracer_mixing" (1: set_tracer_mixing is in force), "tracer_mix_launches" (mixing launches so far), "floats",
+        "tracer_mixing" (1: set_tracer_mixing is in force), "tracer_mix_launches" (mixing launches so far),
+        "tracer_vmixing" (1: set_tracer_vertical_mixing is in force), "tracer_vmix_launches" (its launches so far), "floats",
         "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
         "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
         "tracer_moment_launches", "series" (the series' level), "series_records" (records its recorder holds)."""
@@ -870,6 +896,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
     def update_h(self, gene, ramp, ctim): self._check(self.lib.beom_update_h(self.h, gene, ramp, ctim))
     def update_tracers(self, gene, ramp, ctim): self._check(self.lib.beom_update_tracers(self.h, gene, ramp, ctim))
     def update_tracer_mixing(self): self._check(self.lib.beom_update_tracer_mixing(self.h))
+    def update_tracer_vertical_mixing(self): self._check(self.lib.beom_update_tracer_vmixing(self.h))
     def update_mont(self, ilay=0): self._check(self.lib.beom_update_mont_rvor_pvor_dive_kine(self.h, ilay))
     def update_viscosity(self, ilay=0): self._check(self.lib.beom_update_viscosity(self.h, ilay))
     def update_u(self, ilay, gene, ramp, ctim): self._check(self.lib.beom_update_u(self.h, ilay, gene, ramp, ctim))

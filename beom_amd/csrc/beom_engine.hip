@@ -22,6 +22,7 @@
 #include "beom_tracers.h"
 #include "beom_tracers_lim.h"
 #include "beom_tracer_mix.h"
+#include "beom_tracer_vmix.h"
 #include "beom_floats.h"
 #include "beom_moments.h"
 #include "beom_tracer_moments.h"
@@ -183,6 +184,11 @@ struct beom_engine {
     double *trc_mix = nullptr;
     std::vector<void *> trc_mix_allocs;
     long long trc_mix_launches = 0;
+    // vertical diffusion of the tracers between the layers (beom_set_tracer_vmixing; beom_tracer_vmix.h): rk = 1 / (dt *
+    // kappa_v), [ntrc][nlay-1] on the device, null while it is off; the launches so far
+    double *trc_vmix = nullptr;
+    std::vector<void *> trc_vmix_allocs;
+    long long trc_vmix_launches = 0;
     // Lagrangian floats (beom_set_floats; beom_floats.h): positions, layers, rejected steps, stage 1's increment and
     // provisional position; the track recorder [record][3][float] with the step of every held record
     long long nflt = 0;
@@ -552,7 +558,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -816,10 +822,17 @@ static void launch_tracer_mix(beom_engine *E) {
     swp(E->trc_q, E->trc_q_alt);
     ++E->trc_mix_launches;
 }
+// vertical diffusion of the tracers (beom_tracer_vmix.h): all tracers in one launch, one thread per water column, q in place
+static void launch_tracer_vmix(beom_engine *E) {
+    const TrcVmixView m{E->ntrc, E->trc_q, E->trc_vmix};
+    pick_int<2, BEOM_MAX_LAYERS>(E->d.nlay, [&](auto nl) { LAUNCH_CTX((k_tracer_vmix<CellGather, nl>), (k_tracer_vmix<CellDense, nl>), 1, E->d, m); });
+    ++E->trc_vmix_launches;
+}
 // the tracer sweep of a step (beom_tracers.h): all tracers in one launch, in front of the step's update_h; a step of a
-// handle with mixing runs the mixing launch first, on the q and hlay of the same time level
+// handle with mixing runs the lateral mixing launch first, then the vertical one, on the q and hlay of the same time level
 static void launch_tracers(beom_engine *E, double gene, double ramp, double ctim, bool mix = true) {
     if (mix && E->trc_mix) launch_tracer_mix(E);
+    if (mix && E->trc_vmix) launch_tracer_vmix(E);
     TrcView tv{E->ntrc, E->trc_ctrg ? 1 : 0, E->trc_q, E->trc_q_alt, E->trc_rq[0], E->trc_rq[1], E->trc_ctrg};
     const int nz = E->d.nlay;
     // scheme 2 (beom_tracers_lim.h): the tiled kernel in the handle's tile geometry, or the table path
@@ -1045,6 +1058,7 @@ extern "C" {
 int beom_update_h(beom_handle E, double gene, double ramp, double ctim) { NEED_ARRAYS(E); launch_h(E, gene, ramp, ctim); return LAUNCHED(); }
 int beom_update_tracers(beom_handle E, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (E->ntrc < 1) return -3; launch_tracers(E, gene, ramp, ctim, false); return LAUNCHED(); }
 int beom_update_tracer_mixing(beom_handle E) { NEED_ARRAYS(E); if (E->ntrc < 1 || !E->trc_mix) return -3; launch_tracer_mix(E); return LAUNCHED(); }
+int beom_update_tracer_vmixing(beom_handle E) { NEED_ARRAYS(E); if (E->ntrc < 1 || !E->trc_vmix) return -3; launch_tracer_vmix(E); return LAUNCHED(); }
 int beom_update_mont_rvor_pvor_dive_kine(beom_handle E, int ilay) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_mont(E, ilay); return LAUNCHED(); }
 int beom_update_viscosity(beom_handle E, int ilay) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_visc(E, ilay); return LAUNCHED(); }
 int beom_update_u(beom_handle E, int ilay, double gene, double ramp, double ctim) { NEED_ARRAYS(E); if (ilay < 0 || ilay > E->d.nlay) return -3; launch_uv<true>(E, ilay, gene, ramp, ctim); return LAUNCHED(); }
@@ -1551,6 +1565,10 @@ static void free_tracer_mixing(beom_engine *E) {
     free_list(E->trc_mix_allocs);
     E->trc_mix = nullptr;
 }
+static void free_tracer_vmixing(beom_engine *E) {
+    free_list(E->trc_vmix_allocs);
+    E->trc_vmix = nullptr;
+}
 static void free_tracers(beom_engine *E) {
     free_list(E->trc_allocs);
     E->ntrc = 0;
@@ -1563,7 +1581,7 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); }        // (their arrays have the tracers' shape)
+    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); }        // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
@@ -1611,6 +1629,38 @@ int beom_set_tracer_mixing(beom_handle E, const double *kappa, const double *dec
     int rc;
     if (!E->trc_mix && (rc = alloc_plain(E, E->trc_mix_allocs, &E->trc_mix, co.size(), errm, errm_len))) { free_tracer_mixing(E); return rc; }
     HIP_TRY(hipMemcpyAsync(E->trc_mix, co.data(), co.size() * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+// Vertical diffusion (beom_tracer_vmix.h).  Everything is looked at before anything is touched; null or all zero switches it
+// off and frees the coefficients.  The device holds rk = 1 / (dt * kappa_v), +0 where kappa_v is 0: a closed interface.
+int beom_set_tracer_vmixing(beom_handle E, const double *kappa_v, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->ntrc < 1) { set_err(errm, errm_len, "beom_set_tracer_vmixing: the handle carries no tracer (beom_set_tracers comes first)"); return -3; }
+    const int nk = E->d.nlay - 1;
+    if (kappa_v && nk < 1) { set_err(errm, errm_len, "beom_set_tracer_vmixing: a handle with one layer has no interface to mix through"); return -3; }
+    const double dt = E->d.dt;
+    std::vector<double> rk(kappa_v ? (size_t)E->ntrc * nk : 0, 0.0);
+    bool any = false;
+    for (size_t i = 0; i < rk.size(); ++i) {
+        const double v = kappa_v[i];
+        const int t = (int)(i / nk) + 1, k = (int)(i % nk) + 1;
+        if (!std::isfinite(v)) { set_err(errm, errm_len, "beom_set_tracer_vmixing: kappa_v of tracer %d, interface %d is not finite", t, k); return -3; }
+        if (v < 0.0) { set_err(errm, errm_len, "beom_set_tracer_vmixing: kappa_v of tracer %d, interface %d is negative (%g)", t, k, v); return -3; }
+        if (v == 0.0) continue;                                 // (-0 counts as +0)
+        const double prod = dt * v;
+        const double r = 1.0 / prod;
+        if (!(std::isnormal(r) && r > 0.0)) { set_err(errm, errm_len, "beom_set_tracer_vmixing: kappa_v of tracer %d, interface %d: 1/(dt*kappa_v) = %g is no positive normal number (dt*kappa_v = %g)", t, k, r, prod); return -3; }
+        rk[i] = r;
+        any = true;
+    }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    if (!any) { free_tracer_vmixing(E); return 0; }
+    int rc;
+    if (!E->trc_vmix && (rc = alloc_plain(E, E->trc_vmix_allocs, &E->trc_vmix, rk.size(), errm, errm_len))) { free_tracer_vmixing(E); return rc; }
+    HIP_TRY(hipMemcpyAsync(E->trc_vmix, rk.data(), rk.size() * sizeof(double), hipMemcpyHostToDevice, E->stream));
     HIP_TRY(hipStreamSynchronize(E->stream));
     return 0;
 }
@@ -2057,6 +2107,8 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_scheme")) return E->trc_scheme;
     if (!strcmp(what, "tracer_mixing")) return E->trc_mix ? 1 : 0;
     if (!strcmp(what, "tracer_mix_launches")) return (int)std::min<long long>(E->trc_mix_launches, 2000000000ll);      // all calls so far
+    if (!strcmp(what, "tracer_vmixing")) return E->trc_vmix ? 1 : 0;
+    if (!strcmp(what, "tracer_vmix_launches")) return (int)std::min<long long>(E->trc_vmix_launches, 2000000000ll);      // all calls so far
     if (!strcmp(what, "floats")) return (int)std::min<long long>(E->nflt, 2000000000ll);
     if (!strcmp(what, "float_records")) return (int)E->flt_rec_tstp.size();
     if (!strcmp(what, "float_launches")) return (int)std::min<long long>(E->flt_launches, 2000000000ll);      // all calls so far

@@ -888,6 +888,18 @@ int beom_multi_set_tracer_mixing(beom_multi_handle M, const double *kappa, const
     return 0;
 }
 
+// beom_set_tracer_vmixing on every band: the same coefficients, looked at by band 0 before any band is touched.  A column
+// is its own cell's: the launch covers a band's whole window and the ghost rows come out as the neighbour's own rows do.
+int beom_multi_set_tracer_vmixing(beom_multi_handle M, const double *kappa_v, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracer_vmixing: an earlier step failed half way; destroy the handle"); return -30; }
+    M_RC(tracers_refused(M, "beom_multi_set_tracer_vmixing", errm, errm_len));
+    if (M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_vmixing: the handle carries no tracer (beom_multi_set_tracers comes first)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    for (int k = 0; k < M->n; ++k) M_RC(beom_set_tracer_vmixing(M->eng[k], kappa_v, errm, errm_len));
+    return 0;
+}
+
 int beom_multi_upload_tracers(beom_multi_handle M, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
     M_RC(tracers_refused(M, "beom_multi_upload_tracers", errm, errm_len));

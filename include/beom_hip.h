@@ -356,6 +356,52 @@ int beom_set_tracer_scheme(beom_handle h, int scheme, char *errm, int errm_len);
  * alone.  beom_info: "tracer_mixing" (0 | 1), "tracer_mix_launches" (all calls so far). */
 int beom_set_tracer_mixing(beom_handle h, const double *kappa, const double *decay, const double *source, char *errm, int errm_len);
 int beom_update_tracer_mixing(beom_handle h);
+/* Vertical (diapycnal) diffusion of the tracers between the layers of a water column (no reference routine; DESIGN.md
+ * f-N12): an operator-split backward-Euler update of q in a launch of its own, behind the lateral mixing and in front of the
+ * tracer sweep of either scheme, while q and hlay still belong to the same time level.  The unknowns are the FLUXES through
+ * the interfaces k = 1..nlay-1 (between layers k and k+1, 1 = top), not the concentrations.  Per cell p and tracer t, all
+ * FP64, no contraction, in this order:
+ *   m_l   = hlay(p,l) > 0
+ *   c_l   = m_l ? q_l / h_l : +0.0
+ *   b_l   = m_l ? 1.0 / h_l : +0.0                (once per cell, for every tracer)
+ *   rk(t,k) = 1.0 / (dt * kappa_v(t,k))           formed on the host in FP64 (product first, then reciprocal);
+ *                                                 +0.0 where kappa_v(t,k) == 0
+ *   open(k) = mk_n(p) > 0.5 && m_k && m_{k+1} && rk(t,k) > 0
+ *   forward, k = 1 .. nlay-1, with s_0 = 1.0, y_0 = +0.0:
+ *       R   = (0.5 * (h_k + h_{k+1})) * rk(t,k)
+ *       pp  = R + b_k * s_{k-1}
+ *       den = pp + b_{k+1}
+ *       inv = 1.0 / den
+ *       num = (c_k - c_{k+1}) + b_k * y_{k-1}
+ *       open(k):  g_k = b_{k+1} * inv;  y_k = num * inv;  s_k = pp * inv
+ *       else:     g_k = +0.0;           y_k = +0.0;       s_k = 1.0
+ *   back:  G_{nlay-1} = y_{nlay-1};   G_k = y_k + g_k * G_{k+1};   G_0 = G_nlay = +0.0
+ *   q'_l = m_l ? (q_l + G_{l-1}) - G_l : q_l
+ *  - G_k is the content moved from layer k into layer k+1 during the step.  It solves
+ *    G_k (R_k + b_k + b_{k+1}) - b_k G_{k-1} - b_{k+1} G_{k+1} = c_k - c_{k+1}, that is G = (dt kappa_v / hbar)(c'_k - c'_{k+1})
+ *    with c' = q'/h and hbar the mean of the two thicknesses: backward Euler in the column.
+ *  - The elimination carries s_k = 1 - g_k as pp/den: nothing nearly equal and positive is subtracted.
+ *  - No cap on kappa_v: the matrix's row sum is R_k >= 0, the scheme is unconditionally stable, and kappa_v -> infinity gives
+ *    the thickness-weighted column mean.
+ *  - Every G_k enters two layers with opposite sign: the column sum of q changes by rounding only.
+ *  - With q = hlay every c is exactly 1, every num, y and G is +0 and q' = q: the identity with hlay holds with vertical
+ *    mixing on, under both schemes and with lateral mixing.
+ *  - A dry layer, a land cell (mk_n = 0), the sentinel or kappa_v(t,k) = 0 closes an interface; the column falls into
+ *    independent pieces there.  A thin wet layer conducts: its resistance is its thickness.
+ *  - The error is rounding of the CONTENT: a few units of 2^-52 * (|q_l| + |G_{l-1}| + |G_l|).  A massless layer's
+ *    concentration is therefore accurate only to the rounding of the content that passes through it, as in any conservative
+ *    form.
+ *  - dt is the handle's dt, in steps 1-3 too.  rq is not touched.  q is updated in place: a column reads its own cell only.
+ * beom_set_tracer_vmixing: kappa_v (m2/s) is [ntrc][nlay-1], kappa_v[(k-1) + (nlay-1)*(t-1)].  NULL or all zero switches it
+ * off: the device array is freed and no launch follows, the step is what it was.  Between steps only, after beom_set_tracers.
+ * Refused with -3 and a message, nothing touched: a handle without tracers; a value that is not finite or is negative; a
+ * non-NULL kappa_v on a handle with nlay = 1; a kappa_v > 0 whose 1.0/(dt*kappa_v) is not a positive normal number (so that
+ * rk = 0 means "closed" and nothing else).  beom_set_tracers with another count drops it, the same count keeps it; uploads
+ * leave it alone.  beom_step and beom_step_phase (phase 1) then run: lateral mixing, vertical mixing, the sweep.
+ * beom_update_tracer_vmixing is the launch on its own (-3 without vertical mixing); beom_update_tracers stays the advective
+ * sweep alone.  beom_info: "tracer_vmixing" (0 | 1), "tracer_vmix_launches" (all calls so far). */
+int beom_set_tracer_vmixing(beom_handle h, const double *kappa_v, char *errm, int errm_len);
+int beom_update_tracer_vmixing(beom_handle h);
 
 /* ---- Lagrangian (isopycnal) floats carried by the layer velocities (no reference routine; DESIGN.md f-N7).  A float has a
  * position (x, y) in FP64 grid units and a fixed layer l.  Cell (i, j) spans [i-1, i] x [j-1, j]; u(p) sits on the cell's west
@@ -672,6 +718,11 @@ int beom_multi_set_tracer_scheme(beom_multi_handle m, int scheme, char *errm, in
  * reaches one or two: the four ghost rows still suffice, cut steps stay cut and no buffer changes.  Rings and rank-local
  * handles are refused with -6, as by beom_multi_set_tracers. */
 int beom_multi_set_tracer_mixing(beom_multi_handle m, const double *kappa, const double *decay, const double *source, char *errm, int errm_len);
+/* beom_set_tracer_vmixing with the same coefficients on every band; band 0 looks at them before any band is touched.  A
+ * column reads its own cell only: every band's launch covers its whole window, ghost rows included, which hold the
+ * neighbour's values bit for bit and so come out bit for bit; cut steps stay cut and no buffer changes.  Rings and
+ * rank-local handles are refused with -6, as by beom_multi_set_tracers. */
+int beom_multi_set_tracer_vmixing(beom_multi_handle m, const double *kappa_v, char *errm, int errm_len);
 int beom_multi_upload_tracers(beom_multi_handle m, const double *q, const double *rq, const double *ctrg, char *errm, int errm_len);
 int beom_multi_download_tracers(beom_multi_handle m, double *q, double *rq, char *errm, int errm_len);
 

@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_dense_host.h",
                "beom_bands_host.h", "beom_plan.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -281,6 +281,17 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.beom_multi_download_series.argtypes = [MH, dpp, ip, ip, cp, ci]
         for name in SERIES_EXPORTS:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_tracer_series"):   # (likewise: an older build has no tracer series)
+        ip = C.POINTER(ci)
+        lib.beom_tracer_series_count.argtypes = [ci, ci, ci]
+        lib.beom_set_tracer_series.argtypes = [H, ci, ci, ci, cp, ci]
+        lib.beom_band_set_tracer_series.argtypes = [H, ci, ci, ci, ci, ci, cp, ci]
+        lib.beom_sample_tracer_series.argtypes = [H]
+        lib.beom_download_tracer_series.argtypes = [H, dpp, ip, ip, cp, ci]
+        lib.beom_multi_set_tracer_series.argtypes = [MH, ci, ci, ci, cp, ci]
+        lib.beom_multi_download_tracer_series.argtypes = [MH, dpp, ip, ip, cp, ci]
+        for name in TRACER_SERIES_EXPORTS:
+            getattr(lib, name).restype = ci
     for name in ("beom_multi_create", "beom_multi_destroy", "beom_multi_count", "beom_multi_band",
                  "beom_multi_upload_state", "beom_multi_download_state", "beom_multi_step", "beom_multi_sync",
                  "beom_multi_stats", "beom_multi_create_ex", "beom_multi_describe", "beom_multi_engine",
@@ -315,6 +326,9 @@ TRACER_MIX_EXPORTS = ("beom_set_tracer_mixing", "beom_update_tracer_mixing", "be
 TRACER_VMIX_EXPORTS = ("beom_set_tracer_vmixing", "beom_update_tracer_vmixing", "beom_multi_set_tracer_vmixing")
 SERIES_EXPORTS = ("beom_series_count", "beom_set_series", "beom_sample_series", "beom_download_series", "beom_band_set_series",
                   "beom_multi_set_series", "beom_multi_download_series")
+TRACER_SERIES_EXPORTS = ("beom_tracer_series_count", "beom_set_tracer_series", "beom_sample_tracer_series",
+                         "beom_download_tracer_series", "beom_band_set_tracer_series", "beom_multi_set_tracer_series",
+                         "beom_multi_download_tracer_series")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
 
 EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "beom_info", "beom_download_diag", "beom_create", "beom_destroy", "beom_set_rigid_lid", "beom_download_pressure",
@@ -338,7 +352,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -675,7 +689,58 @@ class _Series:
         return out
 
 
-class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
+TRACER_SERIES_NAMES = ("inv", "var", "fu", "fv", "cmin", "cmax")
+
+
+class _TracerSeries:
+    """A record per sampled step of the tracers' row inventories, variance, face fluxes and bounds, kept on the device
+    (beom_set_tracer_series, include/beom_hip.h), with a level, stride and recorder of its own beside the series.  Shared by
+    Engine and MultiEngine."""
+
+    tracer_series_level = 0
+    tracer_series_records = 0
+
+    def set_tracer_series(self, level: int, stride: int = 1, records: int = 64):
+        """level 1: inv, var per tracer and layer; 2: and fu, fv; 3: and cmin, cmax; 0 frees.  `records`: what the recorder
+        holds between two download_tracer_series (a step call that would overflow it is refused).  Between steps only, after
+        set_tracers."""
+        fn = self.lib.beom_multi_set_tracer_series if self._ser_multi else self.lib.beom_set_tracer_series
+        self._check(fn(self.h, int(level), int(stride), int(records), self._err, ERRLEN))
+        self.tracer_series_level, self.tracer_series_records = int(level), (int(records) if level else 0)
+
+    def download_tracer_series(self) -> dict:
+        """The records held, oldest first, and empties the recorder.  count, tstp[n]; rows[n, M, cnt] (M = mm+1 rows in global
+        order); the views inv, var (row sums of q and of q*c) and, at level >= 2, fu, fv (row sums of the upstream face fluxes
+        through the W resp. S faces) and, at level 3, cmin, cmax (the concentration's bounds over the row's wet cells, +inf,
+        -inf where there is none), each [n, M, ntrc, nlay]; total[n, ntrc, nlay] = combine_integral_rows of inv; at level
+        >= 2 transport = dl * fv, the tracer transport through the south faces of row j."""
+        nl, M = self.p.nlay, self.p.mm + 1
+        fn = self.lib.beom_multi_download_tracer_series if self._ser_multi else self.lib.beom_download_tracer_series
+        lv = self.info("tracer_series")                                  # (set_tracers with another count frees it)
+        if lv < 1:                                                       # (the library says why)
+            self._check(fn(self.h, None, None, None, self._err, ERRLEN))
+            raise BeomError("download_tracer_series: the handle keeps no tracer series (set_tracer_series)")
+        self.tracer_series_level = lv
+        nq = 2 * lv
+        cnt = self.lib.beom_tracer_series_count(self.ntrc, nl, lv)
+        rows = np.zeros((max(self.tracer_series_records, 1), M, cnt))
+        tstp = (C.c_int * max(self.tracer_series_records, 1))()
+        count = C.c_int(0)
+        self._check(fn(self.h, _dp(rows), tstp, C.byref(count), self._err, ERRLEN))
+        n = count.value
+        rows = rows[:n].copy()
+        q = rows.reshape(n, M, self.ntrc, nl, nq)
+        out = {"count": n, "tstp": np.array(list(tstp)[:n], dtype=np.int64), "rows": rows}
+        for m in range(nq):
+            out[TRACER_SERIES_NAMES[m]] = q[..., m]
+        out["total"] = np.array([combine_integral_rows(np.ascontiguousarray(r.reshape(M, self.ntrc * nl)))
+                                 for r in out["inv"]]).reshape(n, self.ntrc, nl)
+        if lv >= 2:
+            out["transport"] = float(self.p.dl) * out["fv"]
+        return out
+
+
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
@@ -844,7 +909,8 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
         "tracer_vmixing" (1: set_tracer_vertical_mixing is in force), "tracer_vmix_launches" (its launches so far), "floats",
         "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
         "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
-        "tracer_moment_launches", "series" (the series' level), "series_records" (records its recorder holds)."""
+        "tracer_moment_launches", "series" (the series' level), "series_records" (records its recorder holds), "tracer_series" (the tracer series' level),
+        "tracer_series_records"."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))
@@ -915,11 +981,18 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
         if rc != 0:
             raise BeomError("beom_hip error %d: beom_sample_series (series set? recorder full?)" % rc)
 
+    def sample_tracer_series(self):
+        """Per-sweep entry: one record of the tracers and the state as they stand, under the last step's number, whatever the
+        stride."""
+        rc = self.lib.beom_sample_tracer_series(self.h)
+        if rc != 0:
+            raise BeomError("beom_hip error %d: beom_sample_tracer_series (tracer series set? recorder full?)" % rc)
+
     def rebuild_fluxes(self): self._check(self.lib.beom_rebuild_fluxes(self.h))
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""

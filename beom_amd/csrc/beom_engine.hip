@@ -26,6 +26,7 @@
 #include "beom_floats.h"
 #include "beom_moments.h"
 #include "beom_tracer_moments.h"
+#include "beom_tracer_series.h"
 #include "beom_dense_host.h"
 #include "beom_plan.h"
 
@@ -225,6 +226,14 @@ struct beom_engine {
     double *ser_rec = nullptr;
     std::vector<int> ser_tstp;         // (its size = the records held)
     std::vector<void *> ser_allocs;
+    // tracer series (beom_set_tracer_series; beom_tracer_series.h): a recorder [nrec][tser_rows][ntrc*nlay*2*level] of its
+    // own, with level, stride and rows of its own; the chunk partials of tser_batch rows at a time (kTracerSeriesScratch)
+    int tser_level = 0, tser_stride = 1, tser_nrec = 0, tser_jlo = 1, tser_rows = 0, tser_batch = 0;
+    int tser_batch_opt = 0;            // option "tracer_series_batch": rows per launch (0 = by the bound on the scratch)
+    bool tser_by_caller = false;       // a band: beom_step takes no record by itself (beom_band_set_tracer_series)
+    double *tser_rec = nullptr, *tser_part = nullptr;
+    std::vector<int> tser_tstp;        // (its size = the records held)
+    std::vector<void *> tser_allocs;
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -558,7 +567,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs, &E->tser_allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -923,6 +932,33 @@ static void launch_series(beom_engine *E, int tstp) {
                        (const double *)E->integ_part, rec, count, nch, nchp2);
     E->ser_tstp.push_back(tstp);
 }
+// one record of the tracer series (beom_tracer_series.h) of q, hlay, h_u, h_v as they stand into the next free slot, under step
+// tstp: tser_batch rows per launch, every row finished on its own
+static bool tracer_series_due(const beom_engine *E, int tstp) {
+    return E->tser_level > 0 && tstp % E->tser_stride == 0 && (int)E->tser_tstp.size() < E->tser_nrec;
+}
+static void launch_tracer_series(beom_engine *E, int tstp) {
+    const DevView &d = E->d;
+    const int nq = 2 * E->tser_level, per = E->ntrc * d.nlay, cnt = per * nq, nch = (d.L + 63) / 64;
+    int nchp2 = 1, width = 1;
+    while (nchp2 < nch) nchp2 <<= 1;
+    while (width < d.L && width < 64) width <<= 1;
+    double *rec = E->tser_rec + E->tser_tstp.size() * (size_t)E->tser_rows * cnt;
+    const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
+    for (int r0 = 0; r0 < E->tser_rows; r0 += E->tser_batch) {
+        const int nr = std::min(E->tser_batch, E->tser_rows - r0);
+        const dim3 g((unsigned)nch, (unsigned)((nr + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
+        pick_int<1, 3>(E->tser_level, [&](auto lv) {
+            pick([&](auto dense) {
+                hipLaunchKernelGGL((k_tracer_series_rows<dense, lv>), g, b, 0, E->stream, d, (const double *)E->trc_q, E->ntrc, E->tser_jlo + r0, nr,
+                                   width, E->integ_xper, E->integ_yper, map, E->tser_part);
+            }, E->dense);
+        });
+        hipLaunchKernelGGL(k_tracer_series_chunks, dim3((unsigned)nr, (unsigned)per), dim3(64), 0, E->stream,
+                           (const double *)E->tser_part, rec + (size_t)r0 * cnt, cnt, nq, nch, nchp2);
+    }
+    E->tser_tstp.push_back(tstp);
+}
 static void launch_mont(beom_engine *E, int ilay) {
     if (ilay == 0 && E->d.nlay <= 8) {         // all layers of a column in one thread: instantiated for 1..8 layers
         if (E->dense) pick_int<1, 8>(E->d.nlay, [&](auto n) { hipLaunchKernelGGL((k_update_mont_all<CellDense, n>), CellDense::grid(E->d, 1), dim3(BEOM_BLOCK), 0, E->stream, E->d); });
@@ -1155,6 +1191,7 @@ static void one_step(beom_engine *E, const StepPlan &p, int flt = -1) {
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
     if (!E->ser_by_caller && series_due(E, tstp)) launch_series(E, tstp);
+    if (!E->tser_by_caller && tracer_series_due(E, tstp)) launch_tracer_series(E, tstp);
 }
 
 // rows [jlo, jlo+nrows) of hlay,u,v,h_u,h_v  ->  dbuf (device memory, 5*nlay*nrows*(lm+1) doubles); the *2 forms move a second
@@ -1202,6 +1239,10 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
         !recorder_holds(tstp_first, nsteps, E->ser_stride, E->ser_tstp.size(), E->ser_nrec, errm, errm_len,
                         "beom_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
                         "empty it with beom_download_series, or take fewer steps per call")) return -3;
+    if (E->tser_level > 0 && !E->tser_by_caller &&
+        !recorder_holds(tstp_first, nsteps, E->tser_stride, E->tser_tstp.size(), E->tser_nrec, errm, errm_len,
+                        "beom_step: steps %d..%d would write %lld records of the tracer series (stride %d) but the recorder holds %lld of %d: "
+                        "empty it with beom_download_tracer_series, or take fewer steps per call")) return -3;
     HIP_TRY(hipSetDevice(E->device));
     for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp)      // (the facts move with the steps: mont_levels_valid)
         one_step(E, beom_plan::plan_step(facts_of(E), tstp, tres, dtd8, dt_r, rsta, n_3d),
@@ -1559,6 +1600,82 @@ int beom_download_series(beom_handle E, double *rows, int *tstp, int *count, cha
     return 0;
 }
 
+// ---- tracer series (beom_tracer_series.h) ---------------------------------------------------------------------------------
+// The chunk partials of a launch stay under this many bytes: a record is taken in batches of rows (whole workgroups of
+// BEOM_TILE_Y rows; never fewer than one), every row finished on its own, so the batches cannot change a bit.
+constexpr size_t kTracerSeriesScratch = 64u << 20;
+
+int beom_tracer_series_count(int ntrc, int nlay, int level) { return ntrc * nlay * 2 * level; }
+
+static void tracer_series_free(beom_engine *E) {
+    free_list(E->tser_allocs);
+    E->tser_level = 0; E->tser_stride = 1; E->tser_nrec = 0; E->tser_jlo = 1; E->tser_rows = 0; E->tser_batch = 0; E->tser_by_caller = false;
+    E->tser_rec = E->tser_part = nullptr;
+    E->tser_tstp.clear();
+}
+
+// level 0 frees; else a recorder of nrec records of local rows jlo .. jlo+nrows-1.  A failed allocation leaves level 0
+static int tracer_series_set(beom_engine *E, const char *who, int level, int stride, int nrec, int jlo, int nrows, bool by_caller,
+                             char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (level < 0 || level > 3 || (level > 0 && (stride < 1 || nrec < 1))) {
+        set_err(errm, errm_len, "%s: level %d, stride %d, %d records (level 0..3, stride >= 1, records >= 1)", who, level, stride, nrec);
+        return -3;
+    }
+    if (level > 0 && E->ntrc < 1) { set_err(errm, errm_len, "%s: the handle carries no tracer (beom_set_tracers comes first)", who); return -3; }
+    const DevView &d = E->d;
+    if (level > 0 && (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M)) { set_err(errm, errm_len, "%s: rows %d..%d outside 1..%d", who, jlo, jlo + nrows - 1, d.M); return -3; }
+    if (level > 0 && pow2_ceil((d.L + 63) / 64) / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    tracer_series_free(E);
+    if (level == 0) return 0;
+    const size_t cnt = (size_t)beom_tracer_series_count(E->ntrc, d.nlay, level), per_row = (size_t)((d.L + 63) / 64) * cnt;
+    size_t batch = E->tser_batch_opt > 0 ? (size_t)E->tser_batch_opt : kTracerSeriesScratch / (per_row * sizeof(double));
+    batch = std::max<size_t>(batch / BEOM_TILE_Y * BEOM_TILE_Y, BEOM_TILE_Y);
+    batch = std::min<size_t>(batch, (size_t)nrows);
+    int rc = ensure_cellmap(E, errm, errm_len);
+    if (!rc) rc = alloc_plain(E, E->tser_allocs, &E->tser_part, batch * per_row, errm, errm_len, false);
+    if (!rc) rc = alloc_aligned(E, E->tser_allocs, &E->tser_rec, (size_t)nrec * nrows * cnt, errm, errm_len);
+    if (rc) { tracer_series_free(E); return rc; }
+    E->tser_level = level; E->tser_stride = stride; E->tser_nrec = nrec; E->tser_jlo = jlo; E->tser_rows = nrows; E->tser_batch = (int)batch;
+    E->tser_by_caller = by_caller;
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int beom_set_tracer_series(beom_handle E, int level, int stride, int nrec, char *errm, int errm_len) {
+    return tracer_series_set(E, "beom_set_tracer_series", level, stride, nrec, 1, E ? E->d.M : 0, false, errm, errm_len);
+}
+
+int beom_band_set_tracer_series(beom_handle E, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len) {
+    return tracer_series_set(E, "beom_band_set_tracer_series", level, stride, nrec, jlo, nrows, true, errm, errm_len);
+}
+
+int beom_sample_tracer_series(beom_handle E) {
+    if (!E) return -1;
+    if (E->tser_level < 1 || (int)E->tser_tstp.size() >= E->tser_nrec) return -3;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    launch_tracer_series(E, E->last_tstp);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int beom_download_tracer_series(beom_handle E, double *rows, int *tstp, int *count, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (E->tser_level < 1) { set_err(errm, errm_len, "beom_download_tracer_series: the handle keeps no tracer series (beom_set_tracer_series)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t n = E->tser_tstp.size(), per = (size_t)E->tser_rows * beom_tracer_series_count(E->ntrc, E->d.nlay, E->tser_level);
+    if (rows && n) {
+        HIP_TRY(hipMemcpyAsync(rows, E->tser_rec, n * per * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+        HIP_TRY(hipStreamSynchronize(E->stream));
+        HIP_TRY(hipGetLastError());
+    }
+    if (tstp) std::copy(E->tser_tstp.begin(), E->tser_tstp.end(), tstp);
+    if (count) *count = (int)n;
+    E->tser_tstp.clear();
+    return 0;
+}
+
 // ---- passive tracers (beom_tracers.h) -----------------------------------------------------------------------------------
 static void accum_free(Accum &A);
 static void free_tracer_mixing(beom_engine *E) {
@@ -1581,7 +1698,7 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); }        // (their arrays have the tracers' shape)
+    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); tracer_series_free(E); }        // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
@@ -2116,6 +2233,8 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_moments")) return E->tmom.level;
     if (!strcmp(what, "tracer_moment_samples")) return (int)std::min<long long>(E->tmom.count, 2000000000ll);
     if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom.launches, 2000000000ll);     // all calls so far
+    if (!strcmp(what, "tracer_series")) return E->tser_level;
+    if (!strcmp(what, "tracer_series_records")) return (int)E->tser_tstp.size();
     if (!strcmp(what, "series")) return E->ser_level;
     if (!strcmp(what, "series_records")) return (int)E->ser_tstp.size();
     if (!strcmp(what, "moments")) return E->mom.level;
@@ -2143,6 +2262,7 @@ int beom_set_option(beom_handle E, const char *name, int value) {
     else if (!strcmp(name, "mont_history")) E->mont_history = value != 0;
     else if (!strcmp(name, "plain_sweeps")) E->plain_sweeps = value != 0;
     else if (!strcmp(name, "moments_by_caller")) E->mom_by_caller = value != 0;
+    else if (!strcmp(name, "tracer_series_batch")) E->tser_batch_opt = value > 0 ? value : 0;      // (looked at by the next beom_set_tracer_series)
     else return -3;
     return 0;
 }

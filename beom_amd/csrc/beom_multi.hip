@@ -285,6 +285,7 @@ struct beom_multi {
     // moments' sample is; the steps of the records held (every band holds as many)
     struct Series { int level = 0, stride = 1, nrec = 0, due = 0; std::vector<int> tstp; };
     Series ser;
+    Series tser;                   // the tracer series likewise (beom_multi_set_tracer_series)
     // Lagrangian floats on the bands (beom_multi_set_floats): every band holds all nflt slots; flt_mode is the float launch
     // owed where the main streams next join the exchange (0 none, 1 stage 1, 3 stage 2 + stage 1 of the next step)
     long long nflt = 0;
@@ -852,7 +853,7 @@ int beom_multi_set_tracers(beom_multi_handle M, int ntrc, char *errm, int errm_l
     M_RC(tracers_refused(M, "beom_multi_set_tracers", errm, errm_len));
     M_RC(beom_multi_sync(M, errm, errm_len));
     for (int k = 0; k < M->n; ++k) M_RC(beom_set_tracers(M->eng[k], ntrc, errm, errm_len));
-    if (ntrc != M->ntrc) M->tmom = {};       // (the bands freed their tracer moments)
+    if (ntrc != M->ntrc) { M->tmom = {}; M->tser = {}; }       // (the bands freed their tracer moments and tracer series)
     M->ntrc = ntrc;
     if (M->nb == 1) return 0;
     // the exchange buffers for 5 + ntrc fields (nothing is in flight after the sync)
@@ -1429,6 +1430,56 @@ int beom_multi_download_series(beom_multi_handle M, double *rows, int *tstp, int
     return 0;
 }
 
+// Tracer series (beom_tracer_series.h) of a frame cut into bands: the series' placement, the tracers' refusals.
+int beom_multi_set_tracer_series(beom_multi_handle M, int level, int stride, int nrec, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracer_series: an earlier step failed half way; destroy the handle"); return -30; }
+    if (level < 0 || level > 3 || (level > 0 && (stride < 1 || nrec < 1))) {
+        m_err(errm, errm_len, "beom_multi_set_tracer_series: level %d, stride %d, %d records (level 0..3, stride >= 1, records >= 1)", level, stride, nrec);
+        return -3;
+    }
+    M_RC(tracers_refused(M, "beom_multi_set_tracer_series", errm, errm_len));
+    if (level > 0 && M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_series: the handle carries no tracer (beom_multi_set_tracers comes first)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    M->tser = {};
+    int rc = 0;
+    for (int k = 0; k < M->n && !rc; ++k) {
+        const Band &s = M->band[k];
+        rc = multi_whole(M) ? beom_set_tracer_series(M->eng[k], level, stride, nrec, errm, errm_len)
+                            : beom_band_set_tracer_series(M->eng[k], level, stride, nrec, s.gs + 1, s.nown(), errm, errm_len);
+    }
+    if (rc) {                           // all bands or none
+        for (int k = 0; k < M->n; ++k) (void)beom_set_tracer_series(M->eng[k], 0, 1, 1, nullptr, 0);
+        return rc;
+    }
+    M->tser.level = level; M->tser.stride = stride; M->tser.nrec = nrec;
+    return 0;
+}
+
+int beom_multi_download_tracer_series(beom_multi_handle M, double *rows, int *tstp, int *count, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    M_RC(tracers_refused(M, "beom_multi_download_tracer_series", errm, errm_len));
+    if (M->tser.level < 1) { m_err(errm, errm_len, "beom_multi_download_tracer_series: the handle keeps no tracer series (beom_multi_set_tracer_series)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (multi_whole(M)) return beom_download_tracer_series(M->eng[0], rows, tstp, count, errm, errm_len);
+    const size_t n = M->tser.tstp.size(), cnt = (size_t)beom_tracer_series_count(M->ntrc, M->P.nlay, M->tser.level), Mg = (size_t)M->P.mm + 1;
+    if (rows) std::fill(rows, rows + n * Mg * cnt, 0.0);
+    for (int k = 0; k < M->n; ++k) {
+        const Band &s = M->band[k];
+        const size_t per = (size_t)s.nown() * cnt;
+        std::vector<double> a(rows ? n * per : 0);
+        int held = 0;
+        M_RC(beom_download_tracer_series(M->eng[k], rows ? ptr(a) : nullptr, nullptr, &held, errm, errm_len));
+        if ((size_t)held != n) { m_err(errm, errm_len, "beom_multi_download_tracer_series: band %d holds %d records, the handle %zu", s.index, held, n); return -3; }
+        for (size_t r = 0; r < n && rows; ++r)
+            std::copy(a.begin() + r * per, a.begin() + (r + 1) * per, rows + (r * Mg + (size_t)(s.own0 - 1)) * cnt);
+    }
+    if (tstp) std::copy(M->tser.tstp.begin(), M->tser.tstp.end(), tstp);
+    if (count) *count = (int)n;
+    M->tser.tstp.clear();
+    return 0;
+}
+
 int beom_multi_upload_local(beom_multi_handle M, const beom_state *win, const beom_state *orphan, char *errm, int errm_len) {
     if (!M || !win) { m_err(errm, errm_len, "null argument"); return -1; }
     if (!M->local_mode) { m_err(errm, errm_len, "beom_multi_upload_local: this handle was created from global arrays"); return -3; }
@@ -1510,6 +1561,12 @@ static int multi_sample_due(beom_multi *M, char *errm, int errm_len) {
             if (beom_sample_series(M->eng[k])) { m_err(errm, errm_len, "beom_sample_series failed on band %d (step %d)", M->band[k].index, M->ser.due); return -3; }
         M->ser.tstp.push_back(M->ser.due);
         M->ser.due = 0;
+    }
+    if (M->tser.due) {
+        for (int k = 0; k < M->n; ++k)
+            if (beom_sample_tracer_series(M->eng[k])) { m_err(errm, errm_len, "beom_sample_tracer_series failed on band %d (step %d)", M->band[k].index, M->tser.due); return -3; }
+        M->tser.tstp.push_back(M->tser.due);
+        M->tser.due = 0;
     }
     return 0;
 }
@@ -1657,6 +1714,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
     for (beom_multi::Moments *m : {&M->mom, &M->tmom})
         if (m->level > 0 && t % m->stride == 0) m->due = t;
     if (M->ser.level > 0 && t % M->ser.stride == 0) M->ser.due = t;
+    if (M->tser.level > 0 && t % M->tser.stride == 0) M->tser.due = t;
     if (M->nflt > 0) M->flt_mode = 3;
     return 0;
 }
@@ -1681,6 +1739,17 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
             return -3;
         }
     }
+    if (M->tser.level > 0) {
+        long long due = 0;
+        for (int t = tstp_first; t < tstp_first + nsteps; ++t) due += t % M->tser.stride == 0;
+        const long long held = (long long)M->tser.tstp.size();
+        if (held + due > M->tser.nrec) {
+            m_err(errm, errm_len, "beom_multi_step: steps %d..%d would write %lld records of the tracer series (stride %d) but the recorder holds %lld of %d: "
+                  "empty it with beom_multi_download_tracer_series, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
+                  M->tser.stride, held, M->tser.nrec);
+            return -3;
+        }
+    }
     M->flt_mode = (M->nflt > 0 && nsteps > 0) ? 1 : 0;          // stage 1 alone in front of the call's first step
     for (int t = tstp_first; t < tstp_first + nsteps; ++t) {
         const int rc = multi_one_step(M, t, tres, dtd8, dt_r, rsta, n_3d, errm, errm_len);
@@ -1691,7 +1760,7 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
             return rc;
         }
     }
-    if (M->mom.due || M->tmom.due || M->ser.due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
+    if (M->mom.due || M->tmom.due || M->ser.due || M->tser.due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
         M_RC(multi_join_exchange(M, errm, errm_len));
         M_RC(multi_sample_due(M, errm, errm_len));
         if (M->flt_mode) {

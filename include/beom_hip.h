@@ -573,6 +573,54 @@ int beom_sample_series(beom_handle h);
 int beom_download_series(beom_handle h, double *rows, int *tstp, int *count, char *errm, int errm_len);
 int beom_band_set_series(beom_handle h, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len);
 
+/* ---- Tracer series: a record per sampled step of the tracers' row inventories, variance, face fluxes and bounds, kept on the
+ * device (no reference routine): how much of a tracer is where, how fast it crosses a latitude, how quickly its variance is
+ * mixed away and whether it has left its bounds, without a download.  A recorder of its own beside the series, as the tracer
+ * moments stand beside the moments: level, stride and records are independent of beom_set_series, beom_set_moments and
+ * beom_set_tracer_moments.
+ * Sampled are q, hlay, h_u, h_v as they stand at the end of a step, exactly what the next step's tracer sweep reads (where
+ * the tracer-moment sample stands).  For tracer t, layer l and packed cell p with W, S = neig(5|7, p), all FP64 without
+ * contraction (trc_conc, trc_face: the sweep's own, "Passive tracers" above):
+ *   x_q  = q(p,l,t)
+ *   c    = hlay(p,l) > 0 ? q(p,l,t) / hlay(p,l) : +0.0
+ *   x_v  = x_q * c                          the product rounded, then summed: its row sum is sum h c^2, which with the
+ *                                           inventory gives the variance whose decay measures mixing
+ *   x_fu = h_u(p,l) * cf between W and p    the upstream face of the tracer moments (x_fu, x_fv there)
+ *   x_fv = h_v(p,l) * cf between S and p
+ *   x_b  = c + 0.0                          enters the bounds only where the position is live and hlay(p,l) > 0
+ * One record is rows[(j-1)*cnt + ((t*nlay + (l-1))*nq + m)] for the handle's rows j = 1..M (M = mm+1), t = 0..ntrc-1,
+ * cnt = beom_tracer_series_count(ntrc, nlay, level) = ntrc * nlay * nq:
+ *   level 1, nq = 2:  m = 0 inv = sum x_q, m = 1 var = sum x_v   (own-cell loads only)
+ *   level 2, nq = 4:  and m = 2 fu = sum x_fu, m = 3 fv = sum x_fv
+ *   level 3, nq = 6:  and m = 4 cmin, m = 5 cmax
+ * Sums (m = 0..3): the integrals' live rule and order of summation, unchanged.  A position contributes +0.0 where there is no
+ * packed cell, on the duplicated column lm+1 of a frame periodic in x and on row mm+1 of one periodic in y; a row is summed
+ * by the pairwise tree over the aligned column index, padded with +0.0 to a power of two.  Bounds (m = 4, 5): the minimum
+ * and maximum of x_b over the live positions of the row with hlay(p,l) > 0.  The + 0.0 turns a -0 into +0, so no signed zero
+ * enters and the result does not depend on the order of comparison; a row with no live wet cell of that layer holds +inf,
+ * -inf; NaNs are not considered.  The bits do not depend on the handle kind, the tile geometry, the division into calls or
+ * the cut into bands.  dl * fv is the tracer transport through the south faces of row j.  Under scheme 2 the faces are still
+ * the upstream ones; diffusive and diapycnal fluxes are not in fu, fv.
+ * A record is written behind every step with tstp % stride == 0, beside the other samples, straight into the next slot of a
+ * device buffer [nrec][M][cnt]; the host keeps the step numbers.  beom_step refuses with -3, before launching anything, a
+ * call whose steps would overflow the recorder (the message names beom_download_tracer_series).  beom_sample_tracer_series:
+ * one record by hand, under the number of the handle's last step; -3 on a full recorder or without a tracer series.
+ * beom_download_tracer_series copies the filled records (rows[n][M][cnt], oldest first) and their steps, then sets the count
+ * to 0; any of rows, tstp, count may be NULL; -3 without a tracer series.  Uploads leave the recorder alone; beom_set_tracers
+ * with another count frees it.  beom_set_tracer_series: level 0 frees; other arguments reallocate and empty; between steps
+ * only; -3 for a level outside 0..3, stride < 1, nrec < 1 or a handle without tracers; -4 for rows too long for the
+ * integrals; a failed allocation leaves the handle without a tracer series.  Every single handle that carries tracers keeps
+ * one: dense, embedded, the table path, svis > 0, open boundaries (variant = 1 and the rigid lid refuse tracers).  A handle
+ * without a tracer series launches exactly what it launched before.  beom_info: "tracer_series" (the level),
+ * "tracer_series_records" (records held).  Option "tracer_series_batch" (beom_set_option, read by the next
+ * beom_set_tracer_series): rows per launch, 0 = as many as keep the chunk partials under 64 MiB; the bits do not depend on
+ * it.  beom_band_set_tracer_series is the band-side piece (local rows jlo..jlo+nrows-1, beom_step takes no record by itself). */
+int beom_tracer_series_count(int ntrc, int nlay, int level);      /* host only: ntrc * nlay * 2 * level */
+int beom_set_tracer_series(beom_handle h, int level, int stride, int nrec, char *errm, int errm_len);
+int beom_sample_tracer_series(beom_handle h);
+int beom_download_tracer_series(beom_handle h, double *rows, int *tstp, int *count, char *errm, int errm_len);
+int beom_band_set_tracer_series(beom_handle h, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len);
+
 /* ---- Several GPUs: the frame cut into bands of rows (SURVEY §8b "Threading", §8e) -------------
  * No reference counterpart (the reference is OpenMP only).  The whole DENSE frame (ndeg = (lm+1)(mm+1))
  * is cut into bands of rows, one band per HIP device, each an ordinary slab handle with 4 ghost rows
@@ -820,6 +868,15 @@ int beom_multi_integral_rows_local(beom_multi_handle m, int *own0, int *own1, do
  * rows are nowhere assembled.  One band that is the whole frame forwards to beom_set_series etc. */
 int beom_multi_set_series(beom_multi_handle m, int level, int stride, int nrec, char *errm, int errm_len);
 int beom_multi_download_series(beom_multi_handle m, double *rows, int *tstp, int *count, char *errm, int errm_len);
+
+/* Tracer series (see beom_set_tracer_series), placed like the series: every band records its OWNED rows on its main stream
+ * behind the wait for that step's ghost rows, so q(S) and hlay(S) of a band's first owned row are landed ghosts; cut steps
+ * stay cut and beom_multi_stats is the same with and without it.  beom_multi_step refuses an overflowing call with -3 before
+ * launching anything.  The download places the bands' rows at their global rows: rows[n][mm+1][cnt].  -6 where the bands
+ * carry no tracers (rings, handles that hold one band's window), -3 without tracers.  One band that is the whole frame
+ * forwards to beom_set_tracer_series etc. */
+int beom_multi_set_tracer_series(beom_multi_handle m, int level, int stride, int nrec, char *errm, int errm_len);
+int beom_multi_download_tracer_series(beom_multi_handle m, double *rows, int *tstp, int *count, char *errm, int errm_len);
 
 #ifdef __cplusplus
 }

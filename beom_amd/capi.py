@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_harmonics.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_dense_host.h",
                "beom_bands_host.h", "beom_plan.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -270,6 +270,16 @@ def load(path: Optional[str] = None) -> C.CDLL:
         getattr(lib, "beom_sample_" + stem).argtypes = [H]
         for name in names:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_harmonics"):       # (likewise: an older build has no harmonics)
+        ip, llp = C.POINTER(ci), C.POINTER(C.c_longlong)
+        lib.beom_harmonic_weights.argtypes = [cd, cd, dpp, dpp]
+        lib.beom_sample_harmonics.argtypes = [H, cd]
+        for pre, T, err in (("beom_", H, []), ("beom_multi_", MH, [cp, ci])):
+            getattr(lib, pre + "set_harmonics").argtypes = [T, ci, dpp, ci, ci, cp, ci]
+            getattr(lib, pre + "reset_harmonics").argtypes = [T] + err
+            getattr(lib, pre + "download_harmonics").argtypes = [T, dpp, dpp, dpp, dpp, llp, ip, ip, cp, ci]
+        for name in HARMONIC_EXPORTS:
+            getattr(lib, name).restype = ci
     if hasattr(lib, "beom_set_series"):          # (likewise: an older build has no series)
         ip = C.POINTER(ci)
         lib.beom_series_count.argtypes = [ci, ci]
@@ -322,6 +332,9 @@ MOMENT_EXPORTS = ("beom_set_moments", "beom_reset_moments", "beom_sample_moments
 TRACER_MOMENT_EXPORTS = ("beom_set_tracer_moments", "beom_reset_tracer_moments", "beom_sample_tracer_moments",
                          "beom_download_tracer_moments", "beom_multi_set_tracer_moments", "beom_multi_reset_tracer_moments",
                          "beom_multi_download_tracer_moments")
+HARMONIC_EXPORTS = ("beom_harmonic_weights", "beom_set_harmonics", "beom_reset_harmonics", "beom_sample_harmonics",
+                    "beom_download_harmonics", "beom_multi_set_harmonics", "beom_multi_reset_harmonics",
+                    "beom_multi_download_harmonics")
 TRACER_MIX_EXPORTS = ("beom_set_tracer_mixing", "beom_update_tracer_mixing", "beom_multi_set_tracer_mixing")
 TRACER_VMIX_EXPORTS = ("beom_set_tracer_vmixing", "beom_update_tracer_vmixing", "beom_multi_set_tracer_vmixing")
 SERIES_EXPORTS = ("beom_series_count", "beom_set_series", "beom_sample_series", "beom_download_series", "beom_band_set_series",
@@ -352,7 +365,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -614,6 +627,87 @@ class _Moments(_Accum):
                                     lambda q, m: np.stack([q[k] - m[a] * m[b] for k, (a, b) in enumerate(MOMENT_PAIRS)]))
 
 
+BEOM_MAX_HARMONICS = 4
+
+
+def harmonic_weights(omega: float, ctim: float):
+    """beom_harmonic_weights (host only, no device): (cos, sin) of the FP64 product omega*ctim, the weights of a sample."""
+    cw, sw = C.c_double(0.0), C.c_double(0.0)
+    rc = load().beom_harmonic_weights(float(omega), float(ctim), C.byref(cw), C.byref(sw))
+    if rc != 0:
+        raise BeomError("beom_harmonic_weights = %d" % rc)
+    return cw.value, sw.value
+
+
+def derive_harmonics(out: dict) -> dict:
+    """Adds the derived keys to a download's raw ref [F, nlay, n], sum [F, 1+2K, nlay, n], gram [1+2K, 1+2K] and count when
+    the fit is determined (count >= 1 + 2K and numpy.linalg.solve succeeds); otherwise leaves them absent.  Per element
+    G a = (S0, C_1, S_1, ...): mean = ref + a_0, amp_k = hypot(a_{2k-1}, a_{2k}), phase_k = atan2(a_{2k}, a_{2k-1}), all
+    [F, K, nlay, n] (mean [F, nlay, n]); eta_amp, eta_phase [K, nlay, n] are those of the interface elevations, by linearity
+    the bottom-up cumulative sum over the layers of the hlay coefficients (interface ilay lies on top of layer ilay)."""
+    sm, gram = out["sum"], out["gram"]
+    nw = gram.shape[0]
+    if out["count"] < nw:
+        return out
+    try:
+        a = np.linalg.solve(gram, sm.transpose(1, 0, 2, 3).reshape(nw, -1)).reshape((nw,) + sm.shape[:1] + sm.shape[2:])
+    except np.linalg.LinAlgError:
+        return out
+    if not np.all(np.isfinite(a)):
+        return out
+    out["mean"] = out["ref"] + a[0]
+    out["amp"] = np.stack([np.hypot(a[1 + 2 * k], a[2 + 2 * k]) for k in range(nw // 2)], axis=1)
+    out["phase"] = np.stack([np.arctan2(a[2 + 2 * k], a[1 + 2 * k]) for k in range(nw // 2)], axis=1)
+    e = np.cumsum(a[1:, 0, ::-1], axis=1)[:, ::-1]            # [2K, nlay, n]: the hlay coefficients summed from the bottom up
+    out["eta_amp"] = np.stack([np.hypot(e[2 * k], e[1 + 2 * k]) for k in range(nw // 2)])
+    out["eta_phase"] = np.stack([np.arctan2(e[1 + 2 * k], e[2 * k]) for k in range(nw // 2)])
+    return out
+
+
+class _Harmonics:
+    """Least-squares harmonic analysis of the layer fields (beom_set_harmonics, include/beom_hip.h): per field a reference
+    and 1 + 2K sums shifted by it, kept on the device and fed behind every step with tstp % stride == 0; the normal matrix
+    on the host.  Shared by Engine and MultiEngine."""
+
+    def _harm_fn(self, op):
+        return getattr(self.lib, "%s%s_harmonics" % ("beom_multi_" if self._mom_multi else "beom_", op))
+
+    def set_harmonics(self, omega=None, level: int = 1, stride: int = 1):
+        """omega: up to BEOM_MAX_HARMONICS frequencies in rad/day (None: the handle's tidal frequency w_ti; an empty
+        sequence frees); level 1: hlay, u, v; 2: and h_u, h_v.  Between steps only."""
+        if omega is None:
+            if float(self.prm.w_ti) == 0.0:
+                raise BeomError("set_harmonics: the handle has no tide (w_ti = 0): give omega")
+            omega = (float(self.prm.w_ti),)
+        om = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
+        self._check(self._harm_fn("set")(self.h, int(om.size), _dp(om), int(level), int(stride), self._err, ERRLEN))
+
+    def reset_harmonics(self):
+        """count = 0 and a zero normal matrix: the next sample is a first sample (no device memory moves)."""
+        if self._mom_multi:
+            self._check(self._harm_fn("reset")(self.h, self._err, ERRLEN))
+        else:
+            rc = self.lib.beom_reset_harmonics(self.h)
+            if rc != 0:
+                raise BeomError("beom_hip error %d: beom_reset_harmonics (harmonics set?)" % rc)
+
+    def download_harmonics(self) -> dict:
+        """count, tstp_first, tstp_last, omega [K]; the raw ref [F, nlay, ndeg+1], sum [F, 1+2K, nlay, ndeg+1] (S0, C_1, S_1,
+        ...) and gram [1+2K, 1+2K]; and, when the fit is determined, the keys of derive_harmonics."""
+        fn = self._harm_fn("download")
+        count, t0, t1 = C.c_longlong(0), C.c_int(0), C.c_int(0)
+        om = np.zeros(BEOM_MAX_HARMONICS)
+        gram = np.zeros((1 + 2 * BEOM_MAX_HARMONICS) ** 2)
+        self._check(fn(self.h, None, None, _dp(gram), _dp(om), C.byref(count), C.byref(t0), C.byref(t1), self._err, ERRLEN))
+        k, nf = self.info("harmonics"), 5 if self.info("harmonic_level") >= 2 else 3      # (bands: what band 0 keeps)
+        nw, shape = 1 + 2 * k, (self.p.nlay, self.p.ndeg + 1)
+        ref, sm = np.zeros((nf,) + shape), np.zeros((nf, nw) + shape)
+        self._check(fn(self.h, _dp(ref), _dp(sm), None, None, None, None, None, self._err, ERRLEN))
+        out = {"count": int(count.value), "tstp_first": int(t0.value), "tstp_last": int(t1.value), "omega": om[:k].copy(),
+               "ref": ref, "sum": sm, "gram": gram[:nw * nw].reshape(nw, nw).copy()}
+        return derive_harmonics(out)
+
+
 TRACER_MOMENT_QUANTITIES = ("q", "c", "fu", "fv")     # content, concentration, upstream face fluxes through the W and S faces
 
 
@@ -740,7 +834,7 @@ class _TracerSeries:
         return out
 
 
-class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries):
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
@@ -909,7 +1003,8 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         "tracer_vmixing" (1: set_tracer_vertical_mixing is in force), "tracer_vmix_launches" (its launches so far), "floats",
         "float_records" (records the track recorder holds), "float_launches" (float launches so far), "moments" (the level kept),
         "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
-        "tracer_moment_launches", "series" (the series' level), "series_records" (records its recorder holds), "tracer_series" (the tracer series' level),
+        "tracer_moment_launches", "harmonics" (the frequencies fitted), "harmonic_level", "harmonic_samples",
+        "harmonic_launches" (one per field and sample), "series" (the series' level), "series_records" (records its recorder holds), "tracer_series" (the tracer series' level),
         "tracer_series_records"."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
@@ -975,6 +1070,12 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         """Per-sweep entry: one sample of the tracers and the state as they stand, whatever the stride."""
         self._accum_plain("sample", "tracer_moments", "tracer moments")
 
+    def sample_harmonics(self, ctim: float):
+        """Per-sweep entry: one sample at time ctim (days) of the state as it stands, whatever the stride."""
+        rc = self.lib.beom_sample_harmonics(self.h, float(ctim))
+        if rc != 0:
+            raise BeomError("beom_hip error %d: beom_sample_harmonics (harmonics set?)" % rc)
+
     def sample_series(self):
         """Per-sweep entry: one record of the fields as they stand, under the last step's number, whatever the stride."""
         rc = self.lib.beom_sample_series(self.h)
@@ -992,7 +1093,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""

@@ -25,6 +25,7 @@
 #include "beom_tracer_vmix.h"
 #include "beom_floats.h"
 #include "beom_moments.h"
+#include "beom_harmonics.h"
 #include "beom_tracer_moments.h"
 #include "beom_tracer_series.h"
 #include "beom_dense_host.h"
@@ -108,6 +109,16 @@ static void accum_note_sample(Accum &A, int tstp) {      // the tail of a sample
     ++A.count;
     ++A.launches;
 }
+
+// The harmonic analysis (beom_set_harmonics; beom_harmonics.h): an accumulator whose sums are 1 + 2K per field.  acc carries
+// level (1 | 2; 0 = none), stride, count, the steps and ref[f]; the normal matrix of the fit is kept here, on the host.
+struct Harmonics {
+    Accum acc{nullptr};
+    int nfreq = 0;
+    double omega[BEOM_MAX_HARMONICS] = {};
+    double *sum[5][1 + 2 * BEOM_MAX_HARMONICS] = {};
+    double gram[(1 + 2 * BEOM_MAX_HARMONICS) * (1 + 2 * BEOM_MAX_HARMONICS)] = {};      // (1+2K)^2 in use, row-major
+};
 
 struct beom_engine {
     beom_params P;
@@ -219,6 +230,9 @@ struct beom_engine {
     // tracer moments (beom_set_tracer_moments; beom_tracer_moments.h): per quantity q, c, fu, fv the reference and the shifted
     // sum, at level 3 the shifted second moment of c, in arrays of the tracers' shape; level, stride and count of their own
     Accum tmom{&kTracerMoments};
+    // harmonics (beom_set_harmonics; beom_harmonics.h): per field the reference and 1 + 2K shifted sums in arrays of the
+    // state's shape, the normal matrix on the host; "moments_by_caller" governs their samples too
+    Harmonics harm;
     // series (beom_set_series; beom_series.h): a recorder [nrec][ser_rows][count] of the row sums of local rows ser_jlo ..
     // ser_jlo+ser_rows-1, one record behind every step with tstp % stride == 0, with the step of every held record
     int ser_level = 0, ser_stride = 1, ser_nrec = 0, ser_jlo = 1, ser_rows = 0;
@@ -567,7 +581,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->ser_allocs, &E->tser_allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser_allocs, &E->tser_allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -899,6 +913,30 @@ static void launch_moments(beom_engine *E, int tstp) {
     });
     accum_note_sample(E->mom, tstp);
 }
+// one sample of the harmonics (beom_harmonics.h) of the fields as they stand at time ctim, recorded under step tstp: the
+// weights and the normal matrix on the host, one launch per field
+static void launch_harmonics(beom_engine *E, int tstp, double ctim) {
+    const DevView &d = E->d;
+    Harmonics &H = E->harm;
+    const int K = H.nfreq, nw = 1 + 2 * K, nf = H.acc.level >= 2 ? 5 : 3;
+    double w[1 + 2 * BEOM_MAX_HARMONICS] = {1.0};
+    for (int k = 0; k < K; ++k) (void)beom_harmonic_weights(H.omega[k], ctim, &w[1 + 2 * k], &w[2 + 2 * k]);
+    for (int i = 0; i < nw; ++i)
+        for (int j = 0; j < nw; ++j) H.gram[i * nw + j] = H.gram[i * nw + j] + w[i] * w[j];
+    const double *const x[5] = {d.hlay, d.u, d.v, d.h_u, d.h_v};
+    const long long n = (long long)d.nlay * d.n1, pairs = (n - 1) / 2;
+    const dim3 g((unsigned)std::max<long long>(1, std::min<long long>((pairs + BEOM_BLOCK - 1) / BEOM_BLOCK, 2048))), b(BEOM_BLOCK);
+    for (int f = 0; f < nf; ++f) {
+        double *const *s = H.sum[f];
+        const HarmView v{n, x[f], H.acc.ref[f], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8],
+                         w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8]};
+        pick_int<1, BEOM_MAX_HARMONICS>(K, [&](auto kk) {
+            pick([&](auto first) { hipLaunchKernelGGL((k_harmonics<kk, first>), g, b, 0, E->stream, v); }, H.acc.count == 0);
+        });
+    }
+    accum_note_sample(H.acc, tstp);
+    H.acc.launches += nf - 1;          // (one launch per field)
+}
 // one sample of the tracer moments (beom_tracer_moments.h) of q, hlay, h_u, h_v as they stand, recorded under step tstp
 static void launch_tracer_moments(beom_engine *E, int tstp) {
     double *const *r = E->tmom.ref, *const *s = E->tmom.sum;
@@ -1190,6 +1228,7 @@ static void one_step(beom_engine *E, const StepPlan &p, int flt = -1) {
     E->last_tstp = tstp; E->split.tstp = 0;      // (a whole step: no part 1 is pending)
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
+    if (!E->mom_by_caller && accum_due(E->harm.acc, tstp)) launch_harmonics(E, tstp, p.ctim);
     if (!E->ser_by_caller && series_due(E, tstp)) launch_series(E, tstp);
     if (!E->tser_by_caller && tracer_series_due(E, tstp)) launch_tracer_series(E, tstp);
 }
@@ -2155,6 +2194,104 @@ int beom_download_tracer_moments(beom_handle E, double *ref, double *sum, double
     return accum_download(E, &beom_engine::tmom, ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
 }
 
+// ---- harmonics (beom_harmonics.h): the accumulator's host side, with the frequencies and the normal matrix ----
+int beom_harmonic_weights(double omega, double ctim, double *cw, double *sw) {
+    if (!cw || !sw) return -3;
+    const double th = omega * ctim;
+    *cw = cos(th);
+    *sw = sin(th);
+    return 0;
+}
+
+static void harmonics_free(Harmonics &H) {
+    accum_free(H.acc);
+    const long long launches = H.acc.launches;      // (all calls so far: kept, as accum_free keeps it)
+    H = Harmonics{};
+    H.acc.launches = launches;
+}
+
+int beom_set_harmonics(beom_handle E, int nfreq, const double *omega, int level, int stride, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    if (nfreq != 0) {
+        if (nfreq < 1 || nfreq > BEOM_MAX_HARMONICS || level < 1 || level > 2 || stride < 1 || !omega) {
+            set_err(errm, errm_len, "beom_set_harmonics: nfreq %d, level %d, stride %d (nfreq 0..%d with omega given, level 1..2, stride >= 1)",
+                    nfreq, level, stride, BEOM_MAX_HARMONICS);
+            return -3;
+        }
+        for (int k = 0; k < nfreq; ++k) {
+            if (!std::isfinite(omega[k]) || !(omega[k] > 0.0)) {
+                set_err(errm, errm_len, "beom_set_harmonics: omega[%d] = %g rad/day (finite and > 0)", k, omega[k]);
+                return -3;
+            }
+            for (int j = 0; j < k; ++j)
+                if (omega[j] == omega[k]) { set_err(errm, errm_len, "beom_set_harmonics: omega[%d] == omega[%d] = %g (the normal matrix would be singular)", j, k, omega[k]); return -3; }
+        }
+    }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    Harmonics &H = E->harm;
+    harmonics_free(H);
+    if (nfreq == 0) return 0;
+    int rc = 0;
+    const size_t n = state_cells(E);
+    const int nf = level >= 2 ? 5 : 3;
+    for (int f = 0; f < nf && !rc; ++f) {
+        rc = alloc_aligned(E, H.acc.allocs, &H.acc.ref[f], n, errm, errm_len);
+        for (int m = 0; m < 1 + 2 * nfreq && !rc; ++m) rc = alloc_aligned(E, H.acc.allocs, &H.sum[f][m], n, errm, errm_len);
+    }
+    if (rc) { harmonics_free(H); return rc; }
+    H.acc.level = level; H.acc.stride = stride; H.nfreq = nfreq;
+    std::copy(omega, omega + nfreq, H.omega);
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+int beom_reset_harmonics(beom_handle E) {
+    if (!E) return -1;
+    const int rc = accum_reset(E->harm.acc);
+    if (!rc) std::fill(std::begin(E->harm.gram), std::end(E->harm.gram), 0.0);
+    return rc;
+}
+
+int beom_sample_harmonics(beom_handle E, double ctim) {
+    if (!E) return -1;
+    if (E->harm.acc.level < 1) return -3;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    launch_harmonics(E, E->last_tstp, ctim);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+// ref [fields][nlay][0:ndeg], sum [fields][1+2K][nlay][0:ndeg], gram [(1+2K)^2], omega [K] of the caller (null: not wanted)
+int beom_download_harmonics(beom_handle E, double *ref, double *sum, double *gram, double *omega, long long *count,
+                            int *tstp_first, int *tstp_last, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    const Harmonics &H = E->harm;
+    const Accum &A = H.acc;
+    if (A.level < 1) { set_err(errm, errm_len, "beom_download_harmonics: the handle keeps no harmonics (beom_set_harmonics)"); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t rows = (size_t)E->d.nlay, slab = ((size_t)E->d.ndeg + 1) * rows;
+    const int nf = A.level >= 2 ? 5 : 3, nw = 1 + 2 * H.nfreq;
+    if (count) *count = A.count;
+    if (tstp_first) *tstp_first = A.first;
+    if (tstp_last) *tstp_last = A.last;
+    if (gram) std::copy(H.gram, H.gram + nw * nw, gram);
+    if (omega) std::copy(H.omega, H.omega + H.nfreq, omega);
+    if (A.count == 0) {                // nothing sampled yet: the arrays hold whatever an earlier analysis left
+        if (ref) std::fill(ref, ref + nf * slab, 0.0);
+        if (sum) std::fill(sum, sum + (size_t)nf * nw * slab, 0.0);
+        return 0;
+    }
+    int rc;
+    for (int f = 0; f < nf; ++f) {
+        if (ref && (rc = copy_out(E, ref + f * slab, A.ref[f], rows, errm, errm_len))) return rc;
+        for (int m = 0; m < nw && sum; ++m)
+            if ((rc = copy_out(E, sum + ((size_t)f * nw + m) * slab, H.sum[f][m], rows, errm, errm_len))) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)
 // of nudged open-boundary segments, Fortran storage.  Activates no_gradient_obc after the
 // momentum sweeps of every step when flag_nudging and mcbc < 0.5 (:2201-2204, 2285-2288).
@@ -2237,6 +2374,10 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_series_records")) return (int)E->tser_tstp.size();
     if (!strcmp(what, "series")) return E->ser_level;
     if (!strcmp(what, "series_records")) return (int)E->ser_tstp.size();
+    if (!strcmp(what, "harmonics")) return E->harm.nfreq;
+    if (!strcmp(what, "harmonic_level")) return E->harm.acc.level;
+    if (!strcmp(what, "harmonic_samples")) return (int)std::min<long long>(E->harm.acc.count, 2000000000ll);
+    if (!strcmp(what, "harmonic_launches")) return (int)std::min<long long>(E->harm.acc.launches, 2000000000ll);     // all calls so far
     if (!strcmp(what, "moments")) return E->mom.level;
     if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom.count, 2000000000ll);
     if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom.launches, 2000000000ll);     // all calls so far

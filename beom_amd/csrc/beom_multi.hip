@@ -281,6 +281,10 @@ struct beom_multi {
     // sample is still owed (0 = none) is taken where the main streams next join the exchange
     struct Moments { int level = 0, stride = 1, due = 0; };
     Moments mom, tmom;             // (tmom: the tracer moments likewise, beom_multi_set_tracer_moments)
+    // harmonics kept by every band (beom_multi_set_harmonics), sampled where the moments are: the step whose sample is owed
+    // and that step's time ctim = tres + dtd8*(double)due
+    struct Harmonics { int nfreq = 0, level = 0, stride = 1, due = 0; double due_ctim = 0.0; };
+    Harmonics harm;
     // series kept by every band over its owned rows (beom_multi_set_series): the record a step left owing is taken where the
     // moments' sample is; the steps of the records held (every band holds as many)
     struct Series { int level = 0, stride = 1, nrec = 0, due = 0; std::vector<int> tstp; };
@@ -1248,6 +1252,65 @@ int beom_multi_download_tracer_moments(beom_multi_handle M, double *ref, double 
     return multi_download_accum(M, kTracerMoments, ref, sum, sq, count, tstp_first, tstp_last, errm, errm_len);
 }
 
+// ---- harmonics (beom_set_harmonics) on the bands: as the moments, every band accumulates over all its rows and keeps the
+//      same normal matrix; a ring's companion frame samples behind its own steps ----
+int beom_multi_set_harmonics(beom_multi_handle M, int nfreq, const double *omega, int level, int stride, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_harmonics: an earlier step failed half way; destroy the handle"); return -30; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_set_harmonics: a handle that holds one band's window does not keep harmonics (its global arrays are nowhere assembled); use a handle created from the global arrays"); return -6; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    // band 0 checks the arguments before it touches anything; the others are given what it accepted.  A band that cannot
+    // allocate leaves the whole handle without harmonics
+    int rc = 0;
+    for (int k = 0; k < M->n && !rc; ++k) {
+        rc = beom_set_harmonics(M->eng[k], nfreq, omega, level, stride, errm, errm_len);
+        if (rc == -3 && k == 0) return rc;          // (refused arguments: nothing touched)
+        if (!rc && beom_set_option(M->eng[k], "moments_by_caller", multi_whole(M) ? 0 : 1)) { m_err(errm, errm_len, "beom_multi_set_harmonics: option refused"); rc = -3; }
+    }
+    if (!rc && M->mini) rc = beom_set_harmonics(M->mini, nfreq, omega, level, stride, errm, errm_len);
+    if (rc) {
+        for (int k = 0; k < M->n; ++k) (void)beom_set_harmonics(M->eng[k], 0, nullptr, 0, 0, nullptr, 0);
+        if (M->mini) (void)beom_set_harmonics(M->mini, 0, nullptr, 0, 0, nullptr, 0);
+        M->harm = {};
+        return rc;
+    }
+    M->harm = {};
+    if (nfreq > 0) { M->harm.nfreq = nfreq; M->harm.level = level; M->harm.stride = stride; }
+    return 0;
+}
+
+int beom_multi_reset_harmonics(beom_multi_handle M, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_reset_harmonics: this handle holds a window and keeps no harmonics"); return -6; }
+    if (M->harm.level < 1) { m_err(errm, errm_len, "beom_multi_reset_harmonics: the handle keeps no harmonics (beom_multi_set_harmonics)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    for (int k = 0; k < M->n; ++k) M_RC(beom_reset_harmonics(M->eng[k]));
+    if (M->mini) M_RC(beom_reset_harmonics(M->mini));
+    M->harm.due = 0;
+    return 0;
+}
+
+int beom_multi_download_harmonics(beom_multi_handle M, double *ref, double *sum, double *gram, double *omega, long long *count,
+                                  int *tstp_first, int *tstp_last, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_harmonics: this handle holds a window and keeps no harmonics"); return -6; }
+    if (M->harm.level < 1) { m_err(errm, errm_len, "beom_multi_download_harmonics: the handle keeps no harmonics (beom_multi_set_harmonics)"); return -3; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (multi_whole(M)) return beom_download_harmonics(M->eng[0], ref, sum, gram, omega, count, tstp_first, tstp_last, errm, errm_len);
+    const size_t nf = M->harm.level >= 2 ? 5 : 3, nw = 1 + 2 * (size_t)M->harm.nfreq;
+    double *dst[2] = {ref, sum};
+    const size_t outer[2] = {nf * M->P.nlay, nf * nw * M->P.nlay};
+    for (const Part &p : parts(M)) {
+        std::vector<double> a[2];
+        for (int f = 0; f < 2; ++f) if (dst[f]) a[f].assign(outer[f] * p.n1(), 0.0);
+        const bool lead = p.k == 0;          // gram, omega, count and the steps are band 0's
+        M_RC(beom_download_harmonics(p.eng, ptr(a[0]), ptr(a[1]), lead ? gram : nullptr, lead ? omega : nullptr, lead ? count : nullptr,
+                                     lead ? tstp_first : nullptr, lead ? tstp_last : nullptr, errm, errm_len));
+        for (int f = 0; f < 2; ++f) copy_rows(dst[f], ptr(a[f]), outer[f], 1, p.out);
+    }
+    return 0;
+}
+
 // ---- output records of all bands (SURVEY §8f N2 for the multi-device handle): as beom_download_outputs /
 //      beom_download_diag with GLOBAL (ndeg, nlay) real*4 records; every band forms its rows on its device.
 int beom_multi_download_outputs(beom_multi_handle M, const float *h0r4, float *eta, float *u4, float *v4,
@@ -1556,6 +1619,11 @@ static int multi_sample_due(beom_multi *M, char *errm, int errm_len) {
             if (K->sample(M->eng[k])) { m_err(errm, errm_len, K->sample_failed, M->band[k].index, due); return -3; }
         due = 0;
     }
+    if (M->harm.due) {
+        for (int k = 0; k < M->n; ++k)
+            if (beom_sample_harmonics(M->eng[k], M->harm.due_ctim)) { m_err(errm, errm_len, "beom_sample_harmonics failed on band %d (step %d)", M->band[k].index, M->harm.due); return -3; }
+        M->harm.due = 0;
+    }
     if (M->ser.due) {
         for (int k = 0; k < M->n; ++k)
             if (beom_sample_series(M->eng[k])) { m_err(errm, errm_len, "beom_sample_series failed on band %d (step %d)", M->band[k].index, M->ser.due); return -3; }
@@ -1713,6 +1781,7 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
     }
     for (beom_multi::Moments *m : {&M->mom, &M->tmom})
         if (m->level > 0 && t % m->stride == 0) m->due = t;
+    if (M->harm.level > 0 && t % M->harm.stride == 0) { M->harm.due = t; M->harm.due_ctim = tres + dtd8 * (double)t; }
     if (M->ser.level > 0 && t % M->ser.stride == 0) M->ser.due = t;
     if (M->tser.level > 0 && t % M->tser.stride == 0) M->tser.due = t;
     if (M->nflt > 0) M->flt_mode = 3;
@@ -1760,7 +1829,7 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
             return rc;
         }
     }
-    if (M->mom.due || M->tmom.due || M->ser.due || M->tser.due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
+    if (M->mom.due || M->tmom.due || M->harm.due || M->ser.due || M->tser.due || M->flt_mode) {       // the last step's sample and stage 2: behind the same wait the next step would begin with
         M_RC(multi_join_exchange(M, errm, errm_len));
         M_RC(multi_sample_due(M, errm, errm_len));
         if (M->flt_mode) {

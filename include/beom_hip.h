@@ -477,6 +477,50 @@ int beom_sample_moments(beom_handle h);
 int beom_download_moments(beom_handle h, double *ref, double *sum, double *sq, long long *count, int *tstp_first, int *tstp_last,
                           char *errm, int errm_len);
 
+/* ---- Harmonics: least-squares harmonic analysis of the layer fields, accumulated on the device (no reference routine;
+ * DESIGN.md f-N14).  The fields are those of the moments, f = 0..4: hlay, u, v (level 1) and h_u, h_v (level 2), fitted at
+ * K = nfreq <= BEOM_MAX_HARMONICS frequencies omega_k given by the caller in rad/day, the unit of w_ti.  A SAMPLE is taken
+ * behind step tstp of beom_step when tstp % stride == 0, where the moments' sample sits (after the open-boundary pass, the
+ * lid's pressure correction and its transport rebuild).  Its time is the step's own ctim = tres + dtd8*(double)tstp, in days.
+ * K steps of one call take their samples without returning to the host; the bits do not depend on how the steps are
+ * divided into calls.
+ * The WEIGHTS of a sample are formed on the host in FP64 with libm: th = omega_k*ctim; cw_k = cos(th); sw_k = sin(th).
+ * beom_harmonic_weights returns exactly them (host only, no device, as beom_integral_combine); the device receives them as
+ * scalars and only subtracts, multiplies and adds.  Per field and per element of the packed (0:ndeg, nlay) storage, the
+ * sentinel included (its sums are +0.0), all FP64, no contraction, in this order, k ascending:
+ *   first sample after beom_set_harmonics / beom_reset_harmonics:   ref = x;  S0 = +0.0;  C_k = S_k = +0.0;  count = 1
+ *   every later sample:   d = x - ref;  S0 = S0 + d;  C_k = C_k + d*cw_k;  S_k = S_k + d*sw_k  (the product rounded, then
+ *   added);  count += 1
+ * The NORMAL MATRIX is kept on the host, for every sample, the first included: with w = (1, cw_1, sw_1, ..., cw_K, sw_K),
+ * G[i][j] = G[i][j] + w_i*w_j, (1+2K)^2 doubles, row-major; set and reset zero it.
+ * Derived by the caller: solve G a = b per element with b = (S0, C_1, S_1, ...); mean = ref + a_0,
+ * amp_k = hypot(a_{2k-1}, a_{2k}), phase_k = atan2(a_{2k}, a_{2k-1}), so x ~ mean + sum_k amp_k*cos(omega_k*t - phase_k).
+ * (The first sample has d = 0: its row of the design matrix is in G and its right-hand side is zero, so a is the exact
+ * least-squares fit of d over all `count` samples, for any record length and sampling.)  Why shifted by the first sample:
+ * the mean is exact for a constant field, and a deep layer keeps its digits: a 0.01 m + 0.005 m signal on 4000 m, 3000
+ * samples, is fitted to 2.2e-12 relative in amplitude shifted against 1.7e-11 unshifted (tests/test_harmonics_cpu.py).
+ * Layout: sum[ipnt + (ndeg+1)*((ilay-1) + nlay*(m + (1+2K)*f))] with m = 0 for S0, m = 2k-1 for C_k, m = 2k for S_k
+ * (k = 1..K); ref as the moments' ref.  fields*(2 + 2K) more arrays of the state's size; 4 + 4K words of traffic per
+ * element, field and later sample, one launch per field.
+ * beom_set_harmonics: nfreq = 0 frees (the other arguments are not looked at); else level 1 or 2, stride >= 1, nfreq
+ * 1..BEOM_MAX_HARMONICS; -3 with a message and nothing touched for anything else, for an omega that is not finite or is
+ * <= 0, and for two omega that are equal (nearly equal ones are the caller's affair: gram shows the conditioning).  It
+ * allocates, count = 0; between steps only; a failed allocation leaves the handle without harmonics.  Every single handle
+ * kind keeps them (embedded, table path, variant = 1, rigid lid, svis > 0, open boundaries).  beom_reset_harmonics sets
+ * count = 0, zeroes G and moves no device memory.  beom_upload_state does NOT reset: a restart continues an analysis.
+ * beom_sample_harmonics is the per-sweep entry: one sample at time ctim of the state as it stands, whatever the stride,
+ * under the step number of the handle's last step.  beom_download_harmonics: any pointer may be NULL; gram has (1+2K)^2
+ * and omega K entries; -3 on a handle without harmonics; with count = 0 it returns zeros.  beom_info: "harmonics" (nfreq),
+ * "harmonic_level", "harmonic_samples" (capped at 2e9), "harmonic_launches" (so far: fields per sample).  The option
+ * "moments_by_caller" governs these samples too.  A handle without harmonics launches exactly what it launched before. */
+#define BEOM_MAX_HARMONICS 4
+int beom_harmonic_weights(double omega, double ctim, double *cw, double *sw);
+int beom_set_harmonics(beom_handle h, int nfreq, const double *omega, int level, int stride, char *errm, int errm_len);
+int beom_reset_harmonics(beom_handle h);
+int beom_sample_harmonics(beom_handle h, double ctim);
+int beom_download_harmonics(beom_handle h, double *ref, double *sum, double *gram, double *omega, long long *count,
+                            int *tstp_first, int *tstp_last, char *errm, int errm_len);
+
 /* ---- Tracer moments: time means of a tracer's content, concentration and face fluxes and the variance of its concentration,
  * accumulated on the device (no reference routine; DESIGN.md f-N9).  With t the tracer, l the layer, p a real cell and
  * W, S = neig(5|7, p), c(x) is trc_conc of beom_tracers.h, c(x) = hlay(x,l) > 0 ? q(x,l,t)/hlay(x,l) : +0.0, and four
@@ -784,6 +828,18 @@ int beom_multi_set_moments(beom_multi_handle m, int level, int stride, char *err
 int beom_multi_reset_moments(beom_multi_handle m, char *errm, int errm_len);
 int beom_multi_download_moments(beom_multi_handle m, double *ref, double *sum, double *sq, long long *count, int *tstp_first,
                                 int *tstp_last, char *errm, int errm_len);
+
+/* Harmonics on a frame cut into bands (see beom_set_harmonics): GLOBAL ref and sum assembled from every band's OWNED rows
+ * through the moments' path, chains and rings; the bits are a single handle's.  Every band accumulates over its whole window
+ * and is sampled with beom_sample_harmonics(h, tres + dtd8*(double)t) exactly where the bands' moments are sampled (in front
+ * of step t + 1, and once more behind the last step of a beom_multi_step call), so cut steps stay cut and beom_multi_stats
+ * is what it is without harmonics.  gram, omega, count and the step numbers come from band 0 (every band holds the same).
+ * A ring's row mm+1 comes from the companion frame, which samples behind its own steps.  Refused with -6: handles that
+ * hold one band's window (beom_multi_create_local*). */
+int beom_multi_set_harmonics(beom_multi_handle m, int nfreq, const double *omega, int level, int stride, char *errm, int errm_len);
+int beom_multi_reset_harmonics(beom_multi_handle m, char *errm, int errm_len);
+int beom_multi_download_harmonics(beom_multi_handle m, double *ref, double *sum, double *gram, double *omega, long long *count,
+                                  int *tstp_first, int *tstp_last, char *errm, int errm_len);
 
 /* Tracer moments on a frame cut into bands (see beom_set_tracer_moments): GLOBAL arrays assembled from every band's OWNED
  * rows; the bits are a single handle's.  Every band samples over its whole window where the bands' field moments are sampled:

@@ -97,7 +97,7 @@ def source_hash() -> str:
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
     for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_harmonics.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_dense_host.h",
-               "beom_bands_host.h", "beom_plan.h", os.path.join("..", "..", "include", "beom_hip.h")):
+               "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -409,20 +409,28 @@ def scale_integrals(raw: np.ndarray, prm: BeomParams) -> dict:
 TRACER_SCHEMES = {"upstream": 1, "limited": 2}
 
 
-class _Tracers:
+class _Handle:
+    """What the mixins below ask of the handle class that joins them: `_prefix`, the prefix of its C symbols ("beom_" on Engine,
+    "beom_multi_" on MultiEngine and so on BandEngine); the calls differ only by it."""
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    @property
+    def _multi(self) -> bool:
+        return self._prefix == "beom_multi_"
+
+
+class _Tracers(_Handle):
     """Passive tracers of a handle (beom_set_tracers, include/beom_hip.h): shared by Engine and MultiEngine, whose C calls
     differ only by name.  Arrays: q, ctrg [ntrc, nlay, ndeg+1] (the layer CONTENT thickness x concentration, and the
     relaxation concentration), rq [ntrc, nlay, ndeg+1, 2] (the tendency history, as rs_h per tracer)."""
 
-    _trc_prefix = "beom_"
     ntrc = 0
-
-    def _trc(self, name):
-        return getattr(self.lib, self._trc_prefix + name)
 
     def set_tracers(self, n: int):
         """Allocates n tracers (q, rq, ctrg = 0); n = 0 frees them.  Between steps only."""
-        self._check(self._trc("set_tracers")(self.h, int(n), self._err, ERRLEN))
+        self._check(self._fn("set_tracers")(self.h, int(n), self._err, ERRLEN))
         self.ntrc = int(n)
 
     def set_tracer_scheme(self, scheme):
@@ -431,7 +439,7 @@ class _Tracers:
         scheme = TRACER_SCHEMES.get(scheme, scheme)
         if isinstance(scheme, str):
             raise BeomError("tracer scheme %r (1 | 'upstream', 2 | 'limited')" % (scheme,))
-        self._check(self._trc("set_tracer_scheme")(self.h, int(scheme), self._err, ERRLEN))
+        self._check(self._fn("set_tracer_scheme")(self.h, int(scheme), self._err, ERRLEN))
 
     def set_tracer_mixing(self, kappa=None, decay=None, source=None):
         """Lateral diffusion kappa (m2/s), decay (1/s) and source (concentration per second) of the tracers, applied in a
@@ -449,7 +457,7 @@ class _Tracers:
                     raise BeomError("%s of shape %s: a scalar, %s or %s expected" % (name, a.shape, want[:1], want))
                 a = np.ascontiguousarray(np.broadcast_to(a[:, None] if a.ndim == 1 else a, want))
             co.append(a)
-        self._check(self._trc("set_tracer_mixing")(self.h, _dp(co[0]), _dp(co[1]), _dp(co[2]), self._err, ERRLEN))
+        self._check(self._fn("set_tracer_mixing")(self.h, _dp(co[0]), _dp(co[1]), _dp(co[2]), self._err, ERRLEN))
 
     def set_tracer_vertical_mixing(self, kappa_v=None):
         """Vertical (diapycnal) diffusion kappa_v (m2/s) of the tracers through the nlay - 1 interfaces of every water column,
@@ -467,7 +475,7 @@ class _Tracers:
             a = np.ascontiguousarray(np.broadcast_to(a, want))
             if a.size == 0:         # (no tracer or one layer: the library refuses in its own words, and reads no value)
                 a = np.zeros(1)
-        self._check(self._trc("set_tracer_vmixing")(self.h, _dp(a), self._err, ERRLEN))
+        self._check(self._fn("set_tracer_vmixing")(self.h, _dp(a), self._err, ERRLEN))
 
     def _trc_array(self, a, tail=()):
         if a is None:
@@ -480,12 +488,12 @@ class _Tracers:
 
     def upload_tracers(self, q=None, rq=None, ctrg=None):
         q, rq, ctrg = self._trc_array(q), self._trc_array(rq, (2,)), self._trc_array(ctrg)
-        self._check(self._trc("upload_tracers")(self.h, _dp(q), _dp(rq), _dp(ctrg), self._err, ERRLEN))
+        self._check(self._fn("upload_tracers")(self.h, _dp(q), _dp(rq), _dp(ctrg), self._err, ERRLEN))
 
     def download_tracers(self) -> dict:
         n = (self.ntrc, self.p.nlay, self.p.ndeg + 1)
         out = {"q": np.zeros(n), "rq": np.zeros(n + (2,))}
-        self._check(self._trc("download_tracers")(self.h, _dp(out["q"]), _dp(out["rq"]), self._err, ERRLEN))
+        self._check(self._fn("download_tracers")(self.h, _dp(out["q"]), _dp(out["rq"]), self._err, ERRLEN))
         return out
 
     def set_concentration(self, c):
@@ -496,14 +504,13 @@ class _Tracers:
         return q
 
 
-class _Floats:
+class _Floats(_Handle):
     """Lagrangian floats of a handle (beom_set_floats, include/beom_hip.h): positions x, y in grid units (cell (i, j) spans
     [i-1, i] x [j-1, j]), a fixed 1-based layer per float, moved by every step with Heun's method on the layer velocities.
     Shared by Engine and MultiEngine (floats on bands: replicated slots and hand-over records, no track recorder)."""
 
     nfloats = 0
     float_records = 0
-    _flt_multi = False
 
     def set_floats(self, x, y, layer, records: int = 0, stride: int = 1, capacity: int = 0):
         """Replaces the handle's floats by these (arrays of one length; an empty x frees them) and zeroes their `rejected`
@@ -515,7 +522,7 @@ class _Floats:
         layer = np.ascontiguousarray(np.broadcast_to(np.asarray(layer, dtype=np.int32), x.shape), dtype=np.int32)
         if y.shape != x.shape:
             raise BeomError("set_floats: x of %d positions, y of %d" % (x.size, y.size))
-        if self._flt_multi:
+        if self._multi:
             if records > 0:
                 raise BeomError("beom_hip error -6: set_floats: bands keep no track recorder (records = %d): a float's records would be "
                                 "spread over the bands it has visited; record on a single handle" % records)
@@ -538,8 +545,7 @@ class _Floats:
     def download_floats(self) -> dict:
         n = self.nfloats
         out = {"x": np.zeros(n), "y": np.zeros(n), "layer": np.zeros(n, dtype=np.int32), "rejected": np.zeros(n, dtype=np.int32)}
-        fn = self.lib.beom_multi_download_floats if self._flt_multi else self.lib.beom_download_floats
-        self._check(fn(self.h, _dp(out["x"]), _dp(out["y"]), _ip(out["layer"]), _ip(out["rejected"]), self._err, ERRLEN))
+        self._check(self._fn("download_floats")(self.h, _dp(out["x"]), _dp(out["y"]), _ip(out["layer"]), _ip(out["rejected"]), self._err, ERRLEN))
         return out
 
     def download_float_track(self) -> dict:
@@ -553,19 +559,17 @@ class _Floats:
 
     def update_floats(self, stage: int):
         """Per-sweep entry: stage 1 or stage 2 of the scheme on the velocities as they stand (no record)."""
-        rc = (self.lib.beom_multi_update_floats if self._flt_multi else self.lib.beom_update_floats)(self.h, int(stage))
+        rc = self._fn("update_floats")(self.h, int(stage))
         if rc != 0:
             raise BeomError("beom_update_floats(stage %d) = %d (floats set and uploaded? stage 1 or 2?)" % (stage, rc))
 
 
-class _Accum:
+class _Accum(_Handle):
     """What _Moments and _TracerMoments share: set, reset and download of a device-side time accumulator through the exports
     beom_[multi_]{set,reset,download}_<stem>, the level asked of the handle (info(<stem>))."""
 
-    _mom_multi = False
-
     def _accum_fn(self, op, stem):
-        return getattr(self.lib, "%s%s_%s" % ("beom_multi_" if self._mom_multi else "beom_", op, stem))
+        return self._fn("%s_%s" % (op, stem))
 
     def _accum_set(self, stem, level, stride):
         self._check(self._accum_fn("set", stem)(self.h, int(level), int(stride), self._err, ERRLEN))
@@ -577,7 +581,7 @@ class _Accum:
             raise BeomError("beom_hip error %d: beom_%s_%s (%s set?)" % (rc, op, stem, what))
 
     def _accum_reset(self, stem, what):
-        if self._mom_multi:
+        if self._multi:
             self._check(self._accum_fn("reset", stem)(self.h, self._err, ERRLEN))
         else:
             self._accum_plain("reset", stem, what)
@@ -664,13 +668,13 @@ def derive_harmonics(out: dict) -> dict:
     return out
 
 
-class _Harmonics:
+class _Harmonics(_Handle):
     """Least-squares harmonic analysis of the layer fields (beom_set_harmonics, include/beom_hip.h): per field a reference
     and 1 + 2K sums shifted by it, kept on the device and fed behind every step with tstp % stride == 0; the normal matrix
     on the host.  Shared by Engine and MultiEngine."""
 
     def _harm_fn(self, op):
-        return getattr(self.lib, "%s%s_harmonics" % ("beom_multi_" if self._mom_multi else "beom_", op))
+        return self._fn(op + "_harmonics")
 
     def set_harmonics(self, omega=None, level: int = 1, stride: int = 1):
         """omega: up to BEOM_MAX_HARMONICS frequencies in rad/day (None: the handle's tidal frequency w_ti; an empty
@@ -684,7 +688,7 @@ class _Harmonics:
 
     def reset_harmonics(self):
         """count = 0 and a zero normal matrix: the next sample is a first sample (no device memory moves)."""
-        if self._mom_multi:
+        if self._multi:
             self._check(self._harm_fn("reset")(self.h, self._err, ERRLEN))
         else:
             rc = self.lib.beom_reset_harmonics(self.h)
@@ -737,21 +741,46 @@ class _TracerMoments(_Accum):
                                     "var_c", lambda q, m: q - m[1] * m[1])
 
 
-class _Series:
+class _Recorder(_Handle):
+    """What _Series and _TracerSeries share: a device-side recorder [records][M][cnt] set and downloaded through the exports
+    beom_[multi_]{set,download}_<stem>, and sampled by hand on a single handle (beom_sample_<stem>)."""
+
+    def _recorder_set(self, stem, level, stride, records):
+        """-> the level and the record count to keep (0 records once freed)."""
+        self._check(self._fn("set_" + stem)(self.h, int(level), int(stride), int(records), self._err, ERRLEN))
+        return int(level), (int(records) if level else 0)
+
+    def _recorder_download(self, stem, what, level, records, cnt_of):
+        """The records held, oldest first: (n, tstp[n], rows[n, M, cnt_of(level)]); empties the recorder."""
+        fn = self._fn("download_" + stem)
+        if level < 1:                                                    # (the library says why)
+            self._check(fn(self.h, None, None, None, self._err, ERRLEN))
+            raise BeomError("download_%s: the handle keeps no %s (set_%s)" % (stem, what, stem))
+        rows = np.zeros((max(records, 1), self.p.mm + 1, cnt_of(level)))
+        tstp = (C.c_int * max(records, 1))()
+        count = C.c_int(0)
+        self._check(fn(self.h, _dp(rows), tstp, C.byref(count), self._err, ERRLEN))
+        n = count.value
+        return n, np.array(list(tstp)[:n], dtype=np.int64), rows[:n].copy()
+
+    def _recorder_sample(self, stem, what):
+        rc = getattr(self.lib, "beom_sample_" + stem)(self.h)
+        if rc != 0:
+            raise BeomError("beom_hip error %d: beom_sample_%s (%s set? recorder full?)" % (rc, stem, what))
+
+
+class _Series(_Recorder):
     """A record of the row sums per sampled step, kept on the device (beom_set_series, include/beom_hip.h): the quantities of
     integral_rows for every row of the frame and, at level 2, the row sums of the layer transports h_u, h_v, written behind
     every step with tstp % stride == 0 without a host copy.  Shared by Engine and MultiEngine."""
 
     series_level = 0
     series_records = 0
-    _ser_multi = False
 
     def set_series(self, level: int, stride: int = 1, records: int = 64):
         """level 1: vol, ke, ens, circ per layer and eta2 per row; 2: and tu, tv per layer; 0 frees.  `records`: what the
         recorder holds between two download_series (a step call that would overflow it is refused).  Between steps only."""
-        fn = self.lib.beom_multi_set_series if self._ser_multi else self.lib.beom_set_series
-        self._check(fn(self.h, int(level), int(stride), int(records), self._err, ERRLEN))
-        self.series_level, self.series_records = int(level), (int(records) if level else 0)
+        self.series_level, self.series_records = self._recorder_set("series", level, stride, records)
 
     def download_series(self) -> dict:
         """The records held, oldest first, and empties the recorder.  count, tstp[n]; rows[n, M, cnt] (M = mm+1 rows in global
@@ -760,19 +789,10 @@ class _Series:
         h_v (thickness * velocity through a cell's W resp. S face, m^2/s), and psi[n, M, nlay] = dl * cumsum(tv, layers):
         the volume transport (m^3/s) above the base of layer l through the south faces of row j."""
         nl, M = self.p.nlay, self.p.mm + 1
-        fn = self.lib.beom_multi_download_series if self._ser_multi else self.lib.beom_download_series
-        if self.series_level < 1:                                        # (the library says why)
-            self._check(fn(self.h, None, None, None, self._err, ERRLEN))
-            raise BeomError("download_series: the handle keeps no series (set_series)")
-        cnt = self.lib.beom_series_count(nl, self.series_level)
-        rows = np.zeros((max(self.series_records, 1), M, cnt))
-        tstp = (C.c_int * max(self.series_records, 1))()
-        count = C.c_int(0)
-        self._check(fn(self.h, _dp(rows), tstp, C.byref(count), self._err, ERRLEN))
-        n = count.value
-        rows = rows[:n].copy()
+        n, tstp, rows = self._recorder_download("series", "series", self.series_level, self.series_records,
+                                                lambda lv: self.lib.beom_series_count(nl, lv))
         q = rows[:, :, :4 * nl].reshape(n, M, nl, 4)
-        out = {"count": n, "tstp": np.array(list(tstp)[:n], dtype=np.int64), "rows": rows,
+        out = {"count": n, "tstp": tstp, "rows": rows,
                "raw": np.array([combine_integral_rows(r[:, :4 * nl + 1]) for r in rows]).reshape(n, 4 * nl + 1),
                "eta2": rows[:, :, 4 * nl]}
         for k, name in enumerate(INTEGRAL_NAMES):
@@ -786,7 +806,7 @@ class _Series:
 TRACER_SERIES_NAMES = ("inv", "var", "fu", "fv", "cmin", "cmax")
 
 
-class _TracerSeries:
+class _TracerSeries(_Recorder):
     """A record per sampled step of the tracers' row inventories, variance, face fluxes and bounds, kept on the device
     (beom_set_tracer_series, include/beom_hip.h), with a level, stride and recorder of its own beside the series.  Shared by
     Engine and MultiEngine."""
@@ -798,9 +818,7 @@ class _TracerSeries:
         """level 1: inv, var per tracer and layer; 2: and fu, fv; 3: and cmin, cmax; 0 frees.  `records`: what the recorder
         holds between two download_tracer_series (a step call that would overflow it is refused).  Between steps only, after
         set_tracers."""
-        fn = self.lib.beom_multi_set_tracer_series if self._ser_multi else self.lib.beom_set_tracer_series
-        self._check(fn(self.h, int(level), int(stride), int(records), self._err, ERRLEN))
-        self.tracer_series_level, self.tracer_series_records = int(level), (int(records) if level else 0)
+        self.tracer_series_level, self.tracer_series_records = self._recorder_set("tracer_series", level, stride, records)
 
     def download_tracer_series(self) -> dict:
         """The records held, oldest first, and empties the recorder.  count, tstp[n]; rows[n, M, cnt] (M = mm+1 rows in global
@@ -809,22 +827,13 @@ class _TracerSeries:
         -inf where there is none), each [n, M, ntrc, nlay]; total[n, ntrc, nlay] = combine_integral_rows of inv; at level
         >= 2 transport = dl * fv, the tracer transport through the south faces of row j."""
         nl, M = self.p.nlay, self.p.mm + 1
-        fn = self.lib.beom_multi_download_tracer_series if self._ser_multi else self.lib.beom_download_tracer_series
         lv = self.info("tracer_series")                                  # (set_tracers with another count frees it)
-        if lv < 1:                                                       # (the library says why)
-            self._check(fn(self.h, None, None, None, self._err, ERRLEN))
-            raise BeomError("download_tracer_series: the handle keeps no tracer series (set_tracer_series)")
+        n, tstp, rows = self._recorder_download("tracer_series", "tracer series", lv, self.tracer_series_records,
+                                                lambda lv: self.lib.beom_tracer_series_count(self.ntrc, nl, lv))
         self.tracer_series_level = lv
         nq = 2 * lv
-        cnt = self.lib.beom_tracer_series_count(self.ntrc, nl, lv)
-        rows = np.zeros((max(self.tracer_series_records, 1), M, cnt))
-        tstp = (C.c_int * max(self.tracer_series_records, 1))()
-        count = C.c_int(0)
-        self._check(fn(self.h, _dp(rows), tstp, C.byref(count), self._err, ERRLEN))
-        n = count.value
-        rows = rows[:n].copy()
         q = rows.reshape(n, M, self.ntrc, nl, nq)
-        out = {"count": n, "tstp": np.array(list(tstp)[:n], dtype=np.int64), "rows": rows}
+        out = {"count": n, "tstp": tstp, "rows": rows}
         for m in range(nq):
             out[TRACER_SERIES_NAMES[m]] = q[..., m]
         out["total"] = np.array([combine_integral_rows(np.ascontiguousarray(r.reshape(M, self.ntrc * nl)))
@@ -836,6 +845,8 @@ class _TracerSeries:
 
 class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
+
+    _prefix = "beom_"
 
     def __init__(self, f: Fields, device: int = 0, variant: int = 0, dense_hint: int = 1,
                  upload: bool = True, slab_row0: int = 0, slab_mm: int = 0):
@@ -1078,16 +1089,12 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
 
     def sample_series(self):
         """Per-sweep entry: one record of the fields as they stand, under the last step's number, whatever the stride."""
-        rc = self.lib.beom_sample_series(self.h)
-        if rc != 0:
-            raise BeomError("beom_hip error %d: beom_sample_series (series set? recorder full?)" % rc)
+        self._recorder_sample("series", "series")
 
     def sample_tracer_series(self):
         """Per-sweep entry: one record of the tracers and the state as they stand, under the last step's number, whatever the
         stride."""
-        rc = self.lib.beom_sample_tracer_series(self.h)
-        if rc != 0:
-            raise BeomError("beom_hip error %d: beom_sample_tracer_series (tracer series set? recorder full?)" % rc)
+        self._recorder_sample("tracer_series", "tracer series")
 
     def rebuild_fluxes(self): self._check(self.lib.beom_rebuild_fluxes(self.h))
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
@@ -1121,10 +1128,7 @@ class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerS
             self.upload(**{k: getattr(f, k) for k in STATE_NAMES})
 
     _check = Engine._check
-    _trc_prefix = "beom_multi_"
-    _mom_multi = True
-    _flt_multi = True
-    _ser_multi = True
+    _prefix = "beom_multi_"
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:

@@ -30,6 +30,7 @@
 #include "beom_tracer_series.h"
 #include "beom_dense_host.h"
 #include "beom_plan.h"
+#include "beom_recorder.h"
 
 using beom_plan::StepFacts;
 using beom_plan::StepPlan;
@@ -119,6 +120,45 @@ struct Harmonics {
     double *sum[5][1 + 2 * BEOM_MAX_HARMONICS] = {};
     double gram[(1 + 2 * BEOM_MAX_HARMONICS) * (1 + 2 * BEOM_MAX_HARMONICS)] = {};      // (1+2K)^2 in use, row-major
 };
+
+// A recorder kept on the device, [nrec][rows][cnt] with the step of every held record: the series and the tracer series
+// share everything on the host but their kernels.  The constant part: the highest level, the entries per row of a frame with
+// ntrc tracers and nlay layers at a level, how the chunk partials of a launch are obtained (with the cell map, in the kind's
+// own order), the launch of one record, and the texts (no_tracer, which takes the caller's name: null where no tracer is needed).
+struct Recorder;
+struct RecorderKind {
+    int max_level;
+    int (*count)(int ntrc, int nlay, int level);
+    int (*scratch)(beom_engine *, Recorder &, int cnt, int nrows, char *errm, int errm_len);
+    void (*launch)(beom_engine *, int tstp);
+    const char *no_tracer, *none, *overflow;
+};
+static int series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
+static int tracer_series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
+static void launch_series(beom_engine *E, int tstp);
+static void launch_tracer_series(beom_engine *E, int tstp);
+constexpr RecorderKind kSeries{2, [](int, int nlay, int level) { return beom_series_count(nlay, level); },
+    series_scratch, launch_series, nullptr,
+    "beom_download_series: the handle keeps no series (beom_set_series)",
+    "beom_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
+    "empty it with beom_download_series, or take fewer steps per call"};
+constexpr RecorderKind kTracerSeries{3, beom_tracer_series_count,
+    tracer_series_scratch, launch_tracer_series,
+    "%s: the handle carries no tracer (beom_set_tracers comes first)",
+    "beom_download_tracer_series: the handle keeps no tracer series (beom_set_tracer_series)",
+    "beom_step: steps %d..%d would write %lld records of the tracer series (stride %d) but the recorder holds %lld of %d: "
+    "empty it with beom_download_tracer_series, or take fewer steps per call"};
+struct Recorder {
+    const RecorderKind *kind;
+    int level = 0, stride = 1, nrec = 0, jlo = 1, rows = 0;      // local rows jlo .. jlo+rows-1
+    bool by_caller = false;            // a band: beom_step takes no record by itself (beom_band_set_series and its like)
+    double *rec = nullptr;
+    std::vector<int> tstp;             // the step of every held record (its size = the records held)
+    double *part = nullptr;            // the tracer series: the chunk partials of `batch` rows at a time (kTracerSeriesScratch)
+    int batch = 0;
+    std::vector<void *> allocs;
+};
+static bool recorder_due(const Recorder &R, int tstp) { return R.level > 0 && tstp % R.stride == 0 && (int)R.tstp.size() < R.nrec; }
 
 struct beom_engine {
     beom_params P;
@@ -233,21 +273,13 @@ struct beom_engine {
     // harmonics (beom_set_harmonics; beom_harmonics.h): per field the reference and 1 + 2K shifted sums in arrays of the
     // state's shape, the normal matrix on the host; "moments_by_caller" governs their samples too
     Harmonics harm;
-    // series (beom_set_series; beom_series.h): a recorder [nrec][ser_rows][count] of the row sums of local rows ser_jlo ..
-    // ser_jlo+ser_rows-1, one record behind every step with tstp % stride == 0, with the step of every held record
-    int ser_level = 0, ser_stride = 1, ser_nrec = 0, ser_jlo = 1, ser_rows = 0;
-    bool ser_by_caller = false;        // a band: beom_step takes no record by itself (beom_band_set_series)
-    double *ser_rec = nullptr;
-    std::vector<int> ser_tstp;         // (its size = the records held)
-    std::vector<void *> ser_allocs;
-    // tracer series (beom_set_tracer_series; beom_tracer_series.h): a recorder [nrec][tser_rows][ntrc*nlay*2*level] of its
-    // own, with level, stride and rows of its own; the chunk partials of tser_batch rows at a time (kTracerSeriesScratch)
-    int tser_level = 0, tser_stride = 1, tser_nrec = 0, tser_jlo = 1, tser_rows = 0, tser_batch = 0;
+    // series (beom_set_series; beom_series.h): the row sums of the recorder's rows, one record behind every step with
+    // tstp % stride == 0
+    Recorder ser{&kSeries};
+    // tracer series (beom_set_tracer_series; beom_tracer_series.h): a recorder [nrec][rows][ntrc*nlay*2*level] of its own,
+    // with level, stride and rows of its own
+    Recorder tser{&kTracerSeries};
     int tser_batch_opt = 0;            // option "tracer_series_batch": rows per launch (0 = by the bound on the scratch)
-    bool tser_by_caller = false;       // a band: beom_step takes no record by itself (beom_band_set_tracer_series)
-    double *tser_rec = nullptr, *tser_part = nullptr;
-    std::vector<int> tser_tstp;        // (its size = the records held)
-    std::vector<void *> tser_allocs;
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -285,6 +317,12 @@ int dev_alloc(beom_engine *E, T **p, size_t n, char *errm, int errm_len, bool ze
 // elements of an array of the state's shape [nlay][n1] and of the tracers' shape [ntrc][nlay][n1]
 size_t state_cells(const beom_engine *E) { return (size_t)E->d.nlay * (size_t)E->d.n1; }
 size_t tracer_cells(const beom_engine *E) { return (size_t)E->ntrc * state_cells(E); }
+
+int pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+// The tree over a row of L columns (beom_integrals.h): chunks of 64 columns, their count padded to a power of two, and the
+// lanes the first level of a chunk's own tree spans.
+struct RowTree { int nch, nchp2, width; };
+RowTree row_tree(int L) { return {(L + 63) / 64, pow2_ceil((L + 63) / 64), std::min(64, pow2_ceil(L))}; }
 
 // one slice [0:ndeg][inner] (x K interleaved levels, level m) of a caller array <-> its device array
 template <class T, bool REMAP = false>
@@ -581,7 +619,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser_allocs, &E->tser_allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -949,53 +987,45 @@ static void launch_tracer_moments(beom_engine *E, int tstp) {
     accum_note_sample(E->tmom, tstp);
 }
 // one record of the series (beom_series.h) of the fields as they stand into the next free slot, under step tstp
-static bool series_due(const beom_engine *E, int tstp) {
-    return E->ser_level > 0 && tstp % E->ser_stride == 0 && (int)E->ser_tstp.size() < E->ser_nrec;
-}
 static void launch_series(beom_engine *E, int tstp) {
     const DevView &d = E->d;
-    const int count = (E->ser_level >= 2 ? 6 : 4) * d.nlay + 1, nch = (d.L + 63) / 64;
-    int nchp2 = 1, width = 1;
-    while (nchp2 < nch) nchp2 <<= 1;
-    while (width < d.L && width < 64) width <<= 1;
-    double *rec = E->ser_rec + E->ser_tstp.size() * (size_t)E->ser_rows * count;
-    const dim3 g((unsigned)nch, (unsigned)((E->ser_rows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
+    Recorder &R = E->ser;
+    const int count = beom_series_count(d.nlay, R.level);
+    const RowTree t = row_tree(d.L);
+    double *rec = R.rec + R.tstp.size() * (size_t)R.rows * count;
+    const dim3 g((unsigned)t.nch, (unsigned)((R.rows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
     const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
     // (the two kernels take the same arguments; named here and not through pick, which would move k_integral_rows behind
     // its other user, beom_integral_rows, in the code object)
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, g, b, 0, E->stream, d, E->ser_jlo, E->ser_rows, width, E->integ_xper, E->integ_yper, map, E->integ_part); };
-    if (E->ser_level == 1) { if (E->dense) go(k_integral_rows<true>); else go(k_integral_rows<false>); }
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, g, b, 0, E->stream, d, R.jlo, R.rows, t.width, E->integ_xper, E->integ_yper, map, E->integ_part); };
+    if (R.level == 1) { if (E->dense) go(k_integral_rows<true>); else go(k_integral_rows<false>); }
     else if (E->dense) go(k_series_rows<true>); else go(k_series_rows<false>);
-    hipLaunchKernelGGL(k_integral_chunks, dim3((unsigned)E->ser_rows), dim3(64), 0, E->stream,
-                       (const double *)E->integ_part, rec, count, nch, nchp2);
-    E->ser_tstp.push_back(tstp);
+    hipLaunchKernelGGL(k_integral_chunks, dim3((unsigned)R.rows), dim3(64), 0, E->stream,
+                       (const double *)E->integ_part, rec, count, t.nch, t.nchp2);
+    R.tstp.push_back(tstp);
 }
 // one record of the tracer series (beom_tracer_series.h) of q, hlay, h_u, h_v as they stand into the next free slot, under step
-// tstp: tser_batch rows per launch, every row finished on its own
-static bool tracer_series_due(const beom_engine *E, int tstp) {
-    return E->tser_level > 0 && tstp % E->tser_stride == 0 && (int)E->tser_tstp.size() < E->tser_nrec;
-}
+// tstp: `batch` rows per launch, every row finished on its own
 static void launch_tracer_series(beom_engine *E, int tstp) {
     const DevView &d = E->d;
-    const int nq = 2 * E->tser_level, per = E->ntrc * d.nlay, cnt = per * nq, nch = (d.L + 63) / 64;
-    int nchp2 = 1, width = 1;
-    while (nchp2 < nch) nchp2 <<= 1;
-    while (width < d.L && width < 64) width <<= 1;
-    double *rec = E->tser_rec + E->tser_tstp.size() * (size_t)E->tser_rows * cnt;
+    Recorder &R = E->tser;
+    const int nq = 2 * R.level, per = E->ntrc * d.nlay, cnt = per * nq;
+    const RowTree t = row_tree(d.L);
+    double *rec = R.rec + R.tstp.size() * (size_t)R.rows * cnt;
     const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
-    for (int r0 = 0; r0 < E->tser_rows; r0 += E->tser_batch) {
-        const int nr = std::min(E->tser_batch, E->tser_rows - r0);
-        const dim3 g((unsigned)nch, (unsigned)((nr + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
-        pick_int<1, 3>(E->tser_level, [&](auto lv) {
+    for (int r0 = 0; r0 < R.rows; r0 += R.batch) {
+        const int nr = std::min(R.batch, R.rows - r0);
+        const dim3 g((unsigned)t.nch, (unsigned)((nr + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
+        pick_int<1, 3>(R.level, [&](auto lv) {
             pick([&](auto dense) {
-                hipLaunchKernelGGL((k_tracer_series_rows<dense, lv>), g, b, 0, E->stream, d, (const double *)E->trc_q, E->ntrc, E->tser_jlo + r0, nr,
-                                   width, E->integ_xper, E->integ_yper, map, E->tser_part);
+                hipLaunchKernelGGL((k_tracer_series_rows<dense, lv>), g, b, 0, E->stream, d, (const double *)E->trc_q, E->ntrc, R.jlo + r0, nr,
+                                   t.width, E->integ_xper, E->integ_yper, map, R.part);
             }, E->dense);
         });
         hipLaunchKernelGGL(k_tracer_series_chunks, dim3((unsigned)nr, (unsigned)per), dim3(64), 0, E->stream,
-                           (const double *)E->tser_part, rec + (size_t)r0 * cnt, cnt, nq, nch, nchp2);
+                           (const double *)R.part, rec + (size_t)r0 * cnt, cnt, nq, t.nch, t.nchp2);
     }
-    E->tser_tstp.push_back(tstp);
+    R.tstp.push_back(tstp);
 }
 static void launch_mont(beom_engine *E, int ilay) {
     if (ilay == 0 && E->d.nlay <= 8) {         // all layers of a column in one thread: instantiated for 1..8 layers
@@ -1229,8 +1259,8 @@ static void one_step(beom_engine *E, const StepPlan &p, int flt = -1) {
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->harm.acc, tstp)) launch_harmonics(E, tstp, p.ctim);
-    if (!E->ser_by_caller && series_due(E, tstp)) launch_series(E, tstp);
-    if (!E->tser_by_caller && tracer_series_due(E, tstp)) launch_tracer_series(E, tstp);
+    for (const Recorder *R : {&E->ser, &E->tser})
+        if (!R->by_caller && recorder_due(*R, tstp)) R->kind->launch(E, tstp);
 }
 
 // rows [jlo, jlo+nrows) of hlay,u,v,h_u,h_v  ->  dbuf (device memory, 5*nlay*nrows*(lm+1) doubles); the *2 forms move a second
@@ -1250,15 +1280,6 @@ static int rows_copy(beom_handle E, int jlo, int nrows, void *dbuf, int jlo2, vo
     }
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
-// Can a recorder of nrec records, `held` of them taken, hold those due in steps tstp_first .. tstp_first+nsteps-1?  If not,
-// the refusal goes to errm in the words of fmt (first step, last step, records due, stride, held, nrec).
-static bool recorder_holds(int tstp_first, int nsteps, int stride, size_t held, int nrec, char *errm, int errm_len, const char *fmt) {
-    long long due = 0;
-    for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp) due += tstp % stride == 0;
-    if ((long long)held + due <= nrec) return true;
-    set_err(errm, errm_len, fmt, tstp_first, tstp_first + nsteps - 1, due, stride, (long long)held, nrec);
-    return false;
-}
 extern "C" {
 
 int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd8, double dt_r,
@@ -1271,17 +1292,12 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
     if (flt && !E->flt_ready) { set_err(errm, errm_len, "beom_step: the handle's %lld floats have no positions yet (beom_upload_floats)", E->nflt); return -3; }
     // a recorder must hold every record of the call: refused before anything is launched
     if (flt && E->flt_nrec > 0 &&
-        !recorder_holds(tstp_first, nsteps, E->flt_stride, E->flt_rec_tstp.size(), E->flt_nrec, errm, errm_len,
-                        "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
-                        "empty it with beom_download_float_track, or take fewer steps per call")) return -3;
-    if (E->ser_level > 0 && !E->ser_by_caller &&
-        !recorder_holds(tstp_first, nsteps, E->ser_stride, E->ser_tstp.size(), E->ser_nrec, errm, errm_len,
-                        "beom_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
-                        "empty it with beom_download_series, or take fewer steps per call")) return -3;
-    if (E->tser_level > 0 && !E->tser_by_caller &&
-        !recorder_holds(tstp_first, nsteps, E->tser_stride, E->tser_tstp.size(), E->tser_nrec, errm, errm_len,
-                        "beom_step: steps %d..%d would write %lld records of the tracer series (stride %d) but the recorder holds %lld of %d: "
-                        "empty it with beom_download_tracer_series, or take fewer steps per call")) return -3;
+        !beom_recorder::holds(tstp_first, nsteps, E->flt_stride, E->flt_rec_tstp.size(), E->flt_nrec, errm, errm_len,
+                              "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
+                              "empty it with beom_download_float_track, or take fewer steps per call")) return -3;
+    for (const Recorder *R : {&E->ser, &E->tser})
+        if (R->level > 0 && !R->by_caller &&
+            !beom_recorder::holds(tstp_first, nsteps, R->stride, R->tstp.size(), R->nrec, errm, errm_len, R->kind->overflow)) return -3;
     HIP_TRY(hipSetDevice(E->device));
     for (int tstp = tstp_first; tstp < tstp_first + nsteps; ++tstp)      // (the facts move with the steps: mont_levels_valid)
         one_step(E, beom_plan::plan_step(facts_of(E), tstp, tres, dtd8, dt_r, rsta, n_3d),
@@ -1475,8 +1491,6 @@ int beom_download_diag(beom_handle E, float *pvor4, float *mont4, float *vcc4, c
 }
 
 // ---- conservation integrals (beom_integrals.h) -----------------------------------------------------------------------
-static int pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-
 int beom_integral_count(int nlay) { return 4 * nlay + 1; }
 
 // Whether the frame wraps (integ_xper, integ_yper) and, on the table path, the packed cell of every (i, j) (integ_cellmap):
@@ -1530,19 +1544,19 @@ int beom_integral_rows(beom_handle E, int jlo, int nrows, double *rows, char *er
     DevView &d = E->d;
     if (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M) { set_err(errm, errm_len, "beom_integral_rows: rows %d..%d outside 1..%d", jlo, jlo + nrows - 1, d.M); return -3; }
     HIP_TRY(hipSetDevice(E->device));
-    const int count = 4 * d.nlay + 1, nch = (d.L + 63) / 64, nchp2 = pow2_ceil(nch);
-    const int width = std::min(64, pow2_ceil(d.L));
-    if (nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "beom_integral_rows: rows of more than %d columns", 64 * 64 * kIntegralMaxGroups); return -4; }
+    const int count = 4 * d.nlay + 1;
+    const RowTree t = row_tree(d.L);
+    if (t.nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "beom_integral_rows: rows of more than %d columns", 64 * 64 * kIntegralMaxGroups); return -4; }
     if (const int rc = ensure_integ_scratch(E, count, errm, errm_len)) return rc;
     if (const int rc = ensure_cellmap(E, errm, errm_len)) return rc;
-    const dim3 g((unsigned)nch, (unsigned)((nrows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
-    if (E->dense) hipLaunchKernelGGL(k_integral_rows<true>, g, b, 0, E->stream, d, jlo, nrows, width, E->integ_xper, E->integ_yper,
+    const dim3 g((unsigned)t.nch, (unsigned)((nrows + BEOM_TILE_Y - 1) / BEOM_TILE_Y), 1), b(BEOM_BLOCK);
+    if (E->dense) hipLaunchKernelGGL(k_integral_rows<true>, g, b, 0, E->stream, d, jlo, nrows, t.width, E->integ_xper, E->integ_yper,
                                      (const int32_t *)nullptr, E->integ_part);
-    else hipLaunchKernelGGL(k_integral_rows<false>, g, b, 0, E->stream, d, jlo, nrows, width, E->integ_xper, E->integ_yper,
+    else hipLaunchKernelGGL(k_integral_rows<false>, g, b, 0, E->stream, d, jlo, nrows, t.width, E->integ_xper, E->integ_yper,
                             (const int32_t *)E->integ_cellmap, E->integ_part);
     const long long nt = (long long)nrows * count;
     hipLaunchKernelGGL(k_integral_chunks, dim3((unsigned)nrows), dim3(64), 0, E->stream,
-                       (const double *)E->integ_part, E->integ_rows, count, nch, nchp2);
+                       (const double *)E->integ_part, E->integ_rows, count, t.nch, t.nchp2);
     HIP_TRY(hipMemcpyAsync(rows, E->integ_rows, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, E->stream));
     HIP_TRY(hipStreamSynchronize(E->stream));
     HIP_TRY(hipGetLastError());
@@ -1572,147 +1586,110 @@ int beom_integrals(beom_handle E, double *out, char *errm, int errm_len) {
     return beom_integral_combine(rows.data(), M, count, out);
 }
 
-// ---- series of row sums (beom_series.h) ----------------------------------------------------------------------------------
+// ---- the recorders: series of row sums (beom_series.h) and tracer series (beom_tracer_series.h) ---------------------------
 int beom_series_count(int nlay, int level) { return (level >= 2 ? 6 : 4) * nlay + 1; }
+int beom_tracer_series_count(int ntrc, int nlay, int level) { return ntrc * nlay * 2 * level; }
 
-static void series_free(beom_engine *E) {
-    free_list(E->ser_allocs);
-    E->ser_level = 0; E->ser_stride = 1; E->ser_nrec = 0; E->ser_jlo = 1; E->ser_rows = 0; E->ser_by_caller = false;
-    E->ser_rec = nullptr;
-    E->ser_tstp.clear();
+// The series' chunk partials go to the integrals' scratch, sized for the larger count.
+static int series_scratch(beom_engine *E, Recorder &, int cnt, int, char *errm, int errm_len) {
+    if (const int rc = ensure_integ_scratch(E, cnt, errm, errm_len)) return rc;
+    return ensure_cellmap(E, errm, errm_len);
+}
+// The tracer series' chunk partials of a launch stay under this many bytes: a record is taken in batches of rows (whole
+// workgroups of BEOM_TILE_Y rows; never fewer than one), every row finished on its own, so the batches cannot change a bit.
+constexpr size_t kTracerSeriesScratch = 64u << 20;
+static int tracer_series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len) {
+    const size_t per_row = (size_t)row_tree(E->d.L).nch * cnt;
+    size_t batch = E->tser_batch_opt > 0 ? (size_t)E->tser_batch_opt : kTracerSeriesScratch / (per_row * sizeof(double));
+    batch = std::max<size_t>(batch / BEOM_TILE_Y * BEOM_TILE_Y, BEOM_TILE_Y);
+    batch = std::min<size_t>(batch, (size_t)nrows);
+    R.batch = (int)batch;
+    if (const int rc = ensure_cellmap(E, errm, errm_len)) return rc;
+    return alloc_plain(E, R.allocs, &R.part, batch * per_row, errm, errm_len, false);
+}
+
+static void recorder_free(Recorder &R) {
+    free_list(R.allocs);
+    R.level = 0; R.stride = 1; R.nrec = 0; R.jlo = 1; R.rows = 0; R.batch = 0; R.by_caller = false;
+    R.rec = R.part = nullptr;
+    R.tstp.clear();
 }
 
 // level 0 frees; else a recorder of nrec records of local rows jlo .. jlo+nrows-1.  A failed allocation leaves level 0
-static int series_set(beom_engine *E, const char *who, int level, int stride, int nrec, int jlo, int nrows, bool by_caller,
-                      char *errm, int errm_len) {
+static int recorder_set(beom_engine *E, Recorder beom_engine::*which, const char *who, int level, int stride, int nrec, int jlo,
+                        int nrows, bool by_caller, char *errm, int errm_len) {
     if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (level < 0 || level > 2 || (level > 0 && (stride < 1 || nrec < 1))) {
-        set_err(errm, errm_len, "%s: level %d, stride %d, %d records (level 0..2, stride >= 1, records >= 1)", who, level, stride, nrec);
+    Recorder &R = E->*which;
+    const RecorderKind &K = *R.kind;
+    if (level < 0 || level > K.max_level || (level > 0 && (stride < 1 || nrec < 1))) {
+        set_err(errm, errm_len, "%s: level %d, stride %d, %d records (level 0..%d, stride >= 1, records >= 1)", who, level, stride, nrec, K.max_level);
         return -3;
     }
+    if (K.no_tracer && level > 0 && E->ntrc < 1) { set_err(errm, errm_len, K.no_tracer, who); return -3; }
     const DevView &d = E->d;
     if (level > 0 && (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M)) { set_err(errm, errm_len, "%s: rows %d..%d outside 1..%d", who, jlo, jlo + nrows - 1, d.M); return -3; }
-    if (level > 0 && pow2_ceil((d.L + 63) / 64) / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
+    if (level > 0 && row_tree(d.L).nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    series_free(E);
+    recorder_free(R);
     if (level == 0) return 0;
-    const int count = beom_series_count(d.nlay, level);
-    int rc = ensure_integ_scratch(E, count, errm, errm_len);
-    if (!rc) rc = ensure_cellmap(E, errm, errm_len);
-    if (!rc) rc = alloc_aligned(E, E->ser_allocs, &E->ser_rec, (size_t)nrec * nrows * count, errm, errm_len);
-    if (rc) { series_free(E); return rc; }
-    E->ser_level = level; E->ser_stride = stride; E->ser_nrec = nrec; E->ser_jlo = jlo; E->ser_rows = nrows; E->ser_by_caller = by_caller;
+    const int cnt = K.count(E->ntrc, d.nlay, level);
+    int rc = K.scratch(E, R, cnt, nrows, errm, errm_len);
+    if (!rc) rc = alloc_aligned(E, R.allocs, &R.rec, (size_t)nrec * nrows * cnt, errm, errm_len);
+    if (rc) { recorder_free(R); return rc; }
+    R.level = level; R.stride = stride; R.nrec = nrec; R.jlo = jlo; R.rows = nrows; R.by_caller = by_caller;
     HIP_TRY(hipStreamSynchronize(E->stream));
+    return 0;
+}
+
+static int recorder_sample(beom_engine *E, Recorder beom_engine::*which) {
+    if (!E) return -1;
+    const Recorder &R = E->*which;
+    if (R.level < 1 || (int)R.tstp.size() >= R.nrec) return -3;
+    if (hipSetDevice(E->device) != hipSuccess) return -9;
+    R.kind->launch(E, E->last_tstp);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+// the records held, oldest first, with their steps; empties the recorder
+static int recorder_download(beom_engine *E, Recorder beom_engine::*which, double *rows, int *tstp, int *count, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    Recorder &R = E->*which;
+    if (R.level < 1) { set_err(errm, errm_len, "%s", R.kind->none); return -3; }
+    HIP_TRY(hipSetDevice(E->device));
+    const size_t n = R.tstp.size(), per = (size_t)R.rows * R.kind->count(E->ntrc, E->d.nlay, R.level);
+    if (rows && n) {
+        HIP_TRY(hipMemcpyAsync(rows, R.rec, n * per * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+        HIP_TRY(hipStreamSynchronize(E->stream));
+        HIP_TRY(hipGetLastError());
+    }
+    if (tstp) std::copy(R.tstp.begin(), R.tstp.end(), tstp);
+    if (count) *count = (int)n;
+    R.tstp.clear();
     return 0;
 }
 
 int beom_set_series(beom_handle E, int level, int stride, int nrec, char *errm, int errm_len) {
-    return series_set(E, "beom_set_series", level, stride, nrec, 1, E ? E->d.M : 0, false, errm, errm_len);
+    return recorder_set(E, &beom_engine::ser, "beom_set_series", level, stride, nrec, 1, E ? E->d.M : 0, false, errm, errm_len);
 }
-
 int beom_band_set_series(beom_handle E, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len) {
-    return series_set(E, "beom_band_set_series", level, stride, nrec, jlo, nrows, true, errm, errm_len);
+    return recorder_set(E, &beom_engine::ser, "beom_band_set_series", level, stride, nrec, jlo, nrows, true, errm, errm_len);
+}
+int beom_set_tracer_series(beom_handle E, int level, int stride, int nrec, char *errm, int errm_len) {
+    return recorder_set(E, &beom_engine::tser, "beom_set_tracer_series", level, stride, nrec, 1, E ? E->d.M : 0, false, errm, errm_len);
+}
+int beom_band_set_tracer_series(beom_handle E, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len) {
+    return recorder_set(E, &beom_engine::tser, "beom_band_set_tracer_series", level, stride, nrec, jlo, nrows, true, errm, errm_len);
 }
 
-int beom_sample_series(beom_handle E) {
-    if (!E) return -1;
-    if (E->ser_level < 1 || (int)E->ser_tstp.size() >= E->ser_nrec) return -3;
-    if (hipSetDevice(E->device) != hipSuccess) return -9;
-    launch_series(E, E->last_tstp);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
+int beom_sample_series(beom_handle E) { return recorder_sample(E, &beom_engine::ser); }
+int beom_sample_tracer_series(beom_handle E) { return recorder_sample(E, &beom_engine::tser); }
 
 int beom_download_series(beom_handle E, double *rows, int *tstp, int *count, char *errm, int errm_len) {
-    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (E->ser_level < 1) { set_err(errm, errm_len, "beom_download_series: the handle keeps no series (beom_set_series)"); return -3; }
-    HIP_TRY(hipSetDevice(E->device));
-    const size_t n = E->ser_tstp.size(), per = (size_t)E->ser_rows * beom_series_count(E->d.nlay, E->ser_level);
-    if (rows && n) {
-        HIP_TRY(hipMemcpyAsync(rows, E->ser_rec, n * per * sizeof(double), hipMemcpyDeviceToHost, E->stream));
-        HIP_TRY(hipStreamSynchronize(E->stream));
-        HIP_TRY(hipGetLastError());
-    }
-    if (tstp) std::copy(E->ser_tstp.begin(), E->ser_tstp.end(), tstp);
-    if (count) *count = (int)n;
-    E->ser_tstp.clear();
-    return 0;
+    return recorder_download(E, &beom_engine::ser, rows, tstp, count, errm, errm_len);
 }
-
-// ---- tracer series (beom_tracer_series.h) ---------------------------------------------------------------------------------
-// The chunk partials of a launch stay under this many bytes: a record is taken in batches of rows (whole workgroups of
-// BEOM_TILE_Y rows; never fewer than one), every row finished on its own, so the batches cannot change a bit.
-constexpr size_t kTracerSeriesScratch = 64u << 20;
-
-int beom_tracer_series_count(int ntrc, int nlay, int level) { return ntrc * nlay * 2 * level; }
-
-static void tracer_series_free(beom_engine *E) {
-    free_list(E->tser_allocs);
-    E->tser_level = 0; E->tser_stride = 1; E->tser_nrec = 0; E->tser_jlo = 1; E->tser_rows = 0; E->tser_batch = 0; E->tser_by_caller = false;
-    E->tser_rec = E->tser_part = nullptr;
-    E->tser_tstp.clear();
-}
-
-// level 0 frees; else a recorder of nrec records of local rows jlo .. jlo+nrows-1.  A failed allocation leaves level 0
-static int tracer_series_set(beom_engine *E, const char *who, int level, int stride, int nrec, int jlo, int nrows, bool by_caller,
-                             char *errm, int errm_len) {
-    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (level < 0 || level > 3 || (level > 0 && (stride < 1 || nrec < 1))) {
-        set_err(errm, errm_len, "%s: level %d, stride %d, %d records (level 0..3, stride >= 1, records >= 1)", who, level, stride, nrec);
-        return -3;
-    }
-    if (level > 0 && E->ntrc < 1) { set_err(errm, errm_len, "%s: the handle carries no tracer (beom_set_tracers comes first)", who); return -3; }
-    const DevView &d = E->d;
-    if (level > 0 && (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M)) { set_err(errm, errm_len, "%s: rows %d..%d outside 1..%d", who, jlo, jlo + nrows - 1, d.M); return -3; }
-    if (level > 0 && pow2_ceil((d.L + 63) / 64) / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
-    HIP_TRY(hipSetDevice(E->device));
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    tracer_series_free(E);
-    if (level == 0) return 0;
-    const size_t cnt = (size_t)beom_tracer_series_count(E->ntrc, d.nlay, level), per_row = (size_t)((d.L + 63) / 64) * cnt;
-    size_t batch = E->tser_batch_opt > 0 ? (size_t)E->tser_batch_opt : kTracerSeriesScratch / (per_row * sizeof(double));
-    batch = std::max<size_t>(batch / BEOM_TILE_Y * BEOM_TILE_Y, BEOM_TILE_Y);
-    batch = std::min<size_t>(batch, (size_t)nrows);
-    int rc = ensure_cellmap(E, errm, errm_len);
-    if (!rc) rc = alloc_plain(E, E->tser_allocs, &E->tser_part, batch * per_row, errm, errm_len, false);
-    if (!rc) rc = alloc_aligned(E, E->tser_allocs, &E->tser_rec, (size_t)nrec * nrows * cnt, errm, errm_len);
-    if (rc) { tracer_series_free(E); return rc; }
-    E->tser_level = level; E->tser_stride = stride; E->tser_nrec = nrec; E->tser_jlo = jlo; E->tser_rows = nrows; E->tser_batch = (int)batch;
-    E->tser_by_caller = by_caller;
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    return 0;
-}
-
-int beom_set_tracer_series(beom_handle E, int level, int stride, int nrec, char *errm, int errm_len) {
-    return tracer_series_set(E, "beom_set_tracer_series", level, stride, nrec, 1, E ? E->d.M : 0, false, errm, errm_len);
-}
-
-int beom_band_set_tracer_series(beom_handle E, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len) {
-    return tracer_series_set(E, "beom_band_set_tracer_series", level, stride, nrec, jlo, nrows, true, errm, errm_len);
-}
-
-int beom_sample_tracer_series(beom_handle E) {
-    if (!E) return -1;
-    if (E->tser_level < 1 || (int)E->tser_tstp.size() >= E->tser_nrec) return -3;
-    if (hipSetDevice(E->device) != hipSuccess) return -9;
-    launch_tracer_series(E, E->last_tstp);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
 int beom_download_tracer_series(beom_handle E, double *rows, int *tstp, int *count, char *errm, int errm_len) {
-    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
-    if (E->tser_level < 1) { set_err(errm, errm_len, "beom_download_tracer_series: the handle keeps no tracer series (beom_set_tracer_series)"); return -3; }
-    HIP_TRY(hipSetDevice(E->device));
-    const size_t n = E->tser_tstp.size(), per = (size_t)E->tser_rows * beom_tracer_series_count(E->ntrc, E->d.nlay, E->tser_level);
-    if (rows && n) {
-        HIP_TRY(hipMemcpyAsync(rows, E->tser_rec, n * per * sizeof(double), hipMemcpyDeviceToHost, E->stream));
-        HIP_TRY(hipStreamSynchronize(E->stream));
-        HIP_TRY(hipGetLastError());
-    }
-    if (tstp) std::copy(E->tser_tstp.begin(), E->tser_tstp.end(), tstp);
-    if (count) *count = (int)n;
-    E->tser_tstp.clear();
-    return 0;
+    return recorder_download(E, &beom_engine::tser, rows, tstp, count, errm, errm_len);
 }
 
 // ---- passive tracers (beom_tracers.h) -----------------------------------------------------------------------------------
@@ -1737,7 +1714,7 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); tracer_series_free(E); }        // (their arrays have the tracers' shape)
+    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); recorder_free(E->tser); }        // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
@@ -2370,10 +2347,10 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_moments")) return E->tmom.level;
     if (!strcmp(what, "tracer_moment_samples")) return (int)std::min<long long>(E->tmom.count, 2000000000ll);
     if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom.launches, 2000000000ll);     // all calls so far
-    if (!strcmp(what, "tracer_series")) return E->tser_level;
-    if (!strcmp(what, "tracer_series_records")) return (int)E->tser_tstp.size();
-    if (!strcmp(what, "series")) return E->ser_level;
-    if (!strcmp(what, "series_records")) return (int)E->ser_tstp.size();
+    if (!strcmp(what, "tracer_series")) return E->tser.level;
+    if (!strcmp(what, "tracer_series_records")) return (int)E->tser.tstp.size();
+    if (!strcmp(what, "series")) return E->ser.level;
+    if (!strcmp(what, "series_records")) return (int)E->ser.tstp.size();
     if (!strcmp(what, "harmonics")) return E->harm.nfreq;
     if (!strcmp(what, "harmonic_level")) return E->harm.acc.level;
     if (!strcmp(what, "harmonic_samples")) return (int)std::min<long long>(E->harm.acc.count, 2000000000ll);

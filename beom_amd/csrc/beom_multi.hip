@@ -39,6 +39,7 @@
 #include "../../include/beom_hip.h"
 #include "beom_bands_host.h"
 #include "beom_dense_host.h"
+#include "beom_recorder.h"
 
 using namespace beom_bands;
 
@@ -1443,38 +1444,79 @@ int beom_multi_integral_rows_local(beom_multi_handle M, int *own0, int *own1, do
     return band_integral_rows(M, 0, rows, errm, errm_len);
 }
 
-// Series (beom_series.h) of a frame cut into bands: a band owns whole rows, so its records' rows are the frame's.
-int beom_multi_set_series(beom_multi_handle M, int level, int stride, int nrec, char *errm, int errm_len) {
+// Series (beom_series.h) and tracer series (beom_tracer_series.h) of a frame cut into bands: a band owns whole rows, so its
+// records' rows are the frame's.  What tells the two recorders apart: the record, the engine's entry points, the entries per
+// row, who is refused (and what the refusal of set and download is told), the highest level, and the texts.
+struct SeriesKind {
+    beom_multi::Series beom_multi::*rec;
+    int (*set)(beom_handle, int, int, int, char *, int);
+    int (*band_set)(beom_handle, int, int, int, int, int, char *, int);
+    int (*sample)(beom_handle);
+    int (*download)(beom_handle, double *, int *, int *, char *, int);
+    int (*count)(int ntrc, int nlay, int level);
+    int (*refused)(beom_multi *, const char *, char *, int);
+    const char *refusal[2];
+    int max_level;
+    const char *failed, *bad_args, *no_tracer, *none, *band_held, *sample_failed, *overflow;
+};
+static const SeriesKind kSeries{
+    &beom_multi::ser, beom_set_series, beom_band_set_series, beom_sample_series, beom_download_series,
+    [](int, int nlay, int level) { return beom_series_count(nlay, level); }, moments_refused,
+    {"beom_multi_set_series: a handle that holds one band's window keeps no series (its rows are nowhere assembled); use a handle created from the global arrays",
+     "beom_multi_download_series: this handle holds a window and keeps no series"},
+    2,
+    "beom_multi_set_series: an earlier step failed half way; destroy the handle",
+    "beom_multi_set_series: level %d, stride %d, %d records (level 0..2, stride >= 1, records >= 1)", nullptr,
+    "beom_multi_download_series: the handle keeps no series (beom_multi_set_series)",
+    "beom_multi_download_series: band %d holds %d records, the handle %zu",
+    "beom_sample_series failed on band %d (step %d)",
+    "beom_multi_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
+    "empty it with beom_multi_download_series, or take fewer steps per call"};
+static const SeriesKind kTracerSeries{
+    &beom_multi::tser, beom_set_tracer_series, beom_band_set_tracer_series, beom_sample_tracer_series, beom_download_tracer_series,
+    beom_tracer_series_count, tracers_refused,
+    {"beom_multi_set_tracer_series", "beom_multi_download_tracer_series"},
+    3,
+    "beom_multi_set_tracer_series: an earlier step failed half way; destroy the handle",
+    "beom_multi_set_tracer_series: level %d, stride %d, %d records (level 0..3, stride >= 1, records >= 1)",
+    "beom_multi_set_tracer_series: the handle carries no tracer (beom_multi_set_tracers comes first)",
+    "beom_multi_download_tracer_series: the handle keeps no tracer series (beom_multi_set_tracer_series)",
+    "beom_multi_download_tracer_series: band %d holds %d records, the handle %zu",
+    "beom_sample_tracer_series failed on band %d (step %d)",
+    "beom_multi_step: steps %d..%d would write %lld records of the tracer series (stride %d) but the recorder holds %lld of %d: "
+    "empty it with beom_multi_download_tracer_series, or take fewer steps per call"};
+
+static int multi_set_recorder(beom_multi *M, const SeriesKind &K, int level, int stride, int nrec, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_series: an earlier step failed half way; destroy the handle"); return -30; }
-    if (level < 0 || level > 2 || (level > 0 && (stride < 1 || nrec < 1))) {
-        m_err(errm, errm_len, "beom_multi_set_series: level %d, stride %d, %d records (level 0..2, stride >= 1, records >= 1)", level, stride, nrec);
-        return -3;
-    }
-    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_set_series: a handle that holds one band's window keeps no series (its rows are nowhere assembled); use a handle created from the global arrays"); return -6; }
+    if (M->failed) { m_err(errm, errm_len, "%s", K.failed); return -30; }
+    if (level < 0 || level > K.max_level || (level > 0 && (stride < 1 || nrec < 1))) { m_err(errm, errm_len, K.bad_args, level, stride, nrec); return -3; }
+    M_RC(K.refused(M, K.refusal[0], errm, errm_len));
+    if (K.no_tracer && level > 0 && M->ntrc < 1) { m_err(errm, errm_len, "%s", K.no_tracer); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
-    M->ser = {};
+    beom_multi::Series &S = M->*K.rec;
+    S = {};
     int rc = 0;
     for (int k = 0; k < M->n && !rc; ++k) {
         const Band &s = M->band[k];
-        rc = multi_whole(M) ? beom_set_series(M->eng[k], level, stride, nrec, errm, errm_len)
-                            : beom_band_set_series(M->eng[k], level, stride, nrec, s.gs + 1, s.nown(), errm, errm_len);
+        rc = multi_whole(M) ? K.set(M->eng[k], level, stride, nrec, errm, errm_len)
+                            : K.band_set(M->eng[k], level, stride, nrec, s.gs + 1, s.nown(), errm, errm_len);
     }
     if (rc) {                           // all bands or none
-        for (int k = 0; k < M->n; ++k) (void)beom_set_series(M->eng[k], 0, 1, 1, nullptr, 0);
+        for (int k = 0; k < M->n; ++k) (void)K.set(M->eng[k], 0, 1, 1, nullptr, 0);
         return rc;
     }
-    M->ser.level = level; M->ser.stride = stride; M->ser.nrec = nrec;
+    S.level = level; S.stride = stride; S.nrec = nrec;
     return 0;
 }
 
-int beom_multi_download_series(beom_multi_handle M, double *rows, int *tstp, int *count, char *errm, int errm_len) {
+static int multi_download_recorder(beom_multi *M, const SeriesKind &K, double *rows, int *tstp, int *count, char *errm, int errm_len) {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_series: this handle holds a window and keeps no series"); return -6; }
-    if (M->ser.level < 1) { m_err(errm, errm_len, "beom_multi_download_series: the handle keeps no series (beom_multi_set_series)"); return -3; }
+    M_RC(K.refused(M, K.refusal[1], errm, errm_len));
+    beom_multi::Series &S = M->*K.rec;
+    if (S.level < 1) { m_err(errm, errm_len, "%s", K.none); return -3; }
     M_RC(beom_multi_sync(M, errm, errm_len));
-    if (multi_whole(M)) return beom_download_series(M->eng[0], rows, tstp, count, errm, errm_len);
-    const size_t n = M->ser.tstp.size(), cnt = (size_t)beom_series_count(M->P.nlay, M->ser.level), Mg = (size_t)M->P.mm + 1;
+    if (multi_whole(M)) return K.download(M->eng[0], rows, tstp, count, errm, errm_len);
+    const size_t n = S.tstp.size(), cnt = (size_t)K.count(M->ntrc, M->P.nlay, S.level), Mg = (size_t)M->P.mm + 1;
     // (a ring's orphan row mm+1 duplicates row 1: every sum of it is +0, the companion frame is not asked)
     if (rows) std::fill(rows, rows + n * Mg * cnt, 0.0);
     for (int k = 0; k < M->n; ++k) {
@@ -1482,65 +1524,28 @@ int beom_multi_download_series(beom_multi_handle M, double *rows, int *tstp, int
         const size_t per = (size_t)s.nown() * cnt;
         std::vector<double> a(rows ? n * per : 0);
         int held = 0;
-        M_RC(beom_download_series(M->eng[k], rows ? ptr(a) : nullptr, nullptr, &held, errm, errm_len));
-        if ((size_t)held != n) { m_err(errm, errm_len, "beom_multi_download_series: band %d holds %d records, the handle %zu", s.index, held, n); return -3; }
+        M_RC(K.download(M->eng[k], rows ? ptr(a) : nullptr, nullptr, &held, errm, errm_len));
+        if ((size_t)held != n) { m_err(errm, errm_len, K.band_held, s.index, held, n); return -3; }
         for (size_t r = 0; r < n && rows; ++r)
             std::copy(a.begin() + r * per, a.begin() + (r + 1) * per, rows + (r * Mg + (size_t)(s.own0 - 1)) * cnt);
     }
-    if (tstp) std::copy(M->ser.tstp.begin(), M->ser.tstp.end(), tstp);
+    if (tstp) std::copy(S.tstp.begin(), S.tstp.end(), tstp);
     if (count) *count = (int)n;
-    M->ser.tstp.clear();
+    S.tstp.clear();
     return 0;
 }
 
-// Tracer series (beom_tracer_series.h) of a frame cut into bands: the series' placement, the tracers' refusals.
+int beom_multi_set_series(beom_multi_handle M, int level, int stride, int nrec, char *errm, int errm_len) {
+    return multi_set_recorder(M, kSeries, level, stride, nrec, errm, errm_len);
+}
 int beom_multi_set_tracer_series(beom_multi_handle M, int level, int stride, int nrec, char *errm, int errm_len) {
-    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_tracer_series: an earlier step failed half way; destroy the handle"); return -30; }
-    if (level < 0 || level > 3 || (level > 0 && (stride < 1 || nrec < 1))) {
-        m_err(errm, errm_len, "beom_multi_set_tracer_series: level %d, stride %d, %d records (level 0..3, stride >= 1, records >= 1)", level, stride, nrec);
-        return -3;
-    }
-    M_RC(tracers_refused(M, "beom_multi_set_tracer_series", errm, errm_len));
-    if (level > 0 && M->ntrc < 1) { m_err(errm, errm_len, "beom_multi_set_tracer_series: the handle carries no tracer (beom_multi_set_tracers comes first)"); return -3; }
-    M_RC(beom_multi_sync(M, errm, errm_len));
-    M->tser = {};
-    int rc = 0;
-    for (int k = 0; k < M->n && !rc; ++k) {
-        const Band &s = M->band[k];
-        rc = multi_whole(M) ? beom_set_tracer_series(M->eng[k], level, stride, nrec, errm, errm_len)
-                            : beom_band_set_tracer_series(M->eng[k], level, stride, nrec, s.gs + 1, s.nown(), errm, errm_len);
-    }
-    if (rc) {                           // all bands or none
-        for (int k = 0; k < M->n; ++k) (void)beom_set_tracer_series(M->eng[k], 0, 1, 1, nullptr, 0);
-        return rc;
-    }
-    M->tser.level = level; M->tser.stride = stride; M->tser.nrec = nrec;
-    return 0;
+    return multi_set_recorder(M, kTracerSeries, level, stride, nrec, errm, errm_len);
 }
-
+int beom_multi_download_series(beom_multi_handle M, double *rows, int *tstp, int *count, char *errm, int errm_len) {
+    return multi_download_recorder(M, kSeries, rows, tstp, count, errm, errm_len);
+}
 int beom_multi_download_tracer_series(beom_multi_handle M, double *rows, int *tstp, int *count, char *errm, int errm_len) {
-    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    M_RC(tracers_refused(M, "beom_multi_download_tracer_series", errm, errm_len));
-    if (M->tser.level < 1) { m_err(errm, errm_len, "beom_multi_download_tracer_series: the handle keeps no tracer series (beom_multi_set_tracer_series)"); return -3; }
-    M_RC(beom_multi_sync(M, errm, errm_len));
-    if (multi_whole(M)) return beom_download_tracer_series(M->eng[0], rows, tstp, count, errm, errm_len);
-    const size_t n = M->tser.tstp.size(), cnt = (size_t)beom_tracer_series_count(M->ntrc, M->P.nlay, M->tser.level), Mg = (size_t)M->P.mm + 1;
-    if (rows) std::fill(rows, rows + n * Mg * cnt, 0.0);
-    for (int k = 0; k < M->n; ++k) {
-        const Band &s = M->band[k];
-        const size_t per = (size_t)s.nown() * cnt;
-        std::vector<double> a(rows ? n * per : 0);
-        int held = 0;
-        M_RC(beom_download_tracer_series(M->eng[k], rows ? ptr(a) : nullptr, nullptr, &held, errm, errm_len));
-        if ((size_t)held != n) { m_err(errm, errm_len, "beom_multi_download_tracer_series: band %d holds %d records, the handle %zu", s.index, held, n); return -3; }
-        for (size_t r = 0; r < n && rows; ++r)
-            std::copy(a.begin() + r * per, a.begin() + (r + 1) * per, rows + (r * Mg + (size_t)(s.own0 - 1)) * cnt);
-    }
-    if (tstp) std::copy(M->tser.tstp.begin(), M->tser.tstp.end(), tstp);
-    if (count) *count = (int)n;
-    M->tser.tstp.clear();
-    return 0;
+    return multi_download_recorder(M, kTracerSeries, rows, tstp, count, errm, errm_len);
 }
 
 int beom_multi_upload_local(beom_multi_handle M, const beom_state *win, const beom_state *orphan, char *errm, int errm_len) {
@@ -1624,17 +1629,13 @@ static int multi_sample_due(beom_multi *M, char *errm, int errm_len) {
             if (beom_sample_harmonics(M->eng[k], M->harm.due_ctim)) { m_err(errm, errm_len, "beom_sample_harmonics failed on band %d (step %d)", M->band[k].index, M->harm.due); return -3; }
         M->harm.due = 0;
     }
-    if (M->ser.due) {
+    for (const SeriesKind *K : {&kSeries, &kTracerSeries}) {
+        beom_multi::Series &S = M->*K->rec;
+        if (!S.due) continue;
         for (int k = 0; k < M->n; ++k)
-            if (beom_sample_series(M->eng[k])) { m_err(errm, errm_len, "beom_sample_series failed on band %d (step %d)", M->band[k].index, M->ser.due); return -3; }
-        M->ser.tstp.push_back(M->ser.due);
-        M->ser.due = 0;
-    }
-    if (M->tser.due) {
-        for (int k = 0; k < M->n; ++k)
-            if (beom_sample_tracer_series(M->eng[k])) { m_err(errm, errm_len, "beom_sample_tracer_series failed on band %d (step %d)", M->band[k].index, M->tser.due); return -3; }
-        M->tser.tstp.push_back(M->tser.due);
-        M->tser.due = 0;
+            if (K->sample(M->eng[k])) { m_err(errm, errm_len, K->sample_failed, M->band[k].index, S.due); return -3; }
+        S.tstp.push_back(S.due);
+        S.due = 0;
     }
     return 0;
 }
@@ -1782,8 +1783,8 @@ static int multi_one_step(beom_multi *M, int t, double tres, double dtd8, double
     for (beom_multi::Moments *m : {&M->mom, &M->tmom})
         if (m->level > 0 && t % m->stride == 0) m->due = t;
     if (M->harm.level > 0 && t % M->harm.stride == 0) { M->harm.due = t; M->harm.due_ctim = tres + dtd8 * (double)t; }
-    if (M->ser.level > 0 && t % M->ser.stride == 0) M->ser.due = t;
-    if (M->tser.level > 0 && t % M->tser.stride == 0) M->tser.due = t;
+    for (beom_multi::Series *s : {&M->ser, &M->tser})
+        if (s->level > 0 && t % s->stride == 0) s->due = t;
     if (M->nflt > 0) M->flt_mode = 3;
     return 0;
 }
@@ -1797,27 +1798,9 @@ int beom_multi_step(beom_multi_handle M, int tstp_first, int nsteps, double tres
     if (tstp_first < 1 || nsteps < 0 || n_3d < 1) { m_err(errm, errm_len, "beom_multi_step: bad arguments"); return -3; }
     if (M->nb == 1 && !M->ring) return beom_step(M->eng[0], tstp_first, nsteps, tres, dtd8, dt_r, rsta, n_3d, errm, errm_len);
     if (M->nflt > 0 && !M->flt_ready) { m_err(errm, errm_len, "beom_multi_step: the handle's %lld floats have no positions yet (beom_multi_upload_floats)", M->nflt); return -3; }
-    if (M->ser.level > 0) {             // the recorder must hold every record of the call: refused before anything is launched
-        long long due = 0;
-        for (int t = tstp_first; t < tstp_first + nsteps; ++t) due += t % M->ser.stride == 0;
-        const long long held = (long long)M->ser.tstp.size();
-        if (held + due > M->ser.nrec) {
-            m_err(errm, errm_len, "beom_multi_step: steps %d..%d would write %lld records of the series (stride %d) but the recorder holds %lld of %d: "
-                  "empty it with beom_multi_download_series, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
-                  M->ser.stride, held, M->ser.nrec);
-            return -3;
-        }
-    }
-    if (M->tser.level > 0) {
-        long long due = 0;
-        for (int t = tstp_first; t < tstp_first + nsteps; ++t) due += t % M->tser.stride == 0;
-        const long long held = (long long)M->tser.tstp.size();
-        if (held + due > M->tser.nrec) {
-            m_err(errm, errm_len, "beom_multi_step: steps %d..%d would write %lld records of the tracer series (stride %d) but the recorder holds %lld of %d: "
-                  "empty it with beom_multi_download_tracer_series, or take fewer steps per call", tstp_first, tstp_first + nsteps - 1, due,
-                  M->tser.stride, held, M->tser.nrec);
-            return -3;
-        }
+    for (const SeriesKind *K : {&kSeries, &kTracerSeries}) {      // a recorder must hold every record of the call: refused before anything is launched
+        const beom_multi::Series &S = M->*K->rec;
+        if (S.level > 0 && !beom_recorder::holds(tstp_first, nsteps, S.stride, S.tstp.size(), S.nrec, errm, errm_len, K->overflow)) return -3;
     }
     M->flt_mode = (M->nflt > 0 && nsteps > 0) ? 1 : 0;          // stage 1 alone in front of the call's first step
     for (int t = tstp_first; t < tstp_first + nsteps; ++t) {

@@ -24,6 +24,20 @@ def _rc(call):
     return str(ei.value)
 
 
+def _refusal(call, code):
+    """The whole message behind the `error <code>:` tag."""
+    msg = _rc(call)
+    tag = "beom_hip error %d: " % code
+    assert msg.startswith(tag), msg
+    return msg[len(tag):]
+
+
+BAD_ARGS = "%s: level %d, stride %d, %d records (level 0..2, stride >= 1, records >= 1)"
+OVERFLOW = ("%s: steps %d..%d would write %d records of the series (stride %d) but the recorder holds %d of %d: "
+            "empty it with %s, or take fewer steps per call")
+SAMPLE = "beom_sample_series (series set? recorder full?)"
+
+
 def _series_of(e, calls, level, stride=1, records=16):
     e.set_series(level, stride, records)
     t = 1
@@ -131,24 +145,23 @@ def test_division_into_calls_and_stride():
 def test_refusals():
     f = _case("island_ragged_3l")
     e = capi.Engine(f)
-    assert "-3" in _rc(e.download_series)                       # no series yet
-    assert "-3" in _rc(e.sample_series)
+    assert _refusal(e.download_series, -3) == "beom_download_series: the handle keeps no series (beom_set_series)"
+    assert _refusal(e.sample_series, -3) == SAMPLE
     for args in ((3, 1, 4), (-1, 1, 4), (1, 0, 4), (2, 1, 0)):
-        assert "error -3:" in _rc(lambda: e.set_series(*args)), args
+        assert _refusal(lambda: e.set_series(*args), -3) == BAD_ARGS % (("beom_set_series",) + args), args
     assert e.info("series") == 0
     e.step(1, 3)
     e.set_series(2, 1, 4)
     before = e.download(("hlay", "u", "v"))
-    msg = _rc(lambda: e.step(4, 5))
-    assert "error -3:" in msg and "beom_download_series" in msg, msg
+    assert _refusal(lambda: e.step(4, 5), -3) == OVERFLOW % ("beom_step", 4, 8, 5, 1, 0, 4, "beom_download_series")
     after = e.download(("hlay", "u", "v"))
     for k in before:
         assert same_bits(before[k], after[k]), k
     assert e.info("series_records") == 0
     e.step(4, 4)
     assert e.info("series_records") == 4
-    assert "-3" in _rc(e.sample_series)                         # a full recorder
-    assert "error -3:" in _rc(lambda: e.step(8, 1))
+    assert _refusal(e.sample_series, -3) == SAMPLE              # a full recorder
+    assert _refusal(lambda: e.step(8, 1), -3) == OVERFLOW % ("beom_step", 8, 8, 1, 1, 4, 4, "beom_download_series")
     assert e.info("series_records") == 4
     got = e.download_series()
     assert list(got["tstp"]) == [4, 5, 6, 7]
@@ -162,8 +175,9 @@ def test_a_handle_that_holds_one_bands_window_refuses():
     recipe = I.recipe_headline(150, 131, 3)
     fw, _, orphan = slab.build_band(recipe, 1, 0)
     band = capi.BandEngine(fw, recipe.p, 1, 0, device=0, rccl_id=None, orphan=orphan)
-    msg = _rc(lambda: band.set_series(2))
-    assert "error -6:" in msg and len(msg.split("error -6:")[1].strip()) > 20, msg
+    assert _refusal(lambda: band.set_series(2), -6) == (
+        "beom_multi_set_series: a handle that holds one band's window keeps no series (its rows are nowhere assembled); "
+        "use a handle created from the global arrays")
     band.close()
 
 
@@ -226,9 +240,12 @@ def test_bands_give_the_single_handles_records(case, nband):
     # the recorder is empty again, and a call that would overflow it is refused before anything is launched
     assert many.download_series()["count"] == 0
     many.set_series(2, 1, 3)
-    assert "error -3:" in _rc(lambda: many.step(14, 4))
+    assert _refusal(lambda: many.step(14, 4), -3) == OVERFLOW % ("beom_multi_step", 14, 17, 4, 1, 0, 3, "beom_multi_download_series")
     many.step(14, 3)
     assert list(many.download_series()["tstp"]) == [14, 15, 16]
+    # a handle without a series says so, and bad arguments are refused in the bands' own words
+    assert _refusal(plain.download_series, -3) == "beom_multi_download_series: the handle keeps no series (beom_multi_set_series)"
+    assert _refusal(lambda: plain.set_series(3, 1, 4), -3) == BAD_ARGS % ("beom_multi_set_series", 3, 1, 4)
     many.close(); plain.close()
 
 

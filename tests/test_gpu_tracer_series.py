@@ -33,6 +33,24 @@ def _refused(call, code, what):
     assert tag in msg and len(msg.split(tag)[1].strip()) > 20, (what, msg)
 
 
+def _refusal(call, code):
+    """The whole message behind the `error <code>:` tag."""
+    msg = _rc(call)
+    tag = "beom_hip error %d: " % code
+    assert msg.startswith(tag), msg
+    return msg[len(tag):]
+
+
+BAD_ARGS = "%s: level %d, stride %d, %d records (level 0..3, stride >= 1, records >= 1)"
+OVERFLOW = ("%s: steps %d..%d would write %d records of the tracer series (stride %d) but the recorder holds %d of %d: "
+            "empty it with %s, or take fewer steps per call")
+SAMPLE = "beom_sample_tracer_series (tracer series set? recorder full?)"
+NONE = "beom_download_tracer_series: the handle keeps no tracer series (beom_set_tracer_series)"
+NO_TRACER = "beom_set_tracer_series: the handle carries no tracer (beom_set_tracers comes first)"
+RING = "%s: bands of a frame periodic in y do not carry tracers (the ring's companion frame has no q); use a single handle"
+WINDOW = "%s: a handle that holds one band's window does not carry tracers (its exchange is sized at creation)"
+
+
 def _contents(f, ntrc):
     """q, rq, ctrg of ntrc tracers on the frame's own thicknesses: patches of 5 x 4 cells with other values per tracer, the
     lower one negative for every second tracer; a relaxation concentration that varies from cell to cell."""
@@ -320,19 +338,18 @@ def test_division_into_calls_and_stride():
 def test_refusals():
     f = _case("island_ragged_3l")
     e = capi.Engine(f)
-    _refused(lambda: e.set_tracer_series(1), -3, "no tracers on the handle")
-    assert "-3" in _rc(e.download_tracer_series) and "-3" in _rc(e.sample_tracer_series)
+    assert _refusal(lambda: e.set_tracer_series(1), -3) == NO_TRACER
+    assert _refusal(e.download_tracer_series, -3) == NONE and _refusal(e.sample_tracer_series, -3) == SAMPLE
     _with_tracers(e, f, 2)
-    assert "-3" in _rc(e.download_tracer_series)                # no tracer series yet
-    assert "-3" in _rc(e.sample_tracer_series)
+    assert _refusal(e.download_tracer_series, -3) == NONE       # no tracer series yet
+    assert _refusal(e.sample_tracer_series, -3) == SAMPLE
     for args in ((4, 1, 4), (-1, 1, 4), (1, 0, 4), (2, 1, 0)):
-        _refused(lambda: e.set_tracer_series(*args), -3, args)
+        assert _refusal(lambda: e.set_tracer_series(*args), -3) == BAD_ARGS % (("beom_set_tracer_series",) + args), args
     assert e.info("tracer_series") == 0
     e.step(1, 3)
     e.set_tracer_series(3, 1, 4)
     before, qb = e.download(STATE), e.download_tracers()
-    msg = _rc(lambda: e.step(4, 5))
-    assert "error -3:" in msg and "beom_download_tracer_series" in msg, msg
+    assert _refusal(lambda: e.step(4, 5), -3) == OVERFLOW % ("beom_step", 4, 8, 5, 1, 0, 4, "beom_download_tracer_series")
     after, qa = e.download(STATE), e.download_tracers()
     for k in before:
         assert same_bits(before[k], after[k]), k
@@ -340,8 +357,8 @@ def test_refusals():
     assert e.info("tracer_series_records") == 0
     e.step(4, 4)
     assert e.info("tracer_series_records") == 4
-    assert "-3" in _rc(e.sample_tracer_series)                  # a full recorder
-    assert "error -3:" in _rc(lambda: e.step(8, 1))
+    assert _refusal(e.sample_tracer_series, -3) == SAMPLE       # a full recorder
+    assert _refusal(lambda: e.step(8, 1), -3) == OVERFLOW % ("beom_step", 8, 8, 1, 1, 4, 4, "beom_download_tracer_series")
     assert e.info("tracer_series_records") == 4
     assert list(e.download_tracer_series()["tstp"]) == [4, 5, 6, 7]
     e.step(8, 1)                                                # the same step is taken once the recorder is empty
@@ -353,18 +370,18 @@ def test_handles_that_carry_no_tracers_refuse():
     # bands of a frame periodic in y, and a handle that holds one band's window: neither carries tracers
     ring = capi.MultiEngine(_band_frame("jet_xyper_2l"), devices=(0, 0))
     assert ring.describe()["ring"] == 1
-    _refused(lambda: ring.set_tracer_series(1), -6, "a ring")
-    _refused(ring.download_tracer_series, -6, "a ring's download")
+    assert _refusal(lambda: ring.set_tracer_series(1), -6) == RING % "beom_multi_set_tracer_series"
+    assert _refusal(ring.download_tracer_series, -6) == RING % "beom_multi_download_tracer_series"
     ring.close()
     from beom_amd import slab
     recipe = I.recipe_headline(150, 131, 3)
     fw, _, orphan = slab.build_band(recipe, 1, 0)
     band = capi.BandEngine(fw, recipe.p, 1, 0, device=0, rccl_id=None, orphan=orphan)
-    _refused(lambda: band.set_tracer_series(1), -6, "a handle that holds one band's window")
+    assert _refusal(lambda: band.set_tracer_series(1), -6) == WINDOW % "beom_multi_set_tracer_series"
     band.close()
     many = capi.MultiEngine(_band_frame("closed_2l"), devices=(0, 0))
-    _refused(lambda: many.set_tracer_series(1), -3, "bands without tracers")
-    _refused(many.download_tracer_series, -3, "bands: a download before set")
+    assert _refusal(lambda: many.set_tracer_series(1), -3) == NO_TRACER.replace("beom_", "beom_multi_")
+    assert _refusal(many.download_tracer_series, -3) == NONE.replace("beom_", "beom_multi_")
     many.close()
     # variant = 1 and the rigid lid refuse tracers, as before
     from helpers import Golden
@@ -373,7 +390,7 @@ def test_handles_that_carry_no_tracers_refuse():
         g = Golden(name)
         e = capi.Engine(_fields(g), variant=g.variant)
         _refused(lambda: e.set_tracers(1), -6, name)
-        _refused(lambda: e.set_tracer_series(1), -3, (name, "no tracers"))
+        assert _refusal(lambda: e.set_tracer_series(1), -3) == NO_TRACER, name
         e.close()
 
 
@@ -466,8 +483,10 @@ def test_bands_give_the_single_handles_records(case, nband, overlap):
     # the recorder is empty again, and a call that would overflow it is refused before anything is launched
     assert many.download_tracer_series()["count"] == 0
     many.set_tracer_series(3, 1, 3)
-    msg = _rc(lambda: many.step(13, 4))
-    assert "error -3:" in msg and "beom_multi_download_tracer_series" in msg, msg
+    assert _refusal(lambda: many.step(13, 4), -3) == OVERFLOW % ("beom_multi_step", 13, 16, 4, 1, 0, 3, "beom_multi_download_tracer_series")
     many.step(13, 3)
     assert list(many.download_tracer_series()["tstp"]) == [13, 14, 15]
+    # a handle without a tracer series says so, and bad arguments are refused in the bands' own words
+    assert _refusal(plain.download_tracer_series, -3) == NONE.replace("beom_", "beom_multi_")
+    assert _refusal(lambda: plain.set_tracer_series(4, 1, 4), -3) == BAD_ARGS % ("beom_multi_set_tracer_series", 4, 1, 4)
     many.close(); plain.close()

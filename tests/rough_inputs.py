@@ -7,6 +7,11 @@ ocrp = 1, thicknesses on both sides of the outcropping thresholds.  The shared o
 neig and subc stay the case's own.  Every array draws from a generator of its own (seed, name), so `reseed=("h_to",)`
 changes that one input alone: the liveness tests use it.
 
+Tracers: dry_cell_state and rough_tracers feed the tracer sweep of both schemes.  Scheme 1 meets them in
+test_gpu_rough_inputs; scheme 2 (the flux-limited faces) in test_tracers_limited_rough_cpu, which holds the inputs to what
+the staged form needs (dry cells inside interior tiles, every outer-ring read), and in test_gpu_tracers_limited_rough on
+frame 321 x 50, the first with interior tiles, 321 x 83 for the bands of the island and 321 x 51 for the sill's sponge.
+
 Amplitudes (all configurations; dt, dl, hsal the case's own):
   u, v          uniform in +-U at open faces, U = 0.05 m/s, 5 % exact +0 and 5 % exact -0
   h_u, h_v      velocity x face thickness x a factor in [0.8, 1.2] per cell (not what update_u would have stored)
@@ -433,7 +438,13 @@ GATE_CONFIGS = {
 FRAMES = {"130x18": (130, 18), "321x50": (321, 50), "130x99": (130, 99), "4200x9": (4200, 9),
           # for the output records: one tile, 512 cell slots in three workgroups of the scan (the last holds cell ndeg alone);
           # lm + 1 = 193 = 1 mod 64, a row pitch padded by 15
-          "63x7": (63, 7), "192x30": (192, 30)}
+          "63x7": (63, 7), "192x30": (192, 30),
+          # for the bands under tracer scheme 2: on island_ragged_3l every window of 2 and of 3 bands holds an interior tile of
+          # both geometries (on 321 x 50 the ragged corner leaves band 0 of 3 without one)
+          "321x83": (321, 83),
+          # the sill's northern sponge (the last six rows) inside an interior 64 x 8 tile of the flux-limited tracer sweep: a
+          # tile row ends at row 48 of 52 (on 321 x 50 the last interior one ends at row 40 of 51)
+          "321x51": (321, 51)}
 _BASE = {}
 
 

@@ -353,11 +353,13 @@ def _finite_same(a, b):
 
 
 @pytest.mark.parametrize("kind,frame", [("dense", "130x18"), ("embedded", "130x18"), ("table", "130x18"),
-                                        ("dense", "4200x9"), ("embedded", "4200x9"), ("table", "4200x9")])
+                                        ("dense", "4200x9"), ("embedded", "4200x9"), ("table", "4200x9"),
+                                        ("dense", "321x50"), ("embedded", "321x50"), ("table", "321x50")])
 def test_tracer_sweep_on_its_own_with_dry_cells(kind, frame):
     """beom_update_tracers in front of beom_update_h, no dynamics: 8 tracers on a state with empty cells away from coasts
-    and transports beside them, three sweeps against tracers_ref.update fed with the handle's own thicknesses."""
-    config = "island_ragged_3l" if kind == "embedded" else ("closed_leith_3l" if frame == "130x18" else "zero_visc_2l")
+    and transports beside them, three sweeps against tracers_ref.update fed with the handle's own thicknesses.  321 x 50 is
+    the frame with interior waves; scheme 2 on these states: test_gpu_tracers_limited_rough."""
+    config = "island_ragged_3l" if kind == "embedded" else ("zero_visc_2l" if frame == "4200x9" else "closed_leith_3l")
     f = RI.base_fields(config, frame)
     g = RI.dry_cell_state(f, 3)
     e = capi.Engine(g, dense_hint=0 if kind == "table" else 1)

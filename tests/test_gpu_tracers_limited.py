@@ -4,7 +4,11 @@ from the same handle, step by step, on an input that reaches every outcome of th
 test); the same bits from every handle kind (dense or embedded, table path, 2 and 3 bands); the default, switching between the
 schemes, continuation; the per-sweep entry; and a handle without tracers, which the choice of scheme must leave alone.
 Comparisons are helpers.same (every value equal, +-0 alike, all finite) unless stated; the one fixture with a tidal constituent
-is held to the project's 1e-12 relative for its cos term."""
+is held to the project's 1e-12 relative for its cos term.
+
+These are smooth flows from rest with two tracers: no cell-layer inside an interior tile is dry, so the staged body's wet mask
+is 0x1FF throughout.  Rough states with dry cells inside interior tiles, 1, 3 and 8 tracers, 12 layers, hdot and a band's
+edge tiles meet scheme 2 in test_gpu_tracers_limited_rough (inputs held to that by test_tracers_limited_rough_cpu)."""
 import os
 
 import numpy as np

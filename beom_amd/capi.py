@@ -96,7 +96,7 @@ def source_hash() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
-    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_harmonics.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_dense_host.h",
+    for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_harmonics.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_forcing.h", "beom_dense_host.h",
                "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
@@ -280,6 +280,15 @@ def load(path: Optional[str] = None) -> C.CDLL:
             getattr(lib, pre + "download_harmonics").argtypes = [T, dpp, dpp, dpp, dpp, llp, ip, ip, cp, ci]
         for name in HARMONIC_EXPORTS:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_forcing"):         # (likewise: an older build has no forcing in time)
+        ip = C.POINTER(ci)
+        lib.beom_forcing_weight.argtypes = [ci, dpp, cd, cd, ip, ip, dpp]
+        lib.beom_apply_forcing.argtypes = [H, cd, cp, ci]
+        for pre, T in (("beom_", H), ("beom_multi_", MH)):
+            getattr(lib, pre + "set_forcing").argtypes = [T, ci, ci, dpp, cd, dpp, cp, ci]
+            getattr(lib, pre + "download_forcing").argtypes = [T, dpp, dpp, cp, ci]
+        for name in FORCING_EXPORTS:
+            getattr(lib, name).restype = ci
     if hasattr(lib, "beom_set_series"):          # (likewise: an older build has no series)
         ip = C.POINTER(ci)
         lib.beom_series_count.argtypes = [ci, ci]
@@ -342,6 +351,8 @@ SERIES_EXPORTS = ("beom_series_count", "beom_set_series", "beom_sample_series", 
 TRACER_SERIES_EXPORTS = ("beom_tracer_series_count", "beom_set_tracer_series", "beom_sample_tracer_series",
                          "beom_download_tracer_series", "beom_band_set_tracer_series", "beom_multi_set_tracer_series",
                          "beom_multi_download_tracer_series")
+FORCING_EXPORTS = ("beom_forcing_weight", "beom_set_forcing", "beom_apply_forcing", "beom_download_forcing",
+                   "beom_multi_set_forcing", "beom_multi_download_forcing")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
 
 EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "beom_info", "beom_download_diag", "beom_create", "beom_destroy", "beom_set_rigid_lid", "beom_download_pressure",
@@ -365,7 +376,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS + FORCING_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -712,6 +723,55 @@ class _Harmonics(_Handle):
         return derive_harmonics(out)
 
 
+FORCING_FIELDS = {"taus": 1, "hdot": 2}      # BEOM_FORCING_TAUS, BEOM_FORCING_HDOT
+
+
+def forcing_weight(times, period: float, ctim: float):
+    """beom_forcing_weight (host only, no device): the frames (k0, k1) and the weight a of time ctim for a frame set with
+    these times (days) and period (0 = none)."""
+    t = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float64)
+    k0, k1, a = C.c_int(0), C.c_int(0), C.c_double(0.0)
+    rc = load().beom_forcing_weight(int(t.size), _dp(t), float(period), float(ctim), C.byref(k0), C.byref(k1), C.byref(a))
+    if rc != 0:
+        raise BeomError("beom_forcing_weight = %d" % rc)
+    return k0.value, k1.value, a.value
+
+
+class _Forcing(_Handle):
+    """Forcing in time (beom_set_forcing, include/beom_hip.h): frames of taus [nfr, 2, ndeg+1] or hdot [nfr, nlay, ndeg+1]
+    at times in days, interpolated on the device at the top of every step.  Shared by Engine and MultiEngine."""
+
+    def _forcing_shape(self, field):
+        if field not in FORCING_FIELDS:
+            raise BeomError("forcing field %r: one of %s" % (field, sorted(FORCING_FIELDS)))
+        return (2 if field == "taus" else self.p.nlay, self.p.ndeg + 1)
+
+    def set_forcing(self, field: str, times, frames=None, period: float = 0.0):
+        """times=None clears the set: the handle reads the arrays it was created with again.  Between steps only."""
+        shape = self._forcing_shape(field)
+        fn = self._fn("set_forcing")
+        if times is None:
+            self._check(fn(self.h, FORCING_FIELDS[field], 0, None, 0.0, None, self._err, ERRLEN))
+            return
+        t = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float64)
+        fr = np.ascontiguousarray(frames, dtype=np.float64)
+        if fr.shape != (t.size,) + shape:
+            raise BeomError("set_forcing(%s): frames %s, expected %s" % (field, fr.shape, (t.size,) + shape))
+        self._check(fn(self.h, FORCING_FIELDS[field], int(t.size), _dp(t), float(period), _dp(fr), self._err, ERRLEN))
+
+    def apply_forcing(self, ctim: float):
+        """The launches of time ctim alone, as a step would place them (single handles)."""
+        if self._multi:
+            raise BeomError("apply_forcing: a single handle's call (the bands apply their frames inside their steps)")
+        self._check(self.lib.beom_apply_forcing(self.h, float(ctim), self._err, ERRLEN))
+
+    def download_forcing(self) -> dict:
+        """{"taus", "hdot"}: what the next sweep would read, in the caller's storage."""
+        out = {"taus": np.zeros((2, self.p.ndeg + 1)), "hdot": np.zeros((self.p.nlay, self.p.ndeg + 1))}
+        self._check(self._fn("download_forcing")(self.h, _dp(out["taus"]), _dp(out["hdot"]), self._err, ERRLEN))
+        return out
+
+
 TRACER_MOMENT_QUANTITIES = ("q", "c", "fu", "fv")     # content, concentration, upstream face fluxes through the W and S faces
 
 
@@ -843,7 +903,7 @@ class _TracerSeries(_Recorder):
         return out
 
 
-class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics):
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics, _Forcing):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     _prefix = "beom_"
@@ -1100,7 +1160,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics, _Forcing):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""

@@ -28,6 +28,7 @@
 #include "beom_harmonics.h"
 #include "beom_tracer_moments.h"
 #include "beom_tracer_series.h"
+#include "beom_forcing.h"
 #include "beom_dense_host.h"
 #include "beom_plan.h"
 #include "beom_recorder.h"
@@ -160,6 +161,19 @@ struct Recorder {
 };
 static bool recorder_due(const Recorder &R, int tstp) { return R.level > 0 && tstp % R.stride == 0 && (int)R.tstp.size() < R.nrec; }
 
+// A frame set of one field (beom_set_forcing; beom_forcing.h): the frames in the device layout, the buffer the sweeps read
+// (x; xc: the cells-only copy of taus) and the weight of the last launch, which a step with the same weight leaves out.
+struct ForcingSet {
+    int nfr = 0;
+    double period = 0.0;
+    std::vector<double> times;
+    std::vector<double *> frames;
+    double *x = nullptr, *xc = nullptr;
+    int k0 = -1, k1 = -1;
+    double a = 0.0;
+    std::vector<void *> allocs;
+};
+
 struct beom_engine {
     beom_params P;
     int device = 0;
@@ -280,6 +294,12 @@ struct beom_engine {
     // with level, stride and rows of its own
     Recorder tser{&kTracerSeries};
     int tser_batch_opt = 0;            // option "tracer_series_batch": rows per launch (0 = by the bound on the scratch)
+    // forcing in time (beom_set_forcing; beom_forcing.h): frc[0] the wind stress, frc[1] hdot; what beom_create gave, to
+    // return to when a set is cleared; a body force of exactly -0 (it bars the folded stress, see derive_forcing_flags)
+    ForcingSet frc[2];
+    long long frc_launches = 0;        // beom_info "forcing_launches"
+    const double *taus0 = nullptr, *taus_cells0 = nullptr, *hdot0 = nullptr;
+    bool wind0 = false, has_hdot0 = false, bodf_neg0 = false;
     char last_err[512] = {0};
 };
 static int hist_sync(beom_engine *E);
@@ -425,13 +445,33 @@ void fill_view(DevView &d, const beom_params &prm, const beom_statics &st) {
     d.slab = prm.slab_mm > 0 ? 1 : 0;
     d.joff = d.slab ? prm.slab_row0 : 0;
     d.Mg = d.slab ? prm.slab_mm + 1 : d.M;
-    d.has_hdot = any_nonzero(st.hdot, nl * n1h);
     d.has_tide = any_nonzero(st.tide, 6 * n1h);
     d.has_bodf = any_nonzero(st.bodf, 2 * nl);
     d.has_nudg = any_nonzero(st.nudg, 3 * n1h);
     d.has_hto = any_nonzero(st.h_to, n1h);
     d.vel_targets_zero = beom_dense::vel_targets_zero(st.fnud, n1h, nl);
     d.rho_top = prm.rhon[0]; d.rho_bot = prm.rhon[nl - 1];
+}
+
+// The flags that follow from the forcing fields: distribute_stress's three terms, has_stress (uploaded stresses count),
+// has_hdot, and whether the stress may fold into the momentum sweep.  beom_create and beom_set_forcing share it; plan_step
+// reads the result through facts_of.
+void derive_forcing_flags(beom_engine *E, bool wind, bool has_hdot) {
+    const beom_params &prm = E->P;
+    DevView &d = E->d;
+    E->wind = wind;                                                                                                   // :1945
+    E->bot = prm.bdrg > 1.e-7;                                                                                        // :1969
+    E->top = prm.tdrg > 1.e-7;                                                                                        // :1991
+    d.has_wind = E->wind; d.has_bot = E->bot; d.has_top = E->top;
+    const bool terms = E->wind || E->bot || E->top;
+    d.has_stress = terms || E->up_tt || E->up_tb || E->up_tu;
+    d.has_hdot = has_hdot;
+    // (a body force of exactly -0 would make the sign of a skipped +-0 visible)
+    E->fold_static_ok = E->dense && prm.ocrp < 0.5 && !E->lid && terms && !E->bodf_neg0;
+}
+bool any_wind(const double *taus, size_t n) {      // private_mod.f95:1945
+    if (taus) for (size_t i = 0; i < n; ++i) if (std::fabs(taus[i]) > 1.e-7) return true;
+    return false;
 }
 
 // which paths the steps take: fused sweeps, tile geometry, stress terms, stress folded into the momentum sweep
@@ -446,14 +486,11 @@ void choose_paths(beom_engine *E, const beom_dense::Grid &g, const beom_statics 
     E->tile4 = E->dense && (long long)((d.L + 63) / 64) * ((d.M + 7) / 8) <= 5000;
     if (getenv("BEOM_TILE4")) E->tile4 = E->dense && atoi(getenv("BEOM_TILE4")) != 0;      // (A/B switch)
     if (E->lid) E->fuse = E->fuse_uv = false;      // the lid's flux rebuild reads the stored d2hx, d2hy of the last layer
-    if (st.taus) for (size_t i = 0; i < 2 * n1h; ++i) if (std::fabs(st.taus[i]) > 1.e-7) { E->wind = true; break; }   // :1945
-    E->bot = prm.bdrg > 1.e-7;                                                                                        // :1969
-    E->top = prm.tdrg > 1.e-7;                                                                                        // :1991
-    d.has_wind = E->wind; d.has_bot = E->bot; d.has_top = E->top;
-    d.has_stress = E->wind || E->bot || E->top;
-    bool neg0 = false;                         // a body force of exactly -0 would make the sign of a skipped +-0 visible
-    if (st.bodf) for (size_t i = 0; i < 2 * nl; ++i) if (st.bodf[i] == 0.0 && std::signbit(st.bodf[i])) neg0 = true;
-    E->fold_static_ok = E->dense && prm.ocrp < 0.5 && !E->lid && d.has_stress && !neg0;
+    if (st.bodf) for (size_t i = 0; i < 2 * nl; ++i) if (st.bodf[i] == 0.0 && std::signbit(st.bodf[i])) E->bodf_neg0 = true;
+    E->wind0 = any_wind(st.taus, 2 * n1h);
+    E->has_hdot0 = any_nonzero(st.hdot, nl * n1h);
+    E->taus0 = d.taus; E->taus_cells0 = d.taus_cells; E->hdot0 = d.hdot;
+    derive_forcing_flags(E, E->wind0, E->has_hdot0);
 }
 
 // a host table -> a new device array of n >= v.size() elements (the rest zeroed if zero)
@@ -619,7 +656,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs, &E->frc[0].allocs, &E->frc[1].allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -1151,6 +1188,34 @@ static void launch_stress(beom_engine *E) {
     const dim3 g((unsigned)((E->d.ncell + BEOM_BLOCK - 1) / BEOM_BLOCK));
     hipLaunchKernelGGL(k_stress, g, dim3(BEOM_BLOCK), 0, E->stream, E->d, (int)E->wind, (int)E->bot, (int)E->top);
 }
+// forcing in time (beom_forcing.h): one field's frames k0, k1 with weight a -> the buffer(s) the sweeps read
+static void launch_forcing(beom_engine *E, int field, int k0, int k1, double a) {
+    ForcingSet &S = E->frc[field];
+    const DevView &d = E->d;
+    const ForcingView v{d.n1, S.frames[(size_t)k0], S.frames[(size_t)k1], S.x, S.xc};
+    const unsigned outer = field == 0 ? 2u : (unsigned)d.nlay;
+    // pairs need the four arrays aligned alike (they are: all come from alloc_aligned)
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(v.A) & 15;
+    const bool pairs = (reinterpret_cast<uintptr_t>(v.B) & 15) == lo && (reinterpret_cast<uintptr_t>(v.x) & 15) == lo &&
+                       (!v.xc || (reinterpret_cast<uintptr_t>(v.xc) & 15) == lo);
+    const long long work = pairs ? (d.n1 + 1) / 2 : d.n1;
+    const dim3 g((unsigned)std::max<long long>(1, std::min<long long>((work + BEOM_BLOCK - 1) / BEOM_BLOCK, 2048)), outer), b(BEOM_BLOCK);
+    pick([&](auto two, auto pr) { hipLaunchKernelGGL((k_forcing_lerp<two, pr>), g, b, 0, E->stream, v, a); }, field == 0, pairs);
+    S.k0 = k0; S.k1 = k1; S.a = a;
+    ++E->frc_launches;
+}
+// the fields of time ctim: a launch per field that has frames, left out where the buffer holds these bits already
+static void apply_forcing(beom_engine *E, double ctim) {
+    for (int f = 0; f < 2; ++f) {
+        const ForcingSet &S = E->frc[f];
+        if (S.nfr == 0) continue;
+        int k0, k1;
+        double a;
+        beom_forcing::forcing_weight(S.nfr, S.times.data(), S.period, ctim, &k0, &k1, &a);
+        if (k0 == S.k0 && k1 == S.k1 && std::memcmp(&a, &S.a, sizeof a) == 0) continue;
+        launch_forcing(E, f, k0, k1, a);
+    }
+}
 
 extern "C" {
 
@@ -1214,6 +1279,7 @@ static void timed(StepTimer *T, int c, F &&f) {
 
 // The step up to the momentum sweeps: stress, the rebuild of steps 1-3, update_h, Montgomery + Leith.
 static void step_front(beom_engine *E, const StepPlan &p, StepTimer *T) {
+    apply_forcing(E, p.ctim);                                      // taus, hdot of this step's time, where they have frames
     if (p.launch_stress) launch_stress(E);
     if (E->lid) launch_lid_fluxes(E, p.first3);
     else if (p.rebuild) launch_rebuild(E);                         // :2166-2177
@@ -2272,6 +2338,106 @@ int beom_download_harmonics(beom_handle E, double *ref, double *sum, double *gra
 // Replaces index_boundary_points' product (private_mod.f95:1060-1240): the table segm(nseg, 18)
 // of nudged open-boundary segments, Fortran storage.  Activates no_gradient_obc after the
 // momentum sweeps of every step when flag_nudging and mcbc < 0.5 (:2201-2204, 2285-2288).
+// ---- forcing in time (beom_forcing.h) ----
+int beom_forcing_weight(int nfr, const double *times, double period, double ctim, int *k0, int *k1, double *a) {
+    if (nfr < 1 || !times || !k0 || !k1 || !a) return -1;
+    beom_forcing::forcing_weight(nfr, times, period, ctim, k0, k1, a);
+    return 0;
+}
+
+static void forcing_free(ForcingSet &S) {
+    free_list(S.allocs);
+    S = ForcingSet{};
+}
+
+int beom_set_forcing(beom_handle E, int field, int nfr, const double *times, double period, const double *frames,
+                     char *errm, int errm_len) {
+    char msg[256] = {0};
+    // (field, times and period are looked at before the handle; the frames' values need its sizes)
+    if (beom_forcing::check_set("beom_set_forcing", field, nfr, times, period, frames, 0, msg, sizeof msg)) {
+        set_err(errm, errm_len, "%s", msg);
+        return -3;
+    }
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    DevView &d = E->d;
+    const size_t n1h = (size_t)d.ndeg + 1, nl = (size_t)d.nlay;
+    const size_t outer = field == BEOM_FORCING_TAUS ? 2 : nl, count = outer * n1h;
+    if (beom_forcing::check_set("beom_set_forcing", field, nfr, times, period, frames, count, msg, sizeof msg)) {
+        set_err(errm, errm_len, "%s", msg);
+        return -3;
+    }
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    const int f = field - 1;
+    const bool had_wind = E->wind;
+    ForcingSet &S = E->frc[f];
+    forcing_free(S);
+    // back to what beom_create gave; a new set then takes its place
+    if (f == 0) { d.taus = E->taus0; d.taus_cells = E->taus_cells0; }
+    else d.hdot = E->hdot0;
+    int rc = 0;
+    if (nfr > 0) {
+        const size_t n = outer * (size_t)d.n1;
+        rc = alloc_aligned(E, S.allocs, &S.x, n, errm, errm_len);
+        if (!rc && f == 0) rc = alloc_aligned(E, S.allocs, &S.xc, n, errm, errm_len);
+        S.frames.assign((size_t)nfr, nullptr);
+        std::vector<double> img(n1h);
+        for (int k = 0; k < nfr && !rc; ++k) {
+            rc = alloc_aligned(E, S.allocs, &S.frames[(size_t)k], n, errm, errm_len);
+            for (size_t o = 0; o < outer && !rc; ++o) {
+                const double *src = frames + ((size_t)k * outer + o) * n1h;
+                double *dst = S.frames[(size_t)k] + o * (size_t)d.n1;
+                if (f == 0) {
+                    // the wind stress as the cells-only copy wants it: +0 in every slot that is no cell; the sentinel's own
+                    // value goes to slot 0 alone, which the launch writes to d.taus only
+                    std::memcpy(img.data(), src, n1h * sizeof(double));
+                    img[0] = 0.0;
+                    rc = slice_to_device<double>(E, dst, img.data(), 1, 1, 0, errm, errm_len);
+                    if (!rc) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double), hipMemcpyHostToDevice, E->stream));
+                } else {
+                    rc = slice_to_device<double>(E, dst, src, 1, 1, 0, errm, errm_len);
+                }
+                if (!rc) HIP_TRY(hipStreamSynchronize(E->stream));      // (img and the staging image are used again)
+            }
+        }
+        if (rc) forcing_free(S);
+    }
+    if (S.x) {
+        S.nfr = nfr; S.period = period; S.times.assign(times, times + nfr);
+        if (f == 0) { d.taus = S.x; d.taus_cells = S.xc; }
+        else d.hdot = S.x;
+        launch_forcing(E, f, 0, 0, 0.0);           // the buffers are defined from here on: the first frame
+    }
+    // the flags of the frames in force, or of the arrays of beom_create
+    const ForcingSet &T = E->frc[0], &H = E->frc[1];
+    const bool wind = T.nfr ? (f == 0 ? any_wind(frames, (size_t)nfr * count) : E->wind) : E->wind0;
+    const bool has_hdot = H.nfr ? (f == 1 ? any_nonzero(frames, (size_t)nfr * count) : d.has_hdot != 0) : E->has_hdot0;
+    derive_forcing_flags(E, wind, has_hdot);
+    // a wind that is gone leaves nothing behind in tt3d (distribute_stress would never have written it)
+    if (had_wind && !E->wind && !E->up_tt) HIP_TRY(hipMemsetAsync(d.tt3d, 0, 2 * nl * (size_t)d.n1 * sizeof(double), E->stream));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipGetLastError());
+    return rc;
+}
+
+int beom_apply_forcing(beom_handle E, double ctim, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    HIP_TRY(hipSetDevice(E->device));
+    apply_forcing(E, ctim);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int beom_download_forcing(beom_handle E, double *taus, double *hdot, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    HIP_TRY(hipSetDevice(E->device));
+    int rc;
+    if ((rc = copy_out(E, taus, E->d.taus, 2, errm, errm_len))) return rc;
+    if ((rc = copy_out(E, hdot, E->d.hdot, (size_t)E->d.nlay, errm, errm_len))) return rc;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int beom_set_open_boundaries(beom_handle E, int nseg, const int32_t *segm, char *errm, int errm_len) {
     if (!E || nseg < 0 || (nseg > 0 && !segm)) { set_err(errm, errm_len, "beom_set_open_boundaries: bad arguments"); return -1; }
     HIP_TRY(hipSetDevice(E->device));
@@ -2355,6 +2521,9 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "harmonic_level")) return E->harm.acc.level;
     if (!strcmp(what, "harmonic_samples")) return (int)std::min<long long>(E->harm.acc.count, 2000000000ll);
     if (!strcmp(what, "harmonic_launches")) return (int)std::min<long long>(E->harm.acc.launches, 2000000000ll);     // all calls so far
+    if (!strcmp(what, "forcing_taus_frames")) return E->frc[0].nfr;
+    if (!strcmp(what, "forcing_hdot_frames")) return E->frc[1].nfr;
+    if (!strcmp(what, "forcing_launches")) return (int)std::min<long long>(E->frc_launches, 2000000000ll);          // all so far
     if (!strcmp(what, "moments")) return E->mom.level;
     if (!strcmp(what, "moment_samples")) return (int)std::min<long long>(E->mom.count, 2000000000ll);
     if (!strcmp(what, "moment_launches")) return (int)std::min<long long>(E->mom.launches, 2000000000ll);     // all calls so far

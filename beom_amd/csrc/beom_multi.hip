@@ -40,6 +40,7 @@
 #include "beom_bands_host.h"
 #include "beom_dense_host.h"
 #include "beom_recorder.h"
+#include "beom_forcing.h"
 
 using namespace beom_bands;
 
@@ -1307,6 +1308,53 @@ int beom_multi_download_harmonics(beom_multi_handle M, double *ref, double *sum,
         const bool lead = p.k == 0;          // gram, omega, count and the steps are band 0's
         M_RC(beom_download_harmonics(p.eng, ptr(a[0]), ptr(a[1]), lead ? gram : nullptr, lead ? omega : nullptr, lead ? count : nullptr,
                                      lead ? tstp_first : nullptr, lead ? tstp_last : nullptr, errm, errm_len));
+        for (int f = 0; f < 2; ++f) copy_rows(dst[f], ptr(a[f]), outer[f], 1, p.out);
+    }
+    return 0;
+}
+
+// ---- forcing in time (beom_set_forcing) on the bands: every frame is cut into the windows as beom_multi_create cuts taus
+//      and hdot, the companion frame of a ring included; each band interpolates its own window at the top of its step ----
+int beom_multi_set_forcing(beom_multi_handle M, int field, int nfr, const double *times, double period, const double *frames,
+                           char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->failed) { m_err(errm, errm_len, "beom_multi_set_forcing: an earlier step failed half way; destroy the handle"); return -30; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_set_forcing: a handle that holds one band's window does not take frames (its global arrays are nowhere assembled); use a handle created from the global arrays"); return -6; }
+    const int nl = M->P.nlay;
+    const Shape shape = kStatic[field == BEOM_FORCING_TAUS ? 7 : 5];
+    const size_t outer = shape.outer(nl), count = outer * M->n1g;
+    char msg[256] = {0};
+    if (beom_forcing::check_set("beom_multi_set_forcing", field, nfr, times, period, frames, count, msg, sizeof msg)) {
+        m_err(errm, errm_len, "%s", msg);
+        return -3;
+    }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (multi_whole(M)) return beom_set_forcing(M->eng[0], field, nfr, times, period, frames, errm, errm_len);
+    int rc = 0;
+    for (const Part &p : parts(M)) {
+        std::vector<double> win;               // [nfr][outer][the part's slots]
+        for (int k = 0; k < nfr; ++k) {
+            const std::vector<double> one = cut_rows(frames + (size_t)k * count, outer, shape.inner, p.in);
+            win.insert(win.end(), one.begin(), one.end());
+        }
+        if ((rc = beom_set_forcing(p.eng, field, nfr, times, period, ptr(win), errm, errm_len))) break;
+    }
+    if (rc)                                    // (an allocation failed: no band keeps the set)
+        for (const Part &p : parts(M)) (void)beom_set_forcing(p.eng, field, 0, nullptr, 0.0, nullptr, nullptr, 0);
+    return rc;
+}
+
+int beom_multi_download_forcing(beom_multi_handle M, double *taus, double *hdot, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    if (M->local_mode) { m_err(errm, errm_len, "beom_multi_download_forcing: this handle holds a window and takes no frames"); return -6; }
+    M_RC(beom_multi_sync(M, errm, errm_len));
+    if (multi_whole(M)) return beom_download_forcing(M->eng[0], taus, hdot, errm, errm_len);
+    double *dst[2] = {taus, hdot};
+    const size_t outer[2] = {kStatic[7].outer(M->P.nlay), kStatic[5].outer(M->P.nlay)};
+    for (const Part &p : parts(M)) {
+        std::vector<double> a[2];
+        for (int f = 0; f < 2; ++f) if (dst[f]) a[f].assign(outer[f] * p.n1(), 0.0);
+        M_RC(beom_download_forcing(p.eng, ptr(a[0]), ptr(a[1]), errm, errm_len));
         for (int f = 0; f < 2; ++f) copy_rows(dst[f], ptr(a[f]), outer[f], 1, p.out);
     }
     return 0;

@@ -521,6 +521,57 @@ int beom_sample_harmonics(beom_handle h, double ctim);
 int beom_download_harmonics(beom_handle h, double *ref, double *sum, double *gram, double *omega, long long *count,
                             int *tstp_first, int *tstp_last, char *errm, int errm_len);
 
+/* ---- Forcing in time: the wind stress taus(0:ndeg, 2) and the thickness source hdot(0:ndeg, nlay) interpolated between
+ * frames at the top of every time step, on the device (no reference routine; DESIGN.md §4 "Forcing in time";
+ * tests/forcing_ref.py is this rule in numpy).
+ * A FRAME SET belongs to one field.  It has nfr >= 1 frames in the field's Fortran storage, frames[k][...] one behind the
+ * other, and times[nfr] in days on the clock of ctim = tres + dtd8*(double)tstp, strictly increasing and finite.  period is
+ * 0 (none) or greater than times[nfr-1] - times[0] (the set repeats with that period).
+ * The WEIGHT of a time is formed on the host.  beom_forcing_weight returns exactly it (host only, no device, as
+ * beom_harmonic_weights); FP64, every operation rounded once, written as here:
+ *   nfr == 1:                                  (k0, k1, a) = (0, 0, 0)
+ *   period == 0:  t = ctim
+ *       t <  times[0]                          (0, 0, 0)
+ *       t >= times[nfr-1]                      (nfr-1, nfr-1, 0)
+ *       else  k0 = the largest k with times[k] <= t;  k1 = k0 + 1;  a = (t - times[k0]) / (times[k1] - times[k0])
+ *   period > 0:   r = fmod(ctim - times[0], period);  if (r < 0) r += period;  t = times[0] + r
+ *       t >= times[nfr-1]                      k0 = nfr-1;  k1 = 0;  a = (t - times[nfr-1]) / ((times[0] + period) - times[nfr-1])
+ *       else  as for period == 0
+ * The FIELD, per element, with A, B the values of frames k0, k1 (FP64, no contraction):
+ *   d = B - A;    x = (a == 0 || d == 0) ? A : A + a*d
+ * The select is deliberate: where two frames agree the result is the frame bit for bit, a -0 included, and at a = 0 it is
+ * the frame itself; so a set of equal frames steps exactly as a handle created with that array.  (1-a)*A + a*B does not
+ * have this property.
+ * WHERE it acts: at the top of every time step, in front of the stress, the tracer launches and update_h — steps 1-3, every
+ * step of a K-step beom_step call, and phase 1 of beom_step_phase.  From there the arrays the step reads hold the field at
+ * that step's ctim: for taus the array distribute_stress reads and the cells-only copy the folded momentum sweep reads
+ * (+0 at the sentinel and in every slot that is no cell); for hdot the array update_h and the tracer sweeps read.  The
+ * launch (k_forcing_lerp, beom_forcing.h) is purely elementwise over frames kept in the device layout: 2 words read and
+ * 2 (taus) | 1 (hdot) written per element.  It is left out where the array already holds these bits: the same (k0, k1, a)
+ * as the field's last launch.  beom_info "forcing_launches" counts what ran.
+ * FLAGS: the handle's wind follows private_mod.f95:1945 applied to the frames (any |element| of any frame > 1e-7), hdot is
+ * live if any element of any frame is non-zero; the stress terms, has_stress and the folded stress are re-derived whenever a
+ * set is given or cleared, so a handle created without taus or hdot gains the term, and "stress_folded" stays 1 while the
+ * frames vary.  (The reference decides wind from the array of the moment: a step whose interpolated taus has nothing above
+ * 1e-7 while a frame has differs from a host that replaces the array.)
+ * beom_set_forcing(h, field, nfr, times, period, frames): field = BEOM_FORCING_TAUS | BEOM_FORCING_HDOT; between any two
+ * steps; the frames are copied.  It launches the first frame into the field's buffers, so a download is defined at once.
+ * nfr = 0 clears the set: the handle reads the arrays of beom_create again and steps as before.  Refused with -3 and a
+ * message that names the fault, nothing touched: an unknown field, times that are not finite or not strictly increasing, a
+ * period that is negative, not finite or not greater than the span of the times, a frame value that is not finite.  (Field,
+ * times and period are looked at before the handle, the frames' values with its sizes.)
+ * beom_apply_forcing(h, ctim): the launches of time ctim alone, as a step would place them.
+ * beom_download_forcing(h, taus, hdot): what the next sweep would read, in Fortran storage; either pointer may be NULL;
+ * without a frame set, the array of beom_create (zeros if that was NULL).
+ * beom_info: "forcing_taus_frames", "forcing_hdot_frames" (nfr; 0 = none), "forcing_launches" (so far). */
+#define BEOM_FORCING_TAUS 1
+#define BEOM_FORCING_HDOT 2
+int beom_forcing_weight(int nfr, const double *times, double period, double ctim, int *k0, int *k1, double *a);
+int beom_set_forcing(beom_handle h, int field, int nfr, const double *times, double period, const double *frames,
+                     char *errm, int errm_len);
+int beom_apply_forcing(beom_handle h, double ctim, char *errm, int errm_len);
+int beom_download_forcing(beom_handle h, double *taus, double *hdot, char *errm, int errm_len);
+
 /* ---- Tracer moments: time means of a tracer's content, concentration and face fluxes and the variance of its concentration,
  * accumulated on the device (no reference routine; DESIGN.md f-N9).  With t the tracer, l the layer, p a real cell and
  * W, S = neig(5|7, p), c(x) is trc_conc of beom_tracers.h, c(x) = hlay(x,l) > 0 ? q(x,l,t)/hlay(x,l) : +0.0, and four
@@ -840,6 +891,17 @@ int beom_multi_set_harmonics(beom_multi_handle m, int nfreq, const double *omega
 int beom_multi_reset_harmonics(beom_multi_handle m, char *errm, int errm_len);
 int beom_multi_download_harmonics(beom_multi_handle m, double *ref, double *sum, double *gram, double *omega, long long *count,
                                   int *tstp_first, int *tstp_last, char *errm, int errm_len);
+
+/* Forcing in time on a frame cut into bands (see beom_set_forcing): GLOBAL frames, handles created from the global arrays
+ * (beom_multi_create[_ex]), chains with and without land, and rings.  Every frame is cut into the bands' windows exactly as
+ * beom_multi_create cuts taus and hdot; a ring's companion frame gets its rows the same way.  Each band interpolates its own
+ * window, ghost rows included, at the top of its step (phase 1 of a cut step), so cut steps stay cut, beom_multi_stats is
+ * what it is for a steady handle, and the bits are a single handle's.  The arguments are checked on the global arrays
+ * before any band is touched (-3).  beom_multi_download_forcing assembles the bands' OWNED rows.  Refused with -6: handles
+ * that hold one band's window (beom_multi_create_local*). */
+int beom_multi_set_forcing(beom_multi_handle m, int field, int nfr, const double *times, double period, const double *frames,
+                           char *errm, int errm_len);
+int beom_multi_download_forcing(beom_multi_handle m, double *taus, double *hdot, char *errm, int errm_len);
 
 /* Tracer moments on a frame cut into bands (see beom_set_tracer_moments): GLOBAL arrays assembled from every band's OWNED
  * rows; the bits are a single handle's.  Every band samples over its whole window where the bands' field moments are sampled:

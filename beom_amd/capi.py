@@ -97,7 +97,7 @@ def source_hash() -> str:
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
     for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_harmonics.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_forcing.h", "beom_dense_host.h",
-               "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", os.path.join("..", "..", "include", "beom_hip.h")):
+               "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", "beom_column_series.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -300,6 +300,15 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.beom_multi_download_series.argtypes = [MH, dpp, ip, ip, cp, ci]
         for name in SERIES_EXPORTS:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_column_series"):   # (likewise: an older build has no column series)
+        ip = C.POINTER(ci)
+        lib.beom_set_column_series.argtypes = [H, ci, ci, ci, ci, ci, cp, ci]
+        lib.beom_sample_column_series.argtypes = [H]
+        lib.beom_download_column_series.argtypes = [H, dpp, ip, ip, cp, ci]
+        lib.beom_multi_set_column_series.argtypes = [MH, ci, ci, ci, ci, ci, cp, ci]
+        lib.beom_multi_download_column_series.argtypes = [MH, dpp, ip, ip, cp, ci]
+        for name in COLUMN_SERIES_EXPORTS:
+            getattr(lib, name).restype = ci
     if hasattr(lib, "beom_set_tracer_series"):   # (likewise: an older build has no tracer series)
         ip = C.POINTER(ci)
         lib.beom_tracer_series_count.argtypes = [ci, ci, ci]
@@ -351,6 +360,8 @@ SERIES_EXPORTS = ("beom_series_count", "beom_set_series", "beom_sample_series", 
 TRACER_SERIES_EXPORTS = ("beom_tracer_series_count", "beom_set_tracer_series", "beom_sample_tracer_series",
                          "beom_download_tracer_series", "beom_band_set_tracer_series", "beom_multi_set_tracer_series",
                          "beom_multi_download_tracer_series")
+COLUMN_SERIES_EXPORTS = ("beom_set_column_series", "beom_sample_column_series", "beom_download_column_series",
+                         "beom_multi_set_column_series", "beom_multi_download_column_series")
 FORCING_EXPORTS = ("beom_forcing_weight", "beom_set_forcing", "beom_apply_forcing", "beom_download_forcing",
                    "beom_multi_set_forcing", "beom_multi_download_forcing")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
@@ -376,7 +387,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS + FORCING_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS + FORCING_EXPORTS + COLUMN_SERIES_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -802,21 +813,21 @@ class _TracerMoments(_Accum):
 
 
 class _Recorder(_Handle):
-    """What _Series and _TracerSeries share: a device-side recorder [records][M][cnt] set and downloaded through the exports
+    """What _Series, _TracerSeries and _ColumnSeries share: a device-side recorder [records][lines][cnt] set and downloaded through the exports
     beom_[multi_]{set,download}_<stem>, and sampled by hand on a single handle (beom_sample_<stem>)."""
 
-    def _recorder_set(self, stem, level, stride, records):
-        """-> the level and the record count to keep (0 records once freed)."""
-        self._check(self._fn("set_" + stem)(self.h, int(level), int(stride), int(records), self._err, ERRLEN))
+    def _recorder_set(self, stem, level, stride, records, *window):
+        """-> the level and the record count to keep (0 records once freed).  window: the column series' jlo, jhi."""
+        self._check(self._fn("set_" + stem)(self.h, int(level), int(stride), int(records), *window, self._err, ERRLEN))
         return int(level), (int(records) if level else 0)
 
-    def _recorder_download(self, stem, what, level, records, cnt_of):
-        """The records held, oldest first: (n, tstp[n], rows[n, M, cnt_of(level)]); empties the recorder."""
+    def _recorder_download(self, stem, what, level, records, cnt_of, lines):
+        """The records held, oldest first: (n, tstp[n], rows[n, lines, cnt_of(level)]); empties the recorder."""
         fn = self._fn("download_" + stem)
         if level < 1:                                                    # (the library says why)
             self._check(fn(self.h, None, None, None, self._err, ERRLEN))
             raise BeomError("download_%s: the handle keeps no %s (set_%s)" % (stem, what, stem))
-        rows = np.zeros((max(records, 1), self.p.mm + 1, cnt_of(level)))
+        rows = np.zeros((max(records, 1), lines, cnt_of(level)))
         tstp = (C.c_int * max(records, 1))()
         count = C.c_int(0)
         self._check(fn(self.h, _dp(rows), tstp, C.byref(count), self._err, ERRLEN))
@@ -850,7 +861,7 @@ class _Series(_Recorder):
         the volume transport (m^3/s) above the base of layer l through the south faces of row j."""
         nl, M = self.p.nlay, self.p.mm + 1
         n, tstp, rows = self._recorder_download("series", "series", self.series_level, self.series_records,
-                                                lambda lv: self.lib.beom_series_count(nl, lv))
+                                                lambda lv: self.lib.beom_series_count(nl, lv), M)
         q = rows[:, :, :4 * nl].reshape(n, M, nl, 4)
         out = {"count": n, "tstp": tstp, "rows": rows,
                "raw": np.array([combine_integral_rows(r[:, :4 * nl + 1]) for r in rows]).reshape(n, 4 * nl + 1),
@@ -860,6 +871,45 @@ class _Series(_Recorder):
         if self.series_level >= 2:
             out["tu"], out["tv"] = rows[:, :, 4 * nl + 1:5 * nl + 1], rows[:, :, 5 * nl + 1:6 * nl + 1]
             out["psi"] = float(self.p.dl) * np.cumsum(out["tv"], axis=2)
+        return out
+
+
+class _ColumnSeries(_Recorder):
+    """A record of the sums along columns per sampled step, kept on the device (beom_set_column_series, include/beom_hip.h):
+    the series' quantities for every column of the frame — at level 2 the layer transports through a column's W faces —
+    with a level, stride, row window and recorder of its own.  Engine keeps one; MultiEngine refuses (a column's tree
+    crosses the bands)."""
+
+    column_series_level = 0
+    column_series_records = 0
+
+    def set_column_series(self, level: int, stride: int = 1, records: int = 64, rows=None):
+        """level 1: vol, ke, ens, circ per layer and eta2 per column; 2: and tu, tv per layer; 0 frees.  `records`: what the
+        recorder holds between two download_column_series (a step call that would overflow it is refused).  rows = (jlo,
+        jhi): only these rows of a column count (a strait that spans part of it); None = all, 1..mm+1.  Between steps only."""
+        jlo, jhi = (1, self.p.mm + 1) if rows is None else rows
+        self.column_series_level, self.column_series_records = self._recorder_set("column_series", level, stride, records,
+                                                                                  int(jlo), int(jhi))
+
+    def download_column_series(self) -> dict:
+        """The records held, oldest first, and empties the recorder.  count, tstp[n]; cols[n, L, cnt] (L = lm+1 columns);
+        the views vol, ke, ens, circ [n, L, nlay] and eta2 [n, L]; at level 2 tu, tv [n, L, nlay], the column sums of the
+        stored transports h_u, h_v, and phi[n, L, nlay] = dl * cumsum(tu, layers): the volume transport (m^3/s) above the
+        base of layer l through the W faces of column i.  total[n, 4*nlay+1] = the integrals' tree over the columns of each
+        record: close to integrals()["raw"] but NOT its bits — the integrals add along rows first, this adds along columns
+        first (both pairwise trees over the same terms)."""
+        nl, L = self.p.nlay, self.p.lm + 1
+        n, tstp, cols = self._recorder_download("column_series", "column series", self.column_series_level,
+                                                self.column_series_records, lambda lv: self.lib.beom_series_count(nl, lv), L)
+        q = cols[:, :, :4 * nl].reshape(n, L, nl, 4)
+        out = {"count": n, "tstp": tstp, "cols": cols,
+               "total": np.array([combine_integral_rows(c[:, :4 * nl + 1]) for c in cols]).reshape(n, 4 * nl + 1),
+               "eta2": cols[:, :, 4 * nl]}
+        for k, name in enumerate(INTEGRAL_NAMES):
+            out[name] = q[..., k]
+        if self.column_series_level >= 2:
+            out["tu"], out["tv"] = cols[:, :, 4 * nl + 1:5 * nl + 1], cols[:, :, 5 * nl + 1:6 * nl + 1]
+            out["phi"] = float(self.p.dl) * np.cumsum(out["tu"], axis=2)
         return out
 
 
@@ -889,7 +939,7 @@ class _TracerSeries(_Recorder):
         nl, M = self.p.nlay, self.p.mm + 1
         lv = self.info("tracer_series")                                  # (set_tracers with another count frees it)
         n, tstp, rows = self._recorder_download("tracer_series", "tracer series", lv, self.tracer_series_records,
-                                                lambda lv: self.lib.beom_tracer_series_count(self.ntrc, nl, lv))
+                                                lambda lv: self.lib.beom_tracer_series_count(self.ntrc, nl, lv), M)
         self.tracer_series_level = lv
         nq = 2 * lv
         q = rows.reshape(n, M, self.ntrc, nl, nq)
@@ -903,7 +953,7 @@ class _TracerSeries(_Recorder):
         return out
 
 
-class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics, _Forcing):
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _Harmonics, _Forcing):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     _prefix = "beom_"
@@ -1076,7 +1126,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
         "tracer_moment_launches", "harmonics" (the frequencies fitted), "harmonic_level", "harmonic_samples",
         "harmonic_launches" (one per field and sample), "series" (the series' level), "series_records" (records its recorder holds), "tracer_series" (the tracer series' level),
-        "tracer_series_records"."""
+        "tracer_series_records", "column_series" (the column series' level), "column_series_records"."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))
@@ -1151,6 +1201,10 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         """Per-sweep entry: one record of the fields as they stand, under the last step's number, whatever the stride."""
         self._recorder_sample("series", "series")
 
+    def sample_column_series(self):
+        """One record of the column series by hand, of the fields as they stand, under the last step's number."""
+        self._recorder_sample("column_series", "column series")
+
     def sample_tracer_series(self):
         """Per-sweep entry: one record of the tracers and the state as they stand, under the last step's number, whatever the
         stride."""
@@ -1160,7 +1214,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _Harmonics, _Forcing):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _Harmonics, _Forcing):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""

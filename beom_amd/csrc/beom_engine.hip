@@ -32,6 +32,7 @@
 #include "beom_dense_host.h"
 #include "beom_plan.h"
 #include "beom_recorder.h"
+#include "beom_column_series.h"      // (last: the kernels before it keep their place in the code object)
 
 using beom_plan::StepFacts;
 using beom_plan::StepPlan;
@@ -133,11 +134,14 @@ struct RecorderKind {
     int (*scratch)(beom_engine *, Recorder &, int cnt, int nrows, char *errm, int errm_len);
     void (*launch)(beom_engine *, int tstp);
     const char *no_tracer, *none, *overflow;
+    bool columns = false;              // the recorder's lines are the L columns, and jlo .. jlo+nrows-1 is its row window
 };
 static int series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
 static int tracer_series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
 static void launch_series(beom_engine *E, int tstp);
 static void launch_tracer_series(beom_engine *E, int tstp);
+static int column_series_scratch(beom_engine *E, Recorder &R, int cnt, int ncols, char *errm, int errm_len);
+static void launch_column_series(beom_engine *E, int tstp);
 constexpr RecorderKind kSeries{2, [](int, int nlay, int level) { return beom_series_count(nlay, level); },
     series_scratch, launch_series, nullptr,
     "beom_download_series: the handle keeps no series (beom_set_series)",
@@ -149,6 +153,11 @@ constexpr RecorderKind kTracerSeries{3, beom_tracer_series_count,
     "beom_download_tracer_series: the handle keeps no tracer series (beom_set_tracer_series)",
     "beom_step: steps %d..%d would write %lld records of the tracer series (stride %d) but the recorder holds %lld of %d: "
     "empty it with beom_download_tracer_series, or take fewer steps per call"};
+constexpr RecorderKind kColumnSeries{2, [](int, int nlay, int level) { return beom_series_count(nlay, level); },
+    column_series_scratch, launch_column_series, nullptr,
+    "beom_download_column_series: the handle keeps no column series (beom_set_column_series)",
+    "beom_step: steps %d..%d would write %lld records of the column series (stride %d) but the recorder holds %lld of %d: "
+    "empty it with beom_download_column_series, or take fewer steps per call", true};
 struct Recorder {
     const RecorderKind *kind;
     int level = 0, stride = 1, nrec = 0, jlo = 1, rows = 0;      // local rows jlo .. jlo+rows-1
@@ -156,7 +165,8 @@ struct Recorder {
     double *rec = nullptr;
     std::vector<int> tstp;             // the step of every held record (its size = the records held)
     double *part = nullptr;            // the tracer series: the chunk partials of `batch` rows at a time (kTracerSeriesScratch)
-    int batch = 0;
+    int batch = 0;                     // (the column series: the block partials of `batch` 64-column chunks at a time)
+    int wlo = 1, whi = 0;              // the column series: the row window
     std::vector<void *> allocs;
 };
 static bool recorder_due(const Recorder &R, int tstp) { return R.level > 0 && tstp % R.stride == 0 && (int)R.tstp.size() < R.nrec; }
@@ -294,6 +304,10 @@ struct beom_engine {
     // with level, stride and rows of its own
     Recorder tser{&kTracerSeries};
     int tser_batch_opt = 0;            // option "tracer_series_batch": rows per launch (0 = by the bound on the scratch)
+    // column series (beom_set_column_series; beom_column_series.h): a recorder [nrec][L][cnt] whose lines are the columns, with
+    // level, stride, row window and scratch of its own
+    Recorder cser{&kColumnSeries};
+    int cser_batch_opt = 0;            // option "column_series_batch": 64-column chunks per launch (0 = by the bound on the scratch)
     // forcing in time (beom_set_forcing; beom_forcing.h): frc[0] the wind stress, frc[1] hdot; what beom_create gave, to
     // return to when a set is cleared; a body force of exactly -0 (it bars the folded stress, see derive_forcing_flags)
     ForcingSet frc[2];
@@ -656,7 +670,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs, &E->frc[0].allocs, &E->frc[1].allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs, &E->cser.allocs, &E->frc[0].allocs, &E->frc[1].allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -1325,7 +1339,7 @@ static void one_step(beom_engine *E, const StepPlan &p, int flt = -1) {
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->harm.acc, tstp)) launch_harmonics(E, tstp, p.ctim);
-    for (const Recorder *R : {&E->ser, &E->tser})
+    for (const Recorder *R : {&E->ser, &E->tser, &E->cser})
         if (!R->by_caller && recorder_due(*R, tstp)) R->kind->launch(E, tstp);
 }
 
@@ -1361,7 +1375,7 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
         !beom_recorder::holds(tstp_first, nsteps, E->flt_stride, E->flt_rec_tstp.size(), E->flt_nrec, errm, errm_len,
                               "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
                               "empty it with beom_download_float_track, or take fewer steps per call")) return -3;
-    for (const Recorder *R : {&E->ser, &E->tser})
+    for (const Recorder *R : {&E->ser, &E->tser, &E->cser})
         if (R->level > 0 && !R->by_caller &&
             !beom_recorder::holds(tstp_first, nsteps, R->stride, R->tstp.size(), R->nrec, errm, errm_len, R->kind->overflow)) return -3;
     HIP_TRY(hipSetDevice(E->device));
@@ -1676,7 +1690,7 @@ static int tracer_series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows
 
 static void recorder_free(Recorder &R) {
     free_list(R.allocs);
-    R.level = 0; R.stride = 1; R.nrec = 0; R.jlo = 1; R.rows = 0; R.batch = 0; R.by_caller = false;
+    R.level = 0; R.stride = 1; R.nrec = 0; R.jlo = 1; R.rows = 0; R.batch = 0; R.by_caller = false; R.wlo = 1; R.whi = 0;
     R.rec = R.part = nullptr;
     R.tstp.clear();
 }
@@ -1694,16 +1708,22 @@ static int recorder_set(beom_engine *E, Recorder beom_engine::*which, const char
     if (K.no_tracer && level > 0 && E->ntrc < 1) { set_err(errm, errm_len, K.no_tracer, who); return -3; }
     const DevView &d = E->d;
     if (level > 0 && (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M)) { set_err(errm, errm_len, "%s: rows %d..%d outside 1..%d", who, jlo, jlo + nrows - 1, d.M); return -3; }
-    if (level > 0 && row_tree(d.L).nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
+    if (K.columns && level > 0 && (d.slab || d.joff != 0 || d.Mg != d.M)) {
+        set_err(errm, errm_len, "%s: a handle on a band of rows keeps no column series (a column's tree crosses the bands)", who);
+        return -6;
+    }
+    if (!K.columns && level > 0 && row_tree(d.L).nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
     recorder_free(R);
     if (level == 0) return 0;
     const int cnt = K.count(E->ntrc, d.nlay, level);
+    const int wlo = jlo, whi = jlo + nrows - 1;
+    if (K.columns) { jlo = 1; nrows = d.L; }          // (the lines of the record are the columns)
     int rc = K.scratch(E, R, cnt, nrows, errm, errm_len);
     if (!rc) rc = alloc_aligned(E, R.allocs, &R.rec, (size_t)nrec * nrows * cnt, errm, errm_len);
     if (rc) { recorder_free(R); return rc; }
-    R.level = level; R.stride = stride; R.nrec = nrec; R.jlo = jlo; R.rows = nrows; R.by_caller = by_caller;
+    R.level = level; R.stride = stride; R.nrec = nrec; R.jlo = jlo; R.rows = nrows; R.by_caller = by_caller; R.wlo = wlo; R.whi = whi;
     HIP_TRY(hipStreamSynchronize(E->stream));
     return 0;
 }
@@ -1748,6 +1768,13 @@ int beom_band_set_tracer_series(beom_handle E, int level, int stride, int nrec, 
     return recorder_set(E, &beom_engine::tser, "beom_band_set_tracer_series", level, stride, nrec, jlo, nrows, true, errm, errm_len);
 }
 
+int beom_set_column_series(beom_handle E, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len) {
+    return recorder_set(E, &beom_engine::cser, "beom_set_column_series", level, stride, nrec, jlo, jhi - jlo + 1, false, errm, errm_len);
+}
+int beom_sample_column_series(beom_handle E) { return recorder_sample(E, &beom_engine::cser); }
+int beom_download_column_series(beom_handle E, double *cols, int *tstp, int *count, char *errm, int errm_len) {
+    return recorder_download(E, &beom_engine::cser, cols, tstp, count, errm, errm_len);
+}
 int beom_sample_series(beom_handle E) { return recorder_sample(E, &beom_engine::ser); }
 int beom_sample_tracer_series(beom_handle E) { return recorder_sample(E, &beom_engine::tser); }
 
@@ -2515,6 +2542,8 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom.launches, 2000000000ll);     // all calls so far
     if (!strcmp(what, "tracer_series")) return E->tser.level;
     if (!strcmp(what, "tracer_series_records")) return (int)E->tser.tstp.size();
+    if (!strcmp(what, "column_series")) return E->cser.level;
+    if (!strcmp(what, "column_series_records")) return (int)E->cser.tstp.size();
     if (!strcmp(what, "series")) return E->ser.level;
     if (!strcmp(what, "series_records")) return (int)E->ser.tstp.size();
     if (!strcmp(what, "harmonics")) return E->harm.nfreq;
@@ -2549,6 +2578,7 @@ int beom_set_option(beom_handle E, const char *name, int value) {
     else if (!strcmp(name, "mont_history")) E->mont_history = value != 0;
     else if (!strcmp(name, "plain_sweeps")) E->plain_sweeps = value != 0;
     else if (!strcmp(name, "moments_by_caller")) E->mom_by_caller = value != 0;
+    else if (!strcmp(name, "column_series_batch")) E->cser_batch_opt = value > 0 ? value : 0;      // (looked at by the next beom_set_column_series)
     else if (!strcmp(name, "tracer_series_batch")) E->tser_batch_opt = value > 0 ? value : 0;      // (looked at by the next beom_set_tracer_series)
     else return -3;
     return 0;
@@ -2582,3 +2612,38 @@ int beom_device_field(beom_handle E, const char *name, void **dptr, int64_t *str
 }
 
 }  // extern "C"
+
+// ---- column series (beom_column_series.h): defined last, so that its kernels are instantiated behind every other one ------
+// The column series' block partials of a launch stay under the tracer series' bound: a record is taken in batches of 64-column
+// chunks (never fewer than one); columns are independent, so the batches cannot change a bit.
+static int column_series_scratch(beom_engine *E, Recorder &R, int cnt, int ncols, char *errm, int errm_len) {
+    const size_t nch = (size_t)(ncols + 63) / 64, per_chunk = (size_t)((E->d.M + kColBlockRows - 1) / kColBlockRows) * cnt * 64;
+    size_t batch = E->cser_batch_opt > 0 ? (size_t)E->cser_batch_opt : kTracerSeriesScratch / (per_chunk * sizeof(double));
+    batch = std::min<size_t>(std::max<size_t>(batch, 1), nch);
+    R.batch = (int)batch;
+    if (const int rc = ensure_cellmap(E, errm, errm_len)) return rc;
+    return alloc_plain(E, R.allocs, &R.part, batch * per_chunk, errm, errm_len, false);
+}
+// one record of the column series (beom_column_series.h) of the fields as they stand into the next free slot, under step tstp:
+// `batch` chunks of columns per launch, every column finished on its own
+static void launch_column_series(beom_engine *E, int tstp) {
+    const DevView &d = E->d;
+    Recorder &R = E->cser;
+    const int cnt = beom_series_count(d.nlay, R.level), nch = (d.L + 63) / 64;
+    const int M2 = pow2_ceil(d.M), nblk = (d.M + kColBlockRows - 1) / kColBlockRows, nblkp2 = std::max(1, M2 / kColBlockRows);
+    double *rec = R.rec + R.tstp.size() * (size_t)R.rows * cnt;
+    const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
+    const int colpad = R.batch * 64;
+    for (int c0 = 0; c0 < nch; c0 += R.batch) {
+        const int nc = std::min(R.batch, nch - c0), ncols = std::min(nc * 64, d.L - c0 * 64);
+        pick_int<1, 2>(R.level, [&](auto lv) {
+            pick([&](auto dense) {
+                hipLaunchKernelGGL((k_column_blocks<dense, lv>), dim3((unsigned)nc, (unsigned)nblk), dim3(BEOM_BLOCK), 0, E->stream, d, c0,
+                                   R.wlo, R.whi, M2, E->integ_xper, E->integ_yper, map, R.part, colpad);
+            }, E->dense);
+        });
+        hipLaunchKernelGGL(k_column_finish<kColFinishLevels>, dim3((unsigned)((ncols + BEOM_BLOCK - 1) / BEOM_BLOCK), (unsigned)cnt), dim3(BEOM_BLOCK), 0, E->stream,
+                           (const double *)R.part, rec + (size_t)c0 * 64 * cnt, cnt, colpad, ncols, nblk, nblkp2);
+    }
+    R.tstp.push_back(tstp);
+}

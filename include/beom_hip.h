@@ -668,6 +668,41 @@ int beom_sample_series(beom_handle h);
 int beom_download_series(beom_handle h, double *rows, int *tstp, int *count, char *errm, int errm_len);
 int beom_band_set_series(beom_handle h, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len);
 
+/* ---- Column series: a record of the sums along columns per sampled step, kept on the device (no reference routine).  The
+ * other direction of the series: the volume transport of each layer through a line of W faces (the exchange flow over a sill,
+ * the front of a lock exchange) and x-t diagrams of volume, energy and elevation, for the flows along x.
+ * Terms: the series' own, on the rectangle c = i-1, r = j-1.  Level 1: per layer vol, ke, ens, circ, then eta2; level 2: also
+ * per layer h_u, then h_v.  The layout within a record is the series' and cnt = beom_series_count(nlay, level).  The integrals'
+ * live rule applies: +0.0 where there is no packed cell, on the duplicated column lm+1 of a frame periodic in x and on the
+ * duplicated row mm+1 of one periodic in y.
+ * One record is cols[(i-1)*cnt + k] for the columns i = 1..L (L = lm+1).  dl * tu[l] of column i is the volume transport of
+ * layer l through the W faces of that column; accumulated over the layers, the exchange / zonal overturning streamfunction in
+ * layer coordinates.
+ * Order of summation: a column is summed by the pairwise tree over the aligned GLOBAL row index (level k+1 adds elements 2m
+ * and 2m+1 of level k), the column padded with +0.0 to the next power of two of M = mm+1.  The padding is added, not skipped:
+ * (-0.0) + (+0.0) = +0.0 is part of the contract.  No atomics; the bits do not depend on the handle kind, the tile geometry
+ * or option "column_series_batch".
+ * Row window jlo..jhi (1 <= jlo <= jhi <= M; the whole column is 1..M): rows outside the window contribute +0.0 and the tree
+ * is unchanged — the transport through a strait that spans only part of a column.
+ * Semantics as the series': a record is written behind every step with tstp % stride == 0, where the series' sample sits.
+ * beom_step refuses with -3, before launching anything, a call whose steps would overflow the recorder (the message names
+ * beom_download_column_series).  beom_sample_column_series: one record by hand under the number of the handle's last step;
+ * -3 without a recorder or on a full one.  beom_download_column_series copies the filled records (cols[n][L][cnt], oldest
+ * first) and their steps, then sets the count to 0; any of cols, tstp, count may be NULL; -3 without a column series.  Uploads
+ * do not empty the recorder.  beom_set_column_series: level 0 frees (the other arguments are then not looked at); other
+ * arguments reallocate and empty; between steps only; -3 for a level outside 0..2, stride < 1, nrec < 1 or a window outside
+ * 1 <= jlo <= jhi <= M.  The recorder is independent of the series and the tracer series, and keeps a scratch of its own: the
+ * block partials of a launch stay under 64 MiB, a record being taken in batches of 64-column chunks (option
+ * "column_series_batch", beom_set_option, read by the next beom_set_column_series: chunks per launch, 0 = by that bound).
+ * Every single handle keeps one: dense, embedded, the table path, variant = 1, rigid lid, svis > 0, open boundaries.
+ * beom_info: "column_series" (the level), "column_series_records" (records held).  Handles on bands refuse with -6
+ * (beom_multi_*, whether created from global arrays or holding one band's window; a handle that is a band of rows): a column's
+ * tree crosses the bands, and the same bits would need each band's tree nodes per column and record, which nothing combines
+ * yet.  The definition over the global aligned row index is what lets that be added.  The Fortran host keeps none. */
+int beom_set_column_series(beom_handle h, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len);
+int beom_sample_column_series(beom_handle h);
+int beom_download_column_series(beom_handle h, double *cols, int *tstp, int *count, char *errm, int errm_len);
+
 /* ---- Tracer series: a record per sampled step of the tracers' row inventories, variance, face fluxes and bounds, kept on the
  * device (no reference routine): how much of a tracer is where, how fast it crosses a latitude, how quickly its variance is
  * mixed away and whether it has left its bounds, without a download.  A recorder of its own beside the series, as the tracer
@@ -986,6 +1021,10 @@ int beom_multi_integral_rows_local(beom_multi_handle m, int *own0, int *own1, do
  * rows are nowhere assembled.  One band that is the whole frame forwards to beom_set_series etc. */
 int beom_multi_set_series(beom_multi_handle m, int level, int stride, int nrec, char *errm, int errm_len);
 int beom_multi_download_series(beom_multi_handle m, double *rows, int *tstp, int *count, char *errm, int errm_len);
+
+/* Column series (see beom_set_column_series): both refuse with -6 and say why; a column's tree crosses the bands. */
+int beom_multi_set_column_series(beom_multi_handle m, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len);
+int beom_multi_download_column_series(beom_multi_handle m, double *cols, int *tstp, int *count, char *errm, int errm_len);
 
 /* Tracer series (see beom_set_tracer_series), placed like the series: every band records its OWNED rows on its main stream
  * behind the wait for that step's ghost rows, so q(S) and hlay(S) of a band's first owned row are landed ghosts; cut steps

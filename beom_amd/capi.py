@@ -97,7 +97,7 @@ def source_hash() -> str:
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
     for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_harmonics.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_forcing.h", "beom_dense_host.h",
-               "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", "beom_column_series.h", os.path.join("..", "..", "include", "beom_hip.h")):
+               "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", "beom_column_series.h", "beom_tracer_column_series.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -309,6 +309,15 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.beom_multi_download_column_series.argtypes = [MH, dpp, ip, ip, cp, ci]
         for name in COLUMN_SERIES_EXPORTS:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_tracer_column_series"):   # (likewise: an older build has no tracer column series)
+        ip = C.POINTER(ci)
+        lib.beom_set_tracer_column_series.argtypes = [H, ci, ci, ci, ci, ci, cp, ci]
+        lib.beom_sample_tracer_column_series.argtypes = [H]
+        lib.beom_download_tracer_column_series.argtypes = [H, dpp, ip, ip, cp, ci]
+        lib.beom_multi_set_tracer_column_series.argtypes = [MH, ci, ci, ci, ci, ci, cp, ci]
+        lib.beom_multi_download_tracer_column_series.argtypes = [MH, dpp, ip, ip, cp, ci]
+        for name in TRACER_COLUMN_SERIES_EXPORTS:
+            getattr(lib, name).restype = ci
     if hasattr(lib, "beom_set_tracer_series"):   # (likewise: an older build has no tracer series)
         ip = C.POINTER(ci)
         lib.beom_tracer_series_count.argtypes = [ci, ci, ci]
@@ -362,6 +371,9 @@ TRACER_SERIES_EXPORTS = ("beom_tracer_series_count", "beom_set_tracer_series", "
                          "beom_multi_download_tracer_series")
 COLUMN_SERIES_EXPORTS = ("beom_set_column_series", "beom_sample_column_series", "beom_download_column_series",
                          "beom_multi_set_column_series", "beom_multi_download_column_series")
+TRACER_COLUMN_SERIES_EXPORTS = ("beom_set_tracer_column_series", "beom_sample_tracer_column_series",
+                                "beom_download_tracer_column_series", "beom_multi_set_tracer_column_series",
+                                "beom_multi_download_tracer_column_series")
 FORCING_EXPORTS = ("beom_forcing_weight", "beom_set_forcing", "beom_apply_forcing", "beom_download_forcing",
                    "beom_multi_set_forcing", "beom_multi_download_forcing")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
@@ -387,7 +399,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS + FORCING_EXPORTS + COLUMN_SERIES_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS + FORCING_EXPORTS + COLUMN_SERIES_EXPORTS + TRACER_COLUMN_SERIES_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -813,7 +825,7 @@ class _TracerMoments(_Accum):
 
 
 class _Recorder(_Handle):
-    """What _Series, _TracerSeries and _ColumnSeries share: a device-side recorder [records][lines][cnt] set and downloaded through the exports
+    """What _Series, _TracerSeries, _ColumnSeries and _TracerColumnSeries share: a device-side recorder [records][lines][cnt] set and downloaded through the exports
     beom_[multi_]{set,download}_<stem>, and sampled by hand on a single handle (beom_sample_<stem>)."""
 
     def _recorder_set(self, stem, level, stride, records, *window):
@@ -953,7 +965,46 @@ class _TracerSeries(_Recorder):
         return out
 
 
-class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _Harmonics, _Forcing):
+class _TracerColumnSeries(_Recorder):
+    """A record per sampled step of the tracers' column inventories, variance, face fluxes and bounds, kept on the device
+    (beom_set_tracer_column_series, include/beom_hip.h): the tracer series' quantities for every column of the frame, with a
+    level, stride, row window and recorder of its own.  Engine keeps one; MultiEngine refuses (a column's tree crosses the
+    bands)."""
+
+    tracer_column_series_records = 0
+
+    def set_tracer_column_series(self, level: int, stride: int = 1, records: int = 64, rows=None):
+        """level 1: inv, var per tracer and layer; 2: and fu, fv; 3: and cmin, cmax; 0 frees.  `records`: what the recorder
+        holds between two download_tracer_column_series (a step call that would overflow it is refused).  rows = (jlo, jhi):
+        only these rows of a column count; None = all, 1..mm+1.  Between steps only, after set_tracers."""
+        jlo, jhi = (1, self.p.mm + 1) if rows is None else rows
+        _, self.tracer_column_series_records = self._recorder_set("tracer_column_series", level, stride, records, int(jlo), int(jhi))
+
+    def download_tracer_column_series(self) -> dict:
+        """The records held, oldest first, and empties the recorder.  count, tstp[n]; cols[n, L, cnt] (L = lm+1 columns); the
+        views inv, var (column sums of q and of q*c) and, at level >= 2, fu, fv (column sums of the upstream face fluxes
+        through the W resp. S faces) and, at level 3, cmin, cmax (the concentration's bounds over the column's wet cells
+        inside the row window, +inf, -inf where there is none), each [n, L, ntrc, nlay]; at level >= 2 transport = dl * fu,
+        the tracer transport of layer l through the W faces of column i.  total[n, ntrc, nlay] = the integrals' tree over
+        the columns of inv: close to download_tracer_series()["total"] but NOT its bits — the tracer series adds along rows
+        first, this adds along columns first (both pairwise trees over the same terms)."""
+        nl, L = self.p.nlay, self.p.lm + 1
+        lv = 0 if self._multi else self.info("tracer_column_series")      # (set_tracers with another count frees it)
+        n, tstp, cols = self._recorder_download("tracer_column_series", "tracer column series", lv, self.tracer_column_series_records,
+                                                lambda lv: self.lib.beom_tracer_series_count(self.ntrc, nl, lv), L)
+        nq = 2 * lv
+        q = cols.reshape(n, L, self.ntrc, nl, nq)
+        out = {"count": n, "tstp": tstp, "cols": cols}
+        for m in range(nq):
+            out[TRACER_SERIES_NAMES[m]] = q[..., m]
+        out["total"] = np.array([combine_integral_rows(np.ascontiguousarray(c.reshape(L, self.ntrc * nl)))
+                                 for c in out["inv"]]).reshape(n, self.ntrc, nl)
+        if lv >= 2:
+            out["transport"] = float(self.p.dl) * out["fu"]
+        return out
+
+
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _TracerColumnSeries, _Harmonics, _Forcing):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     _prefix = "beom_"
@@ -1126,7 +1177,8 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         "moment_samples", "moment_launches", "tracer_moments" (the tracer moments' level), "tracer_moment_samples",
         "tracer_moment_launches", "harmonics" (the frequencies fitted), "harmonic_level", "harmonic_samples",
         "harmonic_launches" (one per field and sample), "series" (the series' level), "series_records" (records its recorder holds), "tracer_series" (the tracer series' level),
-        "tracer_series_records", "column_series" (the column series' level), "column_series_records"."""
+        "tracer_series_records", "column_series" (the column series' level), "column_series_records",
+        "tracer_column_series" (the tracer column series' level), "tracer_column_series_records"."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))
@@ -1205,6 +1257,11 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         """One record of the column series by hand, of the fields as they stand, under the last step's number."""
         self._recorder_sample("column_series", "column series")
 
+    def sample_tracer_column_series(self):
+        """One record of the tracer column series by hand, of the tracers and the state as they stand, under the last step's
+        number."""
+        self._recorder_sample("tracer_column_series", "tracer column series")
+
     def sample_tracer_series(self):
         """Per-sweep entry: one record of the tracers and the state as they stand, under the last step's number, whatever the
         stride."""
@@ -1214,7 +1271,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _Harmonics, _Forcing):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _TracerColumnSeries, _Harmonics, _Forcing):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""

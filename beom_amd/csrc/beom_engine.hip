@@ -32,7 +32,8 @@
 #include "beom_dense_host.h"
 #include "beom_plan.h"
 #include "beom_recorder.h"
-#include "beom_column_series.h"      // (last: the kernels before it keep their place in the code object)
+#include "beom_column_series.h"      // (behind every earlier header: the kernels before it keep their place in the code object)
+#include "beom_tracer_column_series.h"      // (last, for the same reason)
 
 using beom_plan::StepFacts;
 using beom_plan::StepPlan;
@@ -135,6 +136,7 @@ struct RecorderKind {
     void (*launch)(beom_engine *, int tstp);
     const char *no_tracer, *none, *overflow;
     bool columns = false;              // the recorder's lines are the L columns, and jlo .. jlo+nrows-1 is its row window
+    const char *what = nullptr;        // (columns) its name in the refusal of a handle on a band of rows
 };
 static int series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
 static int tracer_series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
@@ -142,6 +144,8 @@ static void launch_series(beom_engine *E, int tstp);
 static void launch_tracer_series(beom_engine *E, int tstp);
 static int column_series_scratch(beom_engine *E, Recorder &R, int cnt, int ncols, char *errm, int errm_len);
 static void launch_column_series(beom_engine *E, int tstp);
+static int tracer_column_series_scratch(beom_engine *E, Recorder &R, int cnt, int ncols, char *errm, int errm_len);
+static void launch_tracer_column_series(beom_engine *E, int tstp);
 constexpr RecorderKind kSeries{2, [](int, int nlay, int level) { return beom_series_count(nlay, level); },
     series_scratch, launch_series, nullptr,
     "beom_download_series: the handle keeps no series (beom_set_series)",
@@ -157,7 +161,13 @@ constexpr RecorderKind kColumnSeries{2, [](int, int nlay, int level) { return be
     column_series_scratch, launch_column_series, nullptr,
     "beom_download_column_series: the handle keeps no column series (beom_set_column_series)",
     "beom_step: steps %d..%d would write %lld records of the column series (stride %d) but the recorder holds %lld of %d: "
-    "empty it with beom_download_column_series, or take fewer steps per call", true};
+    "empty it with beom_download_column_series, or take fewer steps per call", true, "column series"};
+constexpr RecorderKind kTracerColumnSeries{3, beom_tracer_series_count,
+    tracer_column_series_scratch, launch_tracer_column_series,
+    "%s: the handle carries no tracer (beom_set_tracers comes first)",
+    "beom_download_tracer_column_series: the handle keeps no tracer column series (beom_set_tracer_column_series)",
+    "beom_step: steps %d..%d would write %lld records of the tracer column series (stride %d) but the recorder holds %lld of %d: "
+    "empty it with beom_download_tracer_column_series, or take fewer steps per call", true, "tracer column series"};
 struct Recorder {
     const RecorderKind *kind;
     int level = 0, stride = 1, nrec = 0, jlo = 1, rows = 0;      // local rows jlo .. jlo+rows-1
@@ -308,6 +318,10 @@ struct beom_engine {
     // level, stride, row window and scratch of its own
     Recorder cser{&kColumnSeries};
     int cser_batch_opt = 0;            // option "column_series_batch": 64-column chunks per launch (0 = by the bound on the scratch)
+    // tracer column series (beom_set_tracer_column_series; beom_tracer_column_series.h): a recorder [nrec][L][ntrc*nlay*2*level]
+    // whose lines are the columns, with level, stride, row window and scratch of its own
+    Recorder tcser{&kTracerColumnSeries};
+    int tcser_batch_opt = 0;           // option "tracer_column_series_batch": 64-column chunks per launch (0 = by the bound on the scratch)
     // forcing in time (beom_set_forcing; beom_forcing.h): frc[0] the wind stress, frc[1] hdot; what beom_create gave, to
     // return to when a set is cleared; a body force of exactly -0 (it bars the folded stress, see derive_forcing_flags)
     ForcingSet frc[2];
@@ -670,7 +684,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs, &E->cser.allocs, &E->frc[0].allocs, &E->frc[1].allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs, &E->cser.allocs, &E->tcser.allocs, &E->frc[0].allocs, &E->frc[1].allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -1339,7 +1353,7 @@ static void one_step(beom_engine *E, const StepPlan &p, int flt = -1) {
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->harm.acc, tstp)) launch_harmonics(E, tstp, p.ctim);
-    for (const Recorder *R : {&E->ser, &E->tser, &E->cser})
+    for (const Recorder *R : {&E->ser, &E->tser, &E->cser, &E->tcser})
         if (!R->by_caller && recorder_due(*R, tstp)) R->kind->launch(E, tstp);
 }
 
@@ -1375,7 +1389,7 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
         !beom_recorder::holds(tstp_first, nsteps, E->flt_stride, E->flt_rec_tstp.size(), E->flt_nrec, errm, errm_len,
                               "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
                               "empty it with beom_download_float_track, or take fewer steps per call")) return -3;
-    for (const Recorder *R : {&E->ser, &E->tser, &E->cser})
+    for (const Recorder *R : {&E->ser, &E->tser, &E->cser, &E->tcser})
         if (R->level > 0 && !R->by_caller &&
             !beom_recorder::holds(tstp_first, nsteps, R->stride, R->tstp.size(), R->nrec, errm, errm_len, R->kind->overflow)) return -3;
     HIP_TRY(hipSetDevice(E->device));
@@ -1709,7 +1723,7 @@ static int recorder_set(beom_engine *E, Recorder beom_engine::*which, const char
     const DevView &d = E->d;
     if (level > 0 && (jlo < 1 || nrows < 1 || jlo + nrows - 1 > d.M)) { set_err(errm, errm_len, "%s: rows %d..%d outside 1..%d", who, jlo, jlo + nrows - 1, d.M); return -3; }
     if (K.columns && level > 0 && (d.slab || d.joff != 0 || d.Mg != d.M)) {
-        set_err(errm, errm_len, "%s: a handle on a band of rows keeps no column series (a column's tree crosses the bands)", who);
+        set_err(errm, errm_len, "%s: a handle on a band of rows keeps no %s (a column's tree crosses the bands)", who, K.what);
         return -6;
     }
     if (!K.columns && level > 0 && row_tree(d.L).nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
@@ -1775,6 +1789,13 @@ int beom_sample_column_series(beom_handle E) { return recorder_sample(E, &beom_e
 int beom_download_column_series(beom_handle E, double *cols, int *tstp, int *count, char *errm, int errm_len) {
     return recorder_download(E, &beom_engine::cser, cols, tstp, count, errm, errm_len);
 }
+int beom_set_tracer_column_series(beom_handle E, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len) {
+    return recorder_set(E, &beom_engine::tcser, "beom_set_tracer_column_series", level, stride, nrec, jlo, jhi - jlo + 1, false, errm, errm_len);
+}
+int beom_sample_tracer_column_series(beom_handle E) { return recorder_sample(E, &beom_engine::tcser); }
+int beom_download_tracer_column_series(beom_handle E, double *cols, int *tstp, int *count, char *errm, int errm_len) {
+    return recorder_download(E, &beom_engine::tcser, cols, tstp, count, errm, errm_len);
+}
 int beom_sample_series(beom_handle E) { return recorder_sample(E, &beom_engine::ser); }
 int beom_sample_tracer_series(beom_handle E) { return recorder_sample(E, &beom_engine::tser); }
 
@@ -1807,7 +1828,7 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); recorder_free(E->tser); }        // (their arrays have the tracers' shape)
+    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); recorder_free(E->tser); recorder_free(E->tcser); }        // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
@@ -2542,6 +2563,8 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_moment_launches")) return (int)std::min<long long>(E->tmom.launches, 2000000000ll);     // all calls so far
     if (!strcmp(what, "tracer_series")) return E->tser.level;
     if (!strcmp(what, "tracer_series_records")) return (int)E->tser.tstp.size();
+    if (!strcmp(what, "tracer_column_series")) return E->tcser.level;
+    if (!strcmp(what, "tracer_column_series_records")) return (int)E->tcser.tstp.size();
     if (!strcmp(what, "column_series")) return E->cser.level;
     if (!strcmp(what, "column_series_records")) return (int)E->cser.tstp.size();
     if (!strcmp(what, "series")) return E->ser.level;
@@ -2579,6 +2602,7 @@ int beom_set_option(beom_handle E, const char *name, int value) {
     else if (!strcmp(name, "plain_sweeps")) E->plain_sweeps = value != 0;
     else if (!strcmp(name, "moments_by_caller")) E->mom_by_caller = value != 0;
     else if (!strcmp(name, "column_series_batch")) E->cser_batch_opt = value > 0 ? value : 0;      // (looked at by the next beom_set_column_series)
+    else if (!strcmp(name, "tracer_column_series_batch")) E->tcser_batch_opt = value > 0 ? value : 0;      // (looked at by the next beom_set_tracer_column_series)
     else if (!strcmp(name, "tracer_series_batch")) E->tser_batch_opt = value > 0 ? value : 0;      // (looked at by the next beom_set_tracer_series)
     else return -3;
     return 0;
@@ -2644,6 +2668,41 @@ static void launch_column_series(beom_engine *E, int tstp) {
         });
         hipLaunchKernelGGL(k_column_finish<kColFinishLevels>, dim3((unsigned)((ncols + BEOM_BLOCK - 1) / BEOM_BLOCK), (unsigned)cnt), dim3(BEOM_BLOCK), 0, E->stream,
                            (const double *)R.part, rec + (size_t)c0 * 64 * cnt, cnt, colpad, ncols, nblk, nblkp2);
+    }
+    R.tstp.push_back(tstp);
+}
+
+// ---- tracer column series (beom_tracer_column_series.h): behind the column series', for the same reason ------------------
+// The block partials of a launch stay under the tracer series' bound, in a scratch of its own: a record is taken in batches of
+// 64-column chunks (never fewer than one); columns are independent, so the batches cannot change a bit.
+static int tracer_column_series_scratch(beom_engine *E, Recorder &R, int cnt, int ncols, char *errm, int errm_len) {
+    const size_t nch = (size_t)(ncols + 63) / 64, per_chunk = (size_t)((E->d.M + kColBlockRows - 1) / kColBlockRows) * cnt * 64;
+    size_t batch = E->tcser_batch_opt > 0 ? (size_t)E->tcser_batch_opt : kTracerSeriesScratch / (per_chunk * sizeof(double));
+    batch = std::min<size_t>(std::max<size_t>(batch, 1), nch);
+    R.batch = (int)batch;
+    if (const int rc = ensure_cellmap(E, errm, errm_len)) return rc;
+    return alloc_plain(E, R.allocs, &R.part, batch * per_chunk, errm, errm_len, false);
+}
+// one record of the tracer column series of q, hlay, h_u, h_v as they stand into the next free slot, under step tstp: `batch`
+// chunks of columns per launch, every column finished on its own
+static void launch_tracer_column_series(beom_engine *E, int tstp) {
+    const DevView &d = E->d;
+    Recorder &R = E->tcser;
+    const int nq = 2 * R.level, cnt = beom_tracer_series_count(E->ntrc, d.nlay, R.level), nch = (d.L + 63) / 64;
+    const int M2 = pow2_ceil(d.M), nblk = (d.M + kColBlockRows - 1) / kColBlockRows, nblkp2 = std::max(1, M2 / kColBlockRows);
+    double *rec = R.rec + R.tstp.size() * (size_t)R.rows * cnt;
+    const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
+    const int colpad = R.batch * 64;
+    for (int c0 = 0; c0 < nch; c0 += R.batch) {
+        const int nc = std::min(R.batch, nch - c0), ncols = std::min(nc * 64, d.L - c0 * 64);
+        pick_int<1, 3>(R.level, [&](auto lv) {
+            pick([&](auto dense) {
+                hipLaunchKernelGGL((k_tracer_column_blocks<dense, lv>), dim3((unsigned)nc, (unsigned)nblk), dim3(BEOM_BLOCK), 0, E->stream, d,
+                                   (const double *)E->trc_q, E->ntrc, c0, R.wlo, R.whi, M2, E->integ_xper, E->integ_yper, map, R.part, colpad);
+            }, E->dense);
+        });
+        hipLaunchKernelGGL(k_tracer_column_finish<kColFinishLevels>, dim3((unsigned)((ncols + BEOM_BLOCK - 1) / BEOM_BLOCK), (unsigned)cnt), dim3(BEOM_BLOCK), 0,
+                           E->stream, (const double *)R.part, rec + (size_t)c0 * 64 * cnt, cnt, nq, colpad, ncols, nblk, nblkp2);
     }
     R.tstp.push_back(tstp);
 }

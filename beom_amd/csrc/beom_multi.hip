@@ -1598,10 +1598,10 @@ int beom_multi_download_tracer_series(beom_multi_handle M, double *rows, int *ts
 
 // Column series (beom_column_series.h): a column's tree crosses the bands, and the same bits would need every band's canonical
 // tree nodes per column and record, which nothing combines yet.  Refused on every handle on bands, whatever it was created from.
-static int column_series_refused(beom_multi *M, const char *who, char *errm, int errm_len) {
+static int column_series_refused(beom_multi *M, const char *who, char *errm, int errm_len, const char *tracer = "", const char *stem = "") {
     if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
-    m_err(errm, errm_len, "%s: a handle on bands keeps no column series (a column's tree over the global rows crosses the bands, "
-                          "and nothing combines the bands' tree nodes yet); use a single handle (beom_set_column_series)", who);
+    m_err(errm, errm_len, "%s: a handle on bands keeps no %scolumn series (a column's tree over the global rows crosses the bands, "
+                          "and nothing combines the bands' tree nodes yet); use a single handle (beom_set_%scolumn_series)", who, tracer, stem);
     return -6;
 }
 int beom_multi_set_column_series(beom_multi_handle M, int, int, int, int, int, char *errm, int errm_len) {
@@ -1609,6 +1609,13 @@ int beom_multi_set_column_series(beom_multi_handle M, int, int, int, int, int, c
 }
 int beom_multi_download_column_series(beom_multi_handle M, double *, int *, int *, char *errm, int errm_len) {
     return column_series_refused(M, "beom_multi_download_column_series", errm, errm_len);
+}
+// Tracer column series (beom_tracer_column_series.h): refused for the same reason.
+int beom_multi_set_tracer_column_series(beom_multi_handle M, int, int, int, int, int, char *errm, int errm_len) {
+    return column_series_refused(M, "beom_multi_set_tracer_column_series", errm, errm_len, "tracer ", "tracer_");
+}
+int beom_multi_download_tracer_column_series(beom_multi_handle M, double *, int *, int *, char *errm, int errm_len) {
+    return column_series_refused(M, "beom_multi_download_tracer_column_series", errm, errm_len, "tracer ", "tracer_");
 }
 
 int beom_multi_upload_local(beom_multi_handle M, const beom_state *win, const beom_state *orphan, char *errm, int errm_len) {

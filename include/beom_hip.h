@@ -751,6 +751,41 @@ int beom_sample_tracer_series(beom_handle h);
 int beom_download_tracer_series(beom_handle h, double *rows, int *tstp, int *count, char *errm, int errm_len);
 int beom_band_set_tracer_series(beom_handle h, int level, int stride, int nrec, int jlo, int nrows, char *errm, int errm_len);
 
+/* ---- Tracer column series: a record per sampled step of the tracers' column inventories, variance, face fluxes and bounds,
+ * kept on the device (no reference routine).  The other direction of the tracer series, for the flows along x in which a dye
+ * is the main observable: how much of the dense-water tracer has crossed the sill, the tracer flux through a strait section,
+ * whether the dye front has left its bounds at some x, without a download.
+ * The per-cell quantities are the tracer series' own, word for word (x_q, c = trc_conc, x_v = x_q * c rounded then summed,
+ * x_fu, x_fv = trc_face, x_b = c + 0.0; "Tracer series" above), of q, hlay, h_u, h_v as the step leaves them.
+ * One record is cols[(i-1)*cnt + ((t*nlay + (l-1))*nq + m)] for the columns i = 1..L (L = lm+1), t = 0..ntrc-1, nq = 2*level,
+ * cnt = beom_tracer_series_count(ntrc, nlay, level):
+ *   level 1:  m = 0 inv = sum x_q, m = 1 var = sum x_v;   level 2:  and m = 2 fu, m = 3 fv;   level 3:  and m = 4 cmin, m = 5 cmax
+ * Live rule: the integrals' and the tracer series'.  A position with no packed cell holds +0.0, as do the duplicated column
+ * lm+1 and row mm+1 of a periodic frame and every row outside the window jlo..jhi (1-based, inclusive; the whole column is 1..M).
+ * Order of summation: the column series' — the pairwise tree over the aligned GLOBAL row index r = j-1, the column padded with
+ * +0.0 to M2, the next power of two of M; the padding is added, not skipped.
+ * Bounds: cmin, cmax are the minimum and maximum of x_b over the live positions of the column inside the window with
+ * hlay(p,l) > 0; +inf, -inf where there is none.  No signed zero enters, so any order of comparison gives the same bits.
+ * dl * fu of column i is the tracer transport of layer l through the W faces of that column.  Under scheme 2 the faces are
+ * still the upstream ones; the fluxes of the lateral and vertical mixing are not in fu, fv.
+ * A record is sampled where the tracer series' record is sampled, behind every step with tstp % stride == 0.  beom_step
+ * refuses with -3, before launching anything, a call whose steps would overflow the recorder (the message names
+ * beom_download_tracer_column_series).  beom_sample_tracer_column_series: one record by hand under the number of the handle's
+ * last step; -3 without a recorder or on a full one.  beom_download_tracer_column_series copies the filled records
+ * (cols[n][L][cnt], oldest first) and their steps, then sets the count to 0; any of cols, tstp, count may be NULL; -3 without a
+ * recorder.  Uploads leave the recorder alone; beom_set_tracers with another count frees it.
+ * beom_set_tracer_column_series: level 0 frees; other arguments reallocate and empty; between steps only; -3 for a level
+ * outside 0..3, stride < 1, nrec < 1, a window outside 1 <= jlo <= jhi <= M or a handle without tracers.  The recorder is
+ * independent of the other three and keeps a scratch of its own: the block partials of a launch stay under 64 MiB, a record
+ * being taken in batches of 64-column chunks (option "tracer_column_series_batch", beom_set_option, read by the next
+ * beom_set_tracer_column_series: chunks per launch, 0 = by that bound; the bits do not depend on it).  A handle without one
+ * launches exactly what it launched before.  beom_info: "tracer_column_series" (the level),
+ * "tracer_column_series_records" (records held).  Handles on bands refuse with -6 (beom_multi_*; a handle that is a band of
+ * rows): a column's tree crosses the bands.  The Fortran host keeps none. */
+int beom_set_tracer_column_series(beom_handle h, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len);
+int beom_sample_tracer_column_series(beom_handle h);
+int beom_download_tracer_column_series(beom_handle h, double *cols, int *tstp, int *count, char *errm, int errm_len);
+
 /* ---- Several GPUs: the frame cut into bands of rows (SURVEY §8b "Threading", §8e) -------------
  * No reference counterpart (the reference is OpenMP only).  The whole DENSE frame (ndeg = (lm+1)(mm+1))
  * is cut into bands of rows, one band per HIP device, each an ordinary slab handle with 4 ghost rows
@@ -1025,6 +1060,10 @@ int beom_multi_download_series(beom_multi_handle m, double *rows, int *tstp, int
 /* Column series (see beom_set_column_series): both refuse with -6 and say why; a column's tree crosses the bands. */
 int beom_multi_set_column_series(beom_multi_handle m, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len);
 int beom_multi_download_column_series(beom_multi_handle m, double *cols, int *tstp, int *count, char *errm, int errm_len);
+
+/* Tracer column series (see beom_set_tracer_column_series): both refuse with -6 and say why; a column's tree crosses the bands. */
+int beom_multi_set_tracer_column_series(beom_multi_handle m, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len);
+int beom_multi_download_tracer_column_series(beom_multi_handle m, double *cols, int *tstp, int *count, char *errm, int errm_len);
 
 /* Tracer series (see beom_set_tracer_series), placed like the series: every band records its OWNED rows on its main stream
  * behind the wait for that step's ghost rows, so q(S) and hlay(S) of a band's first owned row are landed ghosts; cut steps

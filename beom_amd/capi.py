@@ -97,7 +97,7 @@ def source_hash() -> str:
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha1()
     for fn in ("beom_engine.hip", "beom_multi.hip", "beom_dev.h", "beom_kernels.h", "beom_integrals.h", "beom_series.h", "beom_tracers.h", "beom_tracers_lim.h", "beom_tracer_mix.h", "beom_tracer_vmix.h", "beom_floats.h", "beom_moments.h", "beom_harmonics.h", "beom_tracer_moments.h", "beom_tracer_series.h", "beom_forcing.h", "beom_dense_host.h",
-               "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", "beom_column_series.h", "beom_tracer_column_series.h", os.path.join("..", "..", "include", "beom_hip.h")):
+               "beom_bands_host.h", "beom_plan.h", "beom_recorder.h", "beom_column_series.h", "beom_tracer_column_series.h", "beom_maps.h", os.path.join("..", "..", "include", "beom_hip.h")):
         with open(os.path.join(csrc, fn), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -318,6 +318,16 @@ def load(path: Optional[str] = None) -> C.CDLL:
         lib.beom_multi_download_tracer_column_series.argtypes = [MH, dpp, ip, ip, cp, ci]
         for name in TRACER_COLUMN_SERIES_EXPORTS:
             getattr(lib, name).restype = ci
+    if hasattr(lib, "beom_set_maps"):            # (likewise: an older build has no maps)
+        ip = C.POINTER(ci)
+        lib.beom_maps_count.argtypes = [ci, ci, ci]
+        lib.beom_set_maps.argtypes = [H, ci, ci, ci, ci, cp, ci]
+        lib.beom_sample_maps.argtypes = [H]
+        lib.beom_download_maps.argtypes = [H, dpp, ip, ip, cp, ci]
+        lib.beom_multi_set_maps.argtypes = [MH, ci, ci, ci, ci, cp, ci]
+        lib.beom_multi_download_maps.argtypes = [MH, dpp, ip, ip, cp, ci]
+        for name in MAPS_EXPORTS:
+            getattr(lib, name).restype = ci
     if hasattr(lib, "beom_set_tracer_series"):   # (likewise: an older build has no tracer series)
         ip = C.POINTER(ci)
         lib.beom_tracer_series_count.argtypes = [ci, ci, ci]
@@ -374,6 +384,8 @@ COLUMN_SERIES_EXPORTS = ("beom_set_column_series", "beom_sample_column_series", 
 TRACER_COLUMN_SERIES_EXPORTS = ("beom_set_tracer_column_series", "beom_sample_tracer_column_series",
                                 "beom_download_tracer_column_series", "beom_multi_set_tracer_column_series",
                                 "beom_multi_download_tracer_column_series")
+MAPS_EXPORTS = ("beom_maps_count", "beom_set_maps", "beom_sample_maps", "beom_download_maps", "beom_multi_set_maps",
+                "beom_multi_download_maps")
 FORCING_EXPORTS = ("beom_forcing_weight", "beom_set_forcing", "beom_apply_forcing", "beom_download_forcing",
                    "beom_multi_set_forcing", "beom_multi_download_forcing")
 ERR_FLOAT_REACH, ERR_FLOAT_OVERFLOW, ERR_FLOAT_CLAIM = -41, -42, -43      # beom_multi_download_floats (include/beom_hip.h)
@@ -399,7 +411,7 @@ EXPORTS = ("beom_abi_version", "beom_device_count", "beom_device_pci_bus_id", "b
            "beom_multi_set_tracers", "beom_multi_upload_tracers", "beom_multi_download_tracers",
            "beom_set_tracer_scheme", "beom_multi_set_tracer_scheme",
            "beom_set_floats", "beom_upload_floats", "beom_download_floats", "beom_download_float_track", "beom_update_floats",
-           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS + FORCING_EXPORTS + COLUMN_SERIES_EXPORTS + TRACER_COLUMN_SERIES_EXPORTS
+           ) + MOMENT_EXPORTS + MULTI_FLOAT_EXPORTS + TRACER_MOMENT_EXPORTS + SERIES_EXPORTS + TRACER_MIX_EXPORTS + TRACER_VMIX_EXPORTS + TRACER_SERIES_EXPORTS + HARMONIC_EXPORTS + FORCING_EXPORTS + COLUMN_SERIES_EXPORTS + TRACER_COLUMN_SERIES_EXPORTS + MAPS_EXPORTS
 
 STATE_NAMES = ("hlay", "u", "v", "h_u", "h_v", "rs_h", "dmdx", "dmdy", "v_cc", "v_ll",
                "tt3d", "tb3d", "tu3d")
@@ -1004,7 +1016,44 @@ class _TracerColumnSeries(_Recorder):
         return out
 
 
-class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _TracerColumnSeries, _Harmonics, _Forcing):
+class _Maps(_Recorder):
+    """A record of sums over aligned B x B blocks of cells per sampled step, kept on the device (beom_set_maps,
+    include/beom_hip.h): coarse maps of thickness, velocity, kinetic energy, transports and tracer content in time, with a
+    level, block edge, stride and recorder of their own.  Engine keeps them; MultiEngine refuses (a block's tree must not
+    cross a seam between bands)."""
+
+    maps_records = 0
+
+    def set_maps(self, level: int, block: int = 8, stride: int = 1, records: int = 16):
+        """level 1: n per block and h, u, v per layer; 2: and ke, hu, hv; 3: and the content q per tracer and layer (after
+        set_tracers); 0 frees.  block: the edge B of a block, a power of two in 2..64.  `records`: what the recorder holds
+        between two download_maps (a step call that would overflow it is refused).  Between steps only."""
+        self._check(self._fn("set_maps")(self.h, int(level), int(block), int(stride), int(records), self._err, ERRLEN))
+        self.maps_records = int(records) if level else 0
+
+    def download_maps(self) -> dict:
+        """The records held, oldest first, and empties the recorder.  count, tstp[n], block; raw[n, cnt, Mc, Lc] (Mc =
+        ceil((mm+1)/B) block rows, Lc = ceil((lm+1)/B) block columns); the views n[n, Mc, Lc] (live cells per block: what a
+        mean divides by) and h, u, v [n, nlay, Mc, Lc]; at level >= 2 ke, hu, hv; at level 3 q[n, ntrc, nlay, Mc, Lc]."""
+        nl = self.p.nlay
+        lv = 0 if self._multi else self.info("maps")                     # (set_tracers with another count frees level 3)
+        B = self.info("maps_block") if lv else 1
+        Lc, Mc = -(-(self.p.lm + 1) // B), -(-(self.p.mm + 1) // B)
+        n, tstp, raw = self._recorder_download("maps", "maps", lv, self.maps_records,
+                                               lambda lv: self.lib.beom_maps_count(self.ntrc, nl, lv), Mc * Lc)
+        cnt = raw.shape[2]
+        raw = raw.reshape(n, cnt, Mc, Lc)           # (a record is [lines * cnt] doubles; inside it is [cnt][Mc][Lc])
+        E = 6 if lv >= 2 else 3
+        f = raw[:, 1:1 + E * nl].reshape(n, nl, E, Mc, Lc)
+        out = {"count": n, "tstp": tstp, "block": B, "raw": raw, "n": raw[:, 0]}
+        for m, name in enumerate(("h", "u", "v", "ke", "hu", "hv")[:E]):
+            out[name] = f[:, :, m]
+        if lv >= 3:
+            out["q"] = raw[:, 1 + 6 * nl:].reshape(n, self.ntrc, nl, Mc, Lc)
+        return out
+
+
+class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _TracerColumnSeries, _Maps, _Harmonics, _Forcing):
     """One handle = one GPU's copy of the engine state (mirror of the Fortran module)."""
 
     _prefix = "beom_"
@@ -1178,7 +1227,8 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         "tracer_moment_launches", "harmonics" (the frequencies fitted), "harmonic_level", "harmonic_samples",
         "harmonic_launches" (one per field and sample), "series" (the series' level), "series_records" (records its recorder holds), "tracer_series" (the tracer series' level),
         "tracer_series_records", "column_series" (the column series' level), "column_series_records",
-        "tracer_column_series" (the tracer column series' level), "tracer_column_series_records"."""
+        "tracer_column_series" (the tracer column series' level), "tracer_column_series_records", "maps" (the maps' level),
+        "maps_block" (their block edge), "maps_records", "map_launches" (map launches so far)."""
         v = self.lib.beom_info(self.h, what.encode())
         if v < 0:
             raise BeomError("beom_info(%s) = %d" % (what, v))
@@ -1262,6 +1312,10 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
         number."""
         self._recorder_sample("tracer_column_series", "tracer column series")
 
+    def sample_maps(self):
+        """One record of the maps by hand, of the fields as they stand, under the last step's number."""
+        self._recorder_sample("maps", "maps")
+
     def sample_tracer_series(self):
         """Per-sweep entry: one record of the tracers and the state as they stand, under the last step's number, whatever the
         stride."""
@@ -1271,7 +1325,7 @@ class Engine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries
     def distribute_stress(self): self._check(self.lib.beom_distribute_stress(self.h))
 
 
-class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _TracerColumnSeries, _Harmonics, _Forcing):
+class MultiEngine(_Tracers, _Floats, _Moments, _TracerMoments, _Series, _TracerSeries, _ColumnSeries, _TracerColumnSeries, _Maps, _Harmonics, _Forcing):
     """beom_multi_*: the whole frame on several HIP devices from ONE process (row bands with ghost
     exchange inside the library) — what the Fortran host uses with BEOM_NGPU > 1.  `devices` may
     name a device more than once (tests: three bands on the one GPU of the box)."""

@@ -23,23 +23,25 @@ constexpr int kColBlockRows = kColRows * kColWaves;
 
 // The streaming pairwise tree of E sums over kColRows elements pushed in order: s[e][k] waits as the left operand of level k.
 // Every index is static: where r is a constant of an unrolled row loop the conditions fold away, where the row loop is rolled
-// they are wave-uniform.
-template <int E>
+// they are wave-uniform.  LOG: the levels there are registers for; `levels` <= LOG: those in use (the maps' block edge is a
+// run-time value, beom_maps.h), a constant LOG in the column series, where its test folds away.
+template <int E, int LOG = kColLog>
 struct ColumnTree {
-    double s[E][kColLog];
-    // once the sub-block is complete (r = kColRows - 1), sum[] holds its sums
-    __device__ __forceinline__ void push(int r, const double (&t)[E], double (&sum)[E]) {
+    double s[E][LOG];
+    // once the sub-block is complete (r = 2^levels - 1), sum[] holds its sums
+    __device__ __forceinline__ void push(int r, const double (&t)[E], double (&sum)[E], int levels = LOG) {
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             double v = t[e];
-            bool placed = false;
+            bool placed = false, root = false;             // root: v has passed every level in use (stored once, below)
 #pragma unroll
-            for (int k = 0; k < kColLog; ++k) {
+            for (int k = 0; k < LOG; ++k) {
                 if (placed) continue;
-                if ((r >> k) & 1) v = s[e][k] + v;
+                if (k >= levels) { root = true; placed = true; }
+                else if ((r >> k) & 1) v = s[e][k] + v;
                 else { s[e][k] = v; placed = true; }
             }
-            if (!placed) sum[e] = v;
+            if (root || !placed) sum[e] = v;
         }
     }
 };

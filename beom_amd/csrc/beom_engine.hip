@@ -33,7 +33,8 @@
 #include "beom_plan.h"
 #include "beom_recorder.h"
 #include "beom_column_series.h"      // (behind every earlier header: the kernels before it keep their place in the code object)
-#include "beom_tracer_column_series.h"      // (last, for the same reason)
+#include "beom_tracer_column_series.h"      // (behind it, for the same reason)
+#include "beom_maps.h"      // (last, for the same reason)
 
 using beom_plan::StepFacts;
 using beom_plan::StepPlan;
@@ -137,6 +138,7 @@ struct RecorderKind {
     const char *no_tracer, *none, *overflow;
     bool columns = false;              // the recorder's lines are the L columns, and jlo .. jlo+nrows-1 is its row window
     const char *what = nullptr;        // (columns) its name in the refusal of a handle on a band of rows
+    int (*lines)(const beom_engine *) = nullptr;      // the maps: the lines of a record, where they are neither rows nor columns
 };
 static int series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
 static int tracer_series_scratch(beom_engine *E, Recorder &R, int cnt, int nrows, char *errm, int errm_len);
@@ -146,6 +148,9 @@ static int column_series_scratch(beom_engine *E, Recorder &R, int cnt, int ncols
 static void launch_column_series(beom_engine *E, int tstp);
 static int tracer_column_series_scratch(beom_engine *E, Recorder &R, int cnt, int ncols, char *errm, int errm_len);
 static void launch_tracer_column_series(beom_engine *E, int tstp);
+static int maps_scratch(beom_engine *E, Recorder &R, int cnt, int nlines, char *errm, int errm_len);
+static void launch_maps(beom_engine *E, int tstp);
+static int maps_lines(const beom_engine *E);
 constexpr RecorderKind kSeries{2, [](int, int nlay, int level) { return beom_series_count(nlay, level); },
     series_scratch, launch_series, nullptr,
     "beom_download_series: the handle keeps no series (beom_set_series)",
@@ -168,6 +173,10 @@ constexpr RecorderKind kTracerColumnSeries{3, beom_tracer_series_count,
     "beom_download_tracer_column_series: the handle keeps no tracer column series (beom_set_tracer_column_series)",
     "beom_step: steps %d..%d would write %lld records of the tracer column series (stride %d) but the recorder holds %lld of %d: "
     "empty it with beom_download_tracer_column_series, or take fewer steps per call", true, "tracer column series"};
+constexpr RecorderKind kMaps{3, beom_maps_count, maps_scratch, launch_maps, nullptr,
+    "beom_download_maps: the handle keeps no maps (beom_set_maps)",
+    "beom_step: steps %d..%d would write %lld records of the maps (stride %d) but the recorder holds %lld of %d: "
+    "empty it with beom_download_maps, or take fewer steps per call", false, nullptr, maps_lines};
 struct Recorder {
     const RecorderKind *kind;
     int level = 0, stride = 1, nrec = 0, jlo = 1, rows = 0;      // local rows jlo .. jlo+rows-1
@@ -321,6 +330,11 @@ struct beom_engine {
     // tracer column series (beom_set_tracer_column_series; beom_tracer_column_series.h): a recorder [nrec][L][ntrc*nlay*2*level]
     // whose lines are the columns, with level, stride, row window and scratch of its own
     Recorder tcser{&kTracerColumnSeries};
+    // maps (beom_set_maps; beom_maps.h): a recorder [nrec][cnt][Mc][Lc] of sums over aligned blocks of 2^maps_logb cells a
+    // side, whose lines are the Mc * Lc blocks; no scratch
+    Recorder maps{&kMaps};
+    int maps_logb = 0;
+    long long map_launches = 0;
     int tcser_batch_opt = 0;           // option "tracer_column_series_batch": 64-column chunks per launch (0 = by the bound on the scratch)
     // forcing in time (beom_set_forcing; beom_forcing.h): frc[0] the wind stress, frc[1] hdot; what beom_create gave, to
     // return to when a set is cleared; a body force of exactly -0 (it bars the folded stress, see derive_forcing_flags)
@@ -684,7 +698,7 @@ int beom_destroy(beom_handle E) {
     if (!E) return 0;
     (void)hipSetDevice(E->device);
     if (E->stream) (void)hipStreamSynchronize(E->stream);
-    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs, &E->cser.allocs, &E->tcser.allocs, &E->frc[0].allocs, &E->frc[1].allocs}) free_list(*l);
+    for (std::vector<void *> *l : {&E->allocs, &E->trc_allocs, &E->trc_mix_allocs, &E->trc_vmix_allocs, &E->flt_allocs, &E->mom.allocs, &E->tmom.allocs, &E->harm.acc.allocs, &E->ser.allocs, &E->tser.allocs, &E->cser.allocs, &E->tcser.allocs, &E->maps.allocs, &E->frc[0].allocs, &E->frc[1].allocs}) free_list(*l);
     if (E->stage) (void)hipFree(E->stage);
     if (E->timer) { for (hipEvent_t ev : E->timer->ev) (void)hipEventDestroy(ev); delete E->timer; }
     if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
@@ -1353,7 +1367,7 @@ static void one_step(beom_engine *E, const StepPlan &p, int flt = -1) {
     if (!E->mom_by_caller && accum_due(E->mom, tstp)) launch_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->tmom, tstp)) launch_tracer_moments(E, tstp);
     if (!E->mom_by_caller && accum_due(E->harm.acc, tstp)) launch_harmonics(E, tstp, p.ctim);
-    for (const Recorder *R : {&E->ser, &E->tser, &E->cser, &E->tcser})
+    for (const Recorder *R : {&E->ser, &E->tser, &E->cser, &E->tcser, &E->maps})
         if (!R->by_caller && recorder_due(*R, tstp)) R->kind->launch(E, tstp);
 }
 
@@ -1389,7 +1403,7 @@ int beom_step(beom_handle E, int tstp_first, int nsteps, double tres, double dtd
         !beom_recorder::holds(tstp_first, nsteps, E->flt_stride, E->flt_rec_tstp.size(), E->flt_nrec, errm, errm_len,
                               "beom_step: steps %d..%d would write %lld float records (stride %d) but the recorder holds %lld of %d: "
                               "empty it with beom_download_float_track, or take fewer steps per call")) return -3;
-    for (const Recorder *R : {&E->ser, &E->tser, &E->cser, &E->tcser})
+    for (const Recorder *R : {&E->ser, &E->tser, &E->cser, &E->tcser, &E->maps})
         if (R->level > 0 && !R->by_caller &&
             !beom_recorder::holds(tstp_first, nsteps, R->stride, R->tstp.size(), R->nrec, errm, errm_len, R->kind->overflow)) return -3;
     HIP_TRY(hipSetDevice(E->device));
@@ -1726,7 +1740,7 @@ static int recorder_set(beom_engine *E, Recorder beom_engine::*which, const char
         set_err(errm, errm_len, "%s: a handle on a band of rows keeps no %s (a column's tree crosses the bands)", who, K.what);
         return -6;
     }
-    if (!K.columns && level > 0 && row_tree(d.L).nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
+    if (!K.columns && !K.lines && level > 0 && row_tree(d.L).nchp2 / 64 > kIntegralMaxGroups) { set_err(errm, errm_len, "%s: rows of more than %d columns", who, 64 * 64 * kIntegralMaxGroups); return -4; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
     recorder_free(R);
@@ -1734,6 +1748,7 @@ static int recorder_set(beom_engine *E, Recorder beom_engine::*which, const char
     const int cnt = K.count(E->ntrc, d.nlay, level);
     const int wlo = jlo, whi = jlo + nrows - 1;
     if (K.columns) { jlo = 1; nrows = d.L; }          // (the lines of the record are the columns)
+    if (K.lines) { jlo = 1; nrows = K.lines(E); }     // (the maps: its blocks)
     int rc = K.scratch(E, R, cnt, nrows, errm, errm_len);
     if (!rc) rc = alloc_aligned(E, R.allocs, &R.rec, (size_t)nrec * nrows * cnt, errm, errm_len);
     if (rc) { recorder_free(R); return rc; }
@@ -1796,6 +1811,32 @@ int beom_sample_tracer_column_series(beom_handle E) { return recorder_sample(E, 
 int beom_download_tracer_column_series(beom_handle E, double *cols, int *tstp, int *count, char *errm, int errm_len) {
     return recorder_download(E, &beom_engine::tcser, cols, tstp, count, errm, errm_len);
 }
+// Maps (beom_maps.h): the block edge is checked here and kept beside the recorder; the rest is the recorders' own.
+int beom_maps_count(int ntrc, int nlay, int level) {
+    return level < 1 ? 0 : 1 + (level >= 2 ? 6 : 3) * nlay + (level >= 3 ? ntrc * nlay : 0);
+}
+int beom_set_maps(beom_handle E, int level, int block, int stride, int nrec, char *errm, int errm_len) {
+    if (!E) { set_err(errm, errm_len, "null handle"); return -1; }
+    int logb = 0;
+    while (logb < kMapMaxLog && (1 << logb) < block) ++logb;
+    if (level < 0 || level > kMaps.max_level || (level > 0 && (block < 2 || block != (1 << logb) || stride < 1 || nrec < 1))) {
+        set_err(errm, errm_len, "beom_set_maps: level %d, block %d, stride %d, %d records (level 0..%d, block a power of two in 2..%d, "
+                                "stride >= 1, records >= 1)", level, block, stride, nrec, kMaps.max_level, 1 << kMapMaxLog);
+        return -3;
+    }
+    if (level >= 3 && E->ntrc < 1) { set_err(errm, errm_len, kTracerSeries.no_tracer, "beom_set_maps"); return -3; }
+    if (level > 0 && (E->d.slab || E->d.joff != 0 || E->d.Mg != E->d.M)) {
+        set_err(errm, errm_len, "beom_set_maps: a handle on a band of rows keeps no maps (a block's tree must not cross a seam, and "
+                                "nothing aligns the seams to the block edge yet)");
+        return -6;
+    }
+    if (level > 0) E->maps_logb = logb;       // (before the recorder is sized: maps_lines)
+    return recorder_set(E, &beom_engine::maps, "beom_set_maps", level, stride, nrec, 1, E->d.M, false, errm, errm_len);
+}
+int beom_sample_maps(beom_handle E) { return recorder_sample(E, &beom_engine::maps); }
+int beom_download_maps(beom_handle E, double *maps, int *tstp, int *count, char *errm, int errm_len) {
+    return recorder_download(E, &beom_engine::maps, maps, tstp, count, errm, errm_len);
+}
 int beom_sample_series(beom_handle E) { return recorder_sample(E, &beom_engine::ser); }
 int beom_sample_tracer_series(beom_handle E) { return recorder_sample(E, &beom_engine::tser); }
 
@@ -1828,7 +1869,7 @@ int beom_set_tracers(beom_handle E, int ntrc, char *errm, int errm_len) {
     if (ntrc > 0 && E->lid) { set_err(errm, errm_len, "beom_set_tracers: rgld = 1 changes the thickness in the lid's misfit epilogue (private_mod.f95:1648-1700), which the tracer scheme does not follow"); return -6; }
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
-    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); recorder_free(E->tser); recorder_free(E->tcser); }        // (their arrays have the tracers' shape)
+    if (ntrc != E->ntrc) { accum_free(E->tmom); free_tracer_mixing(E); free_tracer_vmixing(E); recorder_free(E->tser); recorder_free(E->tcser); if (E->maps.level >= 3) recorder_free(E->maps); }        // (their arrays have the tracers' shape)
     free_tracers(E);
     if (ntrc == 0) return 0;
     E->ntrc = ntrc;
@@ -2567,6 +2608,10 @@ int beom_info(beom_handle E, const char *what) {
     if (!strcmp(what, "tracer_column_series_records")) return (int)E->tcser.tstp.size();
     if (!strcmp(what, "column_series")) return E->cser.level;
     if (!strcmp(what, "column_series_records")) return (int)E->cser.tstp.size();
+    if (!strcmp(what, "maps")) return E->maps.level;
+    if (!strcmp(what, "maps_block")) return E->maps.level > 0 ? 1 << E->maps_logb : 0;
+    if (!strcmp(what, "maps_records")) return (int)E->maps.tstp.size();
+    if (!strcmp(what, "map_launches")) return (int)std::min<long long>(E->map_launches, 2000000000ll);      // all calls so far
     if (!strcmp(what, "series")) return E->ser.level;
     if (!strcmp(what, "series_records")) return (int)E->ser.tstp.size();
     if (!strcmp(what, "harmonics")) return E->harm.nfreq;
@@ -2704,5 +2749,30 @@ static void launch_tracer_column_series(beom_engine *E, int tstp) {
         hipLaunchKernelGGL(k_tracer_column_finish<kColFinishLevels>, dim3((unsigned)((ncols + BEOM_BLOCK - 1) / BEOM_BLOCK), (unsigned)cnt), dim3(BEOM_BLOCK), 0,
                            E->stream, (const double *)R.part, rec + (size_t)c0 * 64 * cnt, cnt, nq, colpad, ncols, nblk, nblkp2);
     }
+    R.tstp.push_back(tstp);
+}
+
+// ---- maps (beom_maps.h): behind the tracer column series', for the same reason --------------------------------------------
+static int maps_lines(const beom_engine *E) {
+    const int B = 1 << E->maps_logb;
+    return ((E->d.M + B - 1) / B) * ((E->d.L + B - 1) / B);
+}
+// A block is finished inside one wavefront: the maps need the cell map and the frame's wraps, and no scratch.
+static int maps_scratch(beom_engine *E, Recorder &, int, int, char *errm, int errm_len) { return ensure_cellmap(E, errm, errm_len); }
+// one record of the maps (beom_maps.h) of the fields as they stand into the next free slot, under step tstp: one launch
+static void launch_maps(beom_engine *E, int tstp) {
+    const DevView &d = E->d;
+    Recorder &R = E->maps;
+    const int B = 1 << E->maps_logb, Lc = (d.L + B - 1) / B, Mc = (d.M + B - 1) / B, nch = (d.L + 63) / 64;
+    const int cnt = beom_maps_count(E->ntrc, d.nlay, R.level);
+    double *rec = R.rec + R.tstp.size() * (size_t)R.rows * cnt;
+    const int32_t *map = E->dense ? nullptr : E->integ_cellmap;
+    pick_int<1, 3>(R.level, [&](auto lv) {
+        pick([&](auto dense) {
+            hipLaunchKernelGGL((k_map_blocks<dense, lv>), dim3((unsigned)((nch + kMapWaves - 1) / kMapWaves), (unsigned)Mc), dim3(BEOM_BLOCK), 0,
+                               E->stream, d, (const double *)E->trc_q, E->ntrc, E->maps_logb, E->integ_xper, E->integ_yper, map, rec, Lc, Mc);
+        }, E->dense);
+    });
+    ++E->map_launches;
     R.tstp.push_back(tstp);
 }

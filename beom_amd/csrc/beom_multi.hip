@@ -1618,6 +1618,21 @@ int beom_multi_download_tracer_column_series(beom_multi_handle M, double *, int 
     return column_series_refused(M, "beom_multi_download_tracer_column_series", errm, errm_len, "tracer ", "tracer_");
 }
 
+// Maps (beom_maps.h): a block's tree must not cross a seam between bands, and nothing places the seams on multiples of the
+// block edge yet.  Refused on every handle on bands, whatever it was created from.
+static int maps_refused(beom_multi *M, const char *who, char *errm, int errm_len) {
+    if (!M) { m_err(errm, errm_len, "null handle"); return -1; }
+    m_err(errm, errm_len, "%s: a handle on bands keeps no maps (a block's tree must not cross a seam between bands, and nothing "
+                          "aligns the seams to the block edge yet); use a single handle (beom_set_maps)", who);
+    return -6;
+}
+int beom_multi_set_maps(beom_multi_handle M, int, int, int, int, char *errm, int errm_len) {
+    return maps_refused(M, "beom_multi_set_maps", errm, errm_len);
+}
+int beom_multi_download_maps(beom_multi_handle M, double *, int *, int *, char *errm, int errm_len) {
+    return maps_refused(M, "beom_multi_download_maps", errm, errm_len);
+}
+
 int beom_multi_upload_local(beom_multi_handle M, const beom_state *win, const beom_state *orphan, char *errm, int errm_len) {
     if (!M || !win) { m_err(errm, errm_len, "null argument"); return -1; }
     if (!M->local_mode) { m_err(errm, errm_len, "beom_multi_upload_local: this handle was created from global arrays"); return -3; }

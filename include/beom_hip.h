@@ -703,6 +703,43 @@ int beom_set_column_series(beom_handle h, int level, int stride, int nrec, int j
 int beom_sample_column_series(beom_handle h);
 int beom_download_column_series(beom_handle h, double *cols, int *tstp, int *count, char *errm, int errm_len);
 
+/* ---- Maps: a record of sums over aligned B x B blocks of cells per sampled step, kept on the device (no reference routine).
+ * The picture in time: an animation of interface height or dye, a Hovmoeller diagram of an arbitrary section, a map of kinetic
+ * energy every few steps, B*B times smaller than the state and without a download of it.
+ * L = lm+1, M = mm+1; B = block, a power of two in 2..64; Lc = ceil(L/B), Mc = ceil(M/B).  Block (I, J) covers
+ * i = (I-1)B+1 .. IB and j = (J-1)B+1 .. JB on the GLOBAL indices.  A position holds +0.0 unless it is live; the integrals'
+ * live rule applies: not live is a position past L or M, one without a packed cell (land), the sentinel, and the duplicated
+ * column lm+1 of a frame periodic in x resp. row mm+1 of one periodic in y.
+ * Entries per block, cnt = beom_maps_count(ntrc, nlay, level):
+ *   k = 0: n, the sum of 1.0 over the block's live cells (exact in any order): what a caller divides by.
+ *   Level 1, per layer l at k = 1 + (l-1)*E + m, E = 3 at level 1 and 6 at level 2 and above:
+ *     m = 0: h, the term mk_n * hlay (the integrals' vol term);  m = 1: u, the cell's own u;  m = 2: v, the cell's own v.
+ *   Level 2 adds  m = 3: ke, the term mk_u*((u*u)*hcu) + mk_v*((v*v)*hcv) (the integrals' ke term);  m = 4: hu, the stored
+ *     transport h_u;  m = 5: hv, the stored transport h_v.
+ *   Level 3 adds the content q of tracer t and layer l at k = 1 + 6*nlay + t*nlay + (l-1); -3 on a handle without tracers, and
+ *     beom_set_tracers with another count frees a level-3 recorder (as it frees the tracer series).
+ * Order of summation, which is the contract: within a block, first each column's B rows go through the pairwise tree over the
+ * row offset in the block (level k+1 adds elements 2m and 2m+1 of level k), then the B column sums go through the pairwise
+ * tree over the column offset.  Blocks are aligned and B is a power of two: a complete binary tree whose only padding is the
+ * +0.0 of the positions that are not live, which is added, not skipped.  No atomics; the bits do not depend on the handle kind.
+ * Layout of a record: maps[(k*Mc + (J-1))*Lc + (I-1)], an image per entry; beom_download_maps gives maps[n][cnt][Mc][Lc].
+ * Semantics as the series': a record is written behind every step with tstp % stride == 0, where the series' sample sits.
+ * beom_step refuses with -3, before launching anything, a call whose steps would overflow the recorder (the message names
+ * beom_download_maps).  beom_sample_maps: one record by hand under the number of the handle's last step; -3 without a recorder
+ * or on a full one.  beom_download_maps copies the filled records (oldest first) and their steps, then sets the count to 0;
+ * any of maps, tstp, count may be NULL; -3 without maps.  Uploads do not empty the recorder.  beom_set_maps: level 0 frees (the
+ * other arguments are then not looked at); other arguments reallocate and empty; between steps only; -3 for a level outside
+ * 0..3, a block that is no power of two in 2..64, stride < 1 or nrec < 1.  One launch per record and no scratch: a block is
+ * finished inside one wavefront.  A handle without maps launches exactly what it launched before.  Every single handle keeps
+ * them: dense, embedded, the table path, variant = 1, rigid lid, svis > 0, open boundaries; level 3 wherever tracers are
+ * allowed.  beom_info: "maps" (the level), "maps_block" (B; 0 without maps), "maps_records" (records held), "map_launches".
+ * Handles on bands refuse with -6 (beom_multi_*; a handle that is a band of rows): a block's tree must not cross a seam, and
+ * nothing aligns the seams to B yet.  The Fortran host keeps none. */
+int beom_maps_count(int ntrc, int nlay, int level);      /* 1 + 3*nlay;  level 2: 1 + 6*nlay;  level 3: 1 + 6*nlay + ntrc*nlay;  level 0: 0 */
+int beom_set_maps(beom_handle h, int level, int block, int stride, int nrec, char *errm, int errm_len);
+int beom_sample_maps(beom_handle h);
+int beom_download_maps(beom_handle h, double *maps, int *tstp, int *count, char *errm, int errm_len);
+
 /* ---- Tracer series: a record per sampled step of the tracers' row inventories, variance, face fluxes and bounds, kept on the
  * device (no reference routine): how much of a tracer is where, how fast it crosses a latitude, how quickly its variance is
  * mixed away and whether it has left its bounds, without a download.  A recorder of its own beside the series, as the tracer
@@ -1060,6 +1097,10 @@ int beom_multi_download_series(beom_multi_handle m, double *rows, int *tstp, int
 /* Column series (see beom_set_column_series): both refuse with -6 and say why; a column's tree crosses the bands. */
 int beom_multi_set_column_series(beom_multi_handle m, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len);
 int beom_multi_download_column_series(beom_multi_handle m, double *cols, int *tstp, int *count, char *errm, int errm_len);
+
+/* Maps (see beom_set_maps): both refuse with -6 and say why; a block's tree must not cross a seam between bands. */
+int beom_multi_set_maps(beom_multi_handle m, int level, int block, int stride, int nrec, char *errm, int errm_len);
+int beom_multi_download_maps(beom_multi_handle m, double *maps, int *tstp, int *count, char *errm, int errm_len);
 
 /* Tracer column series (see beom_set_tracer_column_series): both refuse with -6 and say why; a column's tree crosses the bands. */
 int beom_multi_set_tracer_column_series(beom_multi_handle m, int level, int stride, int nrec, int jlo, int jhi, char *errm, int errm_len);

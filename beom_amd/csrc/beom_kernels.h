@@ -84,7 +84,14 @@ __device__ __forceinline__ void body_update_h(const C &c, const DevView &d, doub
             rhsi = ((1.5 + d.beta) * rs_3 - (0.5 + 2.0 * d.beta) * r2 + d.beta * r1) * d.dt * gene
                  + rs_3 * d.dt * (1.0 - gene);
         } else {
-            rhsi = rs_3 * d.dt;               // (..)*dt*0 + rs_3*dt*(1-0)
+            // (..)*dt*0 + rs_3*dt*(1-0) = (+-0) + rs_3*dt: rs_3*dt itself unless that is an exact zero — only those lanes
+            // (dry cells, whose rs_3 is a zero with the sign hdot gave it) read rs[0] for the sign of the result
+            rhsi = rs_3 * d.dt;
+            if (rhsi == 0.0) {
+                const double r1 = LL(d.rs[0], ipnt, ilay);
+                rhsi = ((1.5 + d.beta) * rs_3 - (0.5 + 2.0 * d.beta) * r2 + d.beta * r1) * d.dt * gene
+                     + rs_3 * d.dt * (1.0 - gene);
+            }
         }
         hold = hold + rhsi;
         // unforced: hfor*0 + (1-0)*hold with hfor = fnud_n >= +0  ==  (+0) + hold (turns -0 into +0)

@@ -164,6 +164,28 @@ def test_a_cyclic_set_whose_period_is_seven_steps():
     assert not same_bits(want["u"], other["u"]), "the period changed nothing"
 
 
+def test_a_negative_hdot_on_dry_cells_of_a_nudged_frame_keeps_the_oracles_zeros():
+    """Steps 1-3 (gene = 0) on the sill with sponges: its dry margin cells start with a thickness of -0.0 north of row 125,
+    and the frames bring a negative hdot to about half of them, so rs_3 = (hdot)*mk_n is -0.0 there.  The reference adds
+    (..)*dt*0 = +0.0 to rs_3*dt before the thickness: the nudged form of update_h keeps +0.0 as the oracle does."""
+    import addons_kit as K
+    f = K.frame("sill_sponges")
+    kit = K.Kit(f, seed=2)
+    sets = {"hdot": kit.hdot}
+    h0, dry = np.asarray(f.hlay), np.asarray(f.mk_n)[None, :] < 0.5
+    hit = dry & (h0 == 0.0) & np.signbit(h0) & (kit.hdot[1][0] < 0.0)
+    hit[:, 0] = False
+    assert hit.sum() >= 20 and np.any(f.nudg[0] != 0.0), "no dry cell with a -0 thickness under a negative hdot: nothing tested"
+    e = capi.Engine(f)
+    _give(e, sets)
+    for first, k in ((1, 1), (2, 1), (3, 1), (4, NSTEPS - 3)):
+        e.step(first, k)
+        want = FC.oracle_run(f, 0, sets, first + k - 1).state()
+        assert not np.signbit(want["hlay"][hit]).any()
+        _same_state(e.download(), want, ("sill_sponges", first + k - 1), keys=("hlay", "h_u", "h_v", "rs_h"))      # what update_h writes, and the transports built on it
+    e.close()
+
+
 # ---- 3. the folded stress -----------------------------------------------------------------------------------------------------------
 def test_the_stress_stays_folded_while_the_frames_vary():
     g, f = _golden("stommel_24x16")

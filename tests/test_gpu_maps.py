@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import maps_ref as MR
+import rough_inputs as RI
 from beom_amd import capi, inputs as I
 from beom_amd.grid import read_input_data
 from helpers import Golden, same_bits
@@ -71,8 +72,10 @@ def _same_views(got, k, want, ntrc, nl, level, what):
 
 
 # ---- 1. levels 1 and 2 on each handle kind ------------------------------------------------------------------------------------
+# (the block edge is a run-time argument that drives both the tree over a block's rows and the cross-lane steps over its
+# columns: one frame meets every edge)
 RECORD_CASES = [(name, B) for name in ("jet_xyper_2l", "island_ragged_3l", "closed_12l", "soliton_xper", "wide_67_chunks")
-                for B in (2, 8, 64)] + [("smaller_than_a_block", 64)]
+                for B in (2, 8, 64)] + [("smaller_than_a_block", 64)] + [("island_ragged_3l", B) for B in (4, 16, 32)]
 
 
 @pytest.mark.parametrize("level", [1, 2])
@@ -229,6 +232,42 @@ def test_division_into_calls_and_stride():
     assert e.info("maps") == 0 and e.info("maps_block") == 0
     assert _refusal(e.download_maps, -3) == NONE
     e.close()
+
+
+@pytest.mark.parametrize("config", ["jet_xyper_2l", "island_ragged_3l"])
+def test_rough_state_by_hand_at_every_block_edge(config):
+    """The rough state of rough_inputs as uploaded (no step) on frame 321 x 50, where interior waves exist: every block edge
+    2..64 at level 2 on the dense or embedded handle and on the table path equals the restatement and differs from the
+    record with h_u and h_v swapped.  jet_xyper_2l: values put into the duplicated column and row (the steps leave +0 there)
+    contribute +0.0."""
+    g = RI.rough_fields(RI.base_fields(config, "321x50"), 1)
+    p, nl = g.p, g.p.nlay
+    dup = MR.duplicates(g)
+    dup[0] = False
+    assert dup.any() == (config == "jet_xyper_2l")
+    for k, val in (("u", 0.75), ("v", -1.25), ("h_u", 1.5), ("h_v", -2.5)):
+        setattr(g, k, np.where(dup[None, :], val, getattr(g, k)))
+    for dense_hint in (1, 0):
+        e = capi.Engine(g, dense_hint=dense_hint)
+        assert bool(e.is_dense) == bool(dense_hint) and e.is_embedded == (config == "island_ragged_3l" and dense_hint == 1)
+        st = e.download(FIELDS)
+        for k in FIELDS:
+            assert same_bits(st[k], getattr(g, k)), k
+        for B in (2, 4, 8, 16, 32, 64):
+            e.set_maps(2, B, 1, 1)
+            e.sample_maps()
+            got = e.download_maps()
+            assert list(got["tstp"]) == [0] and got["block"] == B
+            want = MR.record(g, st, 2, B)
+            assert np.isfinite(want).all()
+            assert same_bits(got["raw"][0], want), (config, dense_hint, B)
+            assert not same_bits(got["raw"][0], MR.record(g, dict(st, h_u=st["h_v"], h_v=st["h_u"]), 2, B)), (config, dense_hint, B)
+            _same_views(got, 0, want, 0, nl, 2, (config, dense_hint, B))
+            assert got["u"][0].any() and got["v"][0].any() and got["hu"][0].any() and got["hv"][0].any() and got["ke"][0].any()
+            if config == "jet_xyper_2l" and B <= 8:           # (no land, no wall: every block of an interior wave carries transport)
+                inner = got["hu"][0][:, :(p.mm // B), :(p.lm // B)]
+                assert np.all(inner != 0.0) and np.all(inner[:, :, 1:] != inner[:, :, :-1])
+        e.close()
 
 
 # ---- 5. overflow and bad arguments --------------------------------------------------------------------------------------------

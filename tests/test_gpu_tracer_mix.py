@@ -15,6 +15,7 @@ import rough_inputs as RI
 import tracer_mix_ref as TM
 import tracers_limited_ref as TL
 import tracers_ref as T
+from addons_kit import mix_coefficients
 from beom_amd import capi, inputs as I
 from helpers import STATE, Golden, maxrel, same, same_bits, tile_geometry
 from test_gpu_biharm_tiled import CASES
@@ -44,17 +45,10 @@ def _tracers3(f):
 
 
 def _coefficients(p):
-    """kappa, decay, source [3, nlay]: the uniform tracer diffuses at the cap; the patchy one with another kappa in every
-    layer, a decay in layer 1 and a source in the others; the third with decay and source alone."""
-    cap, dt, nl = TM.kappa_cap(p), float(p.dt), p.nlay
-    kappa, decay, source = np.zeros((NTRC, nl)), np.zeros((NTRC, nl)), np.zeros((NTRC, nl))
-    kappa[0] = cap
-    kappa[1] = cap * (0.9 - 0.6 * np.arange(nl) / max(nl - 1, 1))
-    decay[1, 0] = 0.05 / dt
-    source[1, 1:] = 0.02 / dt
-    decay[2] = 0.03 / dt
-    source[2] = 0.01 / dt
-    return kappa, decay, source
+    """kappa, decay, source [3, nlay] (addons_kit.mix_coefficients, which the kit of every add-on shares): the uniform tracer
+    diffuses at the cap; the patchy one with another kappa in every layer, a decay in layer 1 and a source in the others; the
+    third with decay and source alone."""
+    return mix_coefficients(p, NTRC)
 
 
 def _engine(f, dense_hint=1, scheme=1, mixing=True):

@@ -16,6 +16,7 @@ import rough_inputs as RI
 import tracer_mix_ref as TM
 import tracer_vmix_ref as TV
 import tracers_ref as T
+from addons_kit import kappa_v_table
 from beom_amd import capi, inputs as I
 from beom_amd.grid import read_input_data
 from helpers import STATE, Golden, maxrel, same, same_bits, tile_geometry
@@ -38,13 +39,10 @@ def _no_geometry_leak():
 
 
 def _kappa_v(p, ntrc=NTRC):
-    """[ntrc, nlay-1] in m2/s: another value for every tracer and interface, from 1e-5 (explicit would do) to dt kappa_v /
-    hbar^2 far beyond any explicit limit; tracer 0 (the uniform one) gets the largest; the last tracer's row has a zero."""
-    nk = p.nlay - 1
-    kv = 10.0 ** (-5.0 + 6.0 * ((np.arange(ntrc)[:, None] * 5 + np.arange(nk)[None] * 3) % 7) / 6.0)
-    kv[0] = 25.0 * (1.0 + np.arange(nk))
-    kv[ntrc - 1, nk // 2] = 0.0
-    return kv
+    """[ntrc, nlay-1] in m2/s (addons_kit.kappa_v_table, which the kit of every add-on shares): another value for every
+    tracer and interface, from 1e-5 (explicit would do) to dt kappa_v / hbar^2 far beyond any explicit limit; tracer 0 (the
+    uniform one) gets the largest; the last tracer's row has a zero."""
+    return kappa_v_table(p, ntrc)
 
 
 def _moved(kv, got, plain, what):
